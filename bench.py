@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X DDalphaAMG hot path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Headline (`metric`, `value`, `roofline`): a "step" is one fine Wilson-Clover apply (d_plus_clover_float, reference
 src/dirac_generic.c:159-277) over a 32^4 local lattice per GPU of synthetic random SU(3) links (BASELINE.json quotes the
@@ -30,6 +30,7 @@ FLOP_PER_SITE = 1920          # reference model, src/init_generic.c:59,61
 BYTES_PER_SITE_F32 = 816      # 4 B x (24 in + 24 out + 72 links + 84 clover reals), SURVEY.md 8(d)
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 GAUGE_SEED, GAUGE_EPS = 20260101, 0.35   # near-unit links exp(i eps H): a system on which the multigrid has work to do
+DUMP_BYTES, DUMP_SEED = 48 << 20, 20260101   # --dump-outputs: array bytes over all ranks (under 64 MB with the .npy headers); sample seed
 
 
 def parse_args():
@@ -56,7 +57,27 @@ def parse_args():
                     help="N = 1 only: also run the PER-GPU problem of the N-GPU strong-scaling decomposition on this one GPU, every split "
                          "direction through the RCCL self-exchange (0: skip); printed as `rehearsal` next to `strong_scaling`")
     ap.add_argument("--leg-timeout", type=float, default=900.0, help="watchdog for the solve legs on N > 1 (seconds)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output vector of the last step as DIR/dirac_out.npy (DIR/dirac_out_rank<r>.npy "
+                         "on N > 1): [sites][12][2] in the vector's precision, every site while all ranks together stay within "
+                         f"{DUMP_BYTES >> 20} MiB, else the same seeded sample of sites in every run (see dump_output)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_output(path, y, precision, world):
+    """the result of the last timed apply as a caller of ctx.dirac_apply receives it (ctx download: [V][12][2] fp64, exact fp32
+    values for --precision 32, so stored as float32 then).  Larger than DUMP_BYTES / world per rank: the rows of a sorted sample
+    of sites drawn by a fixed seed, identical from run to run for the same lattice."""
+    import numpy as np
+    a = y.astype(np.float32 if precision == 32 else np.float64)
+    V = a.shape[0]
+    n = min(V, DUMP_BYTES // world // (a[0].size * a.itemsize))
+    if n < V:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(V, n, replace=False))]
+    np.save(path, np.ascontiguousarray(a))
 
 
 # ---- N > 1 without a launcher: the parent only starts and reaps the ranks ------------------------------------------
@@ -622,6 +643,10 @@ def main():
         t = torch.tensor([dt], device="cuda" if args.transport == "rccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump_output(os.path.join(args.dump_outputs, "dirac_out.npy" if world == 1 else f"dirac_out_rank{rank}.npy"),
+                    y.download(), args.precision, world)
 
     out = None
     if rank == 0:

@@ -2,12 +2,12 @@
 gauge configurations (read_conf, src/io.c:459-563) and spinor / test-vector files (vector_io :704-846,
 vector_io_single_file :951-1124, write_header :671-702), read and written by every process of a grid for its own part.
 The configuration format is pinned by the reference itself: it reads the files this code's Python twin writes
-(oracle/make_golden.py, ragged and 16^4 cases), and where the reference tree is present the writer reproduces its
-sample configuration byte for byte."""
-import os
+(oracle/make_golden.py, ragged and 16^4 cases), and the writer reproduces its sample configuration byte for byte
+(tests/golden/ref_4x4_conf.json)."""
+import hashlib, json, os
 import numpy as np
 import pytest
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from ddalphaamg_amd import api, dist as ddist
 
 GRIDS = [(1, 1, 1, 1), (2, 1, 1, 1), (1, 2, 1, 2), (2, 2, 2, 2)]
@@ -48,9 +48,9 @@ def test_configuration_layout_is_the_reference_layout(tmp_path, conf4):
     assert np.array_equal(np.frombuffer(raw[:16], dtype="<i4"), L)
     assert np.frombuffer(raw[16:24], dtype="<f8")[0] == plaq
     assert np.array_equal(np.frombuffer(raw[24:], dtype="<f8"), U.ravel())
-    ref = "/root/reference/conf/4x4x4x4b6.0000id3n1"
-    if os.path.exists(ref):        # the reference's own sample configuration, where its tree is mounted
-        assert open(ref, "rb").read() == raw
+    # the reference's own sample configuration, pinned by its size and SHA-256 (tests/golden/ref_4x4_conf.json)
+    ref = json.load(open(os.path.join(GOLDEN, "ref_4x4_conf.json")))
+    assert len(raw) == ref["bytes"] and hashlib.sha256(raw).hexdigest() == ref["sha256"]
 
 
 def test_configuration_errors(tmp_path, conf4):

@@ -4,6 +4,7 @@ driver launches it -- rehearsed with two processes on the one GPU through the ho
 device); and the failure behaviour: a rank that dies or hangs in the solve leg ends the job with a non-zero code, with the
 headline line still printed."""
 import json, os, subprocess, sys
+import numpy as np
 import pytest
 from launcher import torchrun
 
@@ -32,12 +33,16 @@ def check_common(d, n_gpus, steps, warmup, sites_per_gpu=32 ** 4):
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and r["achieved"] > 0
 
 
-def test_single_gpu_line():
-    r = subprocess.run([sys.executable, BENCH, "--steps", "50", "--warmup", "10", "--no-strong"],
+def test_single_gpu_line(tmp_path):
+    r = subprocess.run([sys.executable, BENCH, "--steps", "50", "--warmup", "10", "--no-strong", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = last_json_line(r.stdout)
     check_common(d, 1, 50, 10)
+    # --dump-outputs at the headline volume: a seeded sample of the 32^4 output vector, within 64 MB
+    assert os.listdir(tmp_path) == ["dirac_out.npy"] and os.path.getsize(tmp_path / "dirac_out.npy") <= 64 << 20
+    y = np.load(tmp_path / "dirac_out.npy")
+    assert y.dtype == np.float32 and y.shape[1:] == (12, 2) and 0 < y.shape[0] < 32 ** 4 and np.isfinite(y).all()
     assert d["roofline"]["frac"] > 0.4                       # north-star target: >= 40 % of the HBM roofline at 32^4
     c = d["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["value"] > 0 and c["cores"] >= 1 and c["sample"]
@@ -51,6 +56,27 @@ def test_single_gpu_line():
         assert abs(s["iterations"] - s["iterations_reference"]) <= 1
     if c["kind"] == "reference":
         assert c["solve"]["seconds"] > 0 and c["solve"]["iterations"] > 0 and c["solve"]["kind"] == "reference"
+
+
+@pytest.mark.parametrize("precision,tol", [(32, 2e-6), (64, 1e-13)])
+def test_dumped_output_is_the_operator_applied_to_the_bench_inputs(tmp_path, precision, tol):
+    """--dump-outputs on a lattice small enough to be written whole: --steps timed steps, and the output of the last one is
+    D x of bench.py's seeded inputs, against the CPU oracle"""
+    from conftest import relerr, splitmix_uniform
+    from oracle import orc
+    import bench
+    r = subprocess.run([sys.executable, BENCH, "--lattice", "8", "8", "8", "8", "--steps", "7", "--warmup", "3", "--precision", str(precision),
+                        "--no-solve", "--no-strong", "--no-cpu-baseline", "--rehearse", "0", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = last_json_line(r.stdout)
+    assert (d["steps"], d["warmup"]) == (7, 3) and d["ms_per_step"] > 0
+    y = np.load(tmp_path / "dirac_out.npy")
+    L = [8, 8, 8, 8]; V = 8 ** 4
+    assert y.dtype == (np.float32 if precision == 32 else np.float64) and y.shape == (V, 12, 2)
+    D, cl, _ = orc.gauge_to_operator(L, bench.synth_gauge_random(V, 20260101), 1, -0.1, 1.0)
+    phi = splitmix_uniform(V * 24, 1234).reshape(V, 12, 2)
+    assert relerr(y, orc.dirac_apply(L, D, cl, phi, precision)) < tol
 
 
 SMALL = ["--lattice", "16", "16", "16", "16", "--strong-lattice", "16", "16", "16", "16", "--steps", "5", "--warmup", "2",
