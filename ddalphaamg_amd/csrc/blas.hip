@@ -42,8 +42,6 @@ __global__ __launch_bounds__(64) void publish_kernel(const double* __restrict__ 
   if (threadIdx.x == 0) __hip_atomic_store(hseq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 void publish_to_host(const double* d_src, int n, ReduceWork& rw, hipStream_t st) {
-  static const bool dma = getenv("DDAMG_READBACK_DMA") != nullptr;   // the copy-engine form, for comparison
-  if (dma) { DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, d_src, sizeof(double) * n, hipMemcpyDeviceToHost, st)); return; }
   rw.seq++;
   hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, d_src, n, rw.h_result, rw.h_seq, rw.seq);
   DDAMG_HIP_CHECK(hipGetLastError());
@@ -52,18 +50,10 @@ __global__ __launch_bounds__(64) void upload_kernel(double* __restrict__ dst, co
   for (int i = threadIdx.x; i < n; i += 64) dst[i] = __hip_atomic_load(&hsrc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 void upload_coefficients(ReduceWork& rw, int n, hipStream_t st) {
-  static const bool dma = getenv("DDAMG_READBACK_DMA") != nullptr;
-  if (dma) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(rw.d_coef, rw.h_coef, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    DDAMG_HIP_CHECK(hipStreamSynchronize(st));   // h_coef is free again
-    return;
-  }
   hipLaunchKernelGGL(upload_kernel, dim3(1), dim3(64), 0, st, rw.d_coef, rw.h_coef, n);
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 void wait_published(ReduceWork& rw, hipStream_t st) {
-  static const bool dma = getenv("DDAMG_READBACK_DMA") != nullptr;
-  if (dma) { DDAMG_HIP_CHECK(hipStreamSynchronize(st)); return; }
   volatile unsigned long long* p = rw.h_seq;
   unsigned long long spins = 0;
   while (__atomic_load_n(p, __ATOMIC_ACQUIRE) != rw.seq) {

@@ -70,13 +70,11 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
   DDAMG_REQUIRE(ndev > 0, "no HIP device visible: the MI355X path has no CPU fallback");
   DDAMG_REQUIRE(p->device >= 0 && p->device < ndev, "device ordinal out of range");
   DDAMG_HIP_CHECK(hipSetDevice(p->device));
-  {
-    // the Krylov loops read one small result back per iteration: a host thread that spins on the completion signal sees it
-    // ~15 us earlier than one that sleeps (2 % of a 32^4 solve); one process per GPU owns its core anyway, as the
-    // reference's MPI ranks do.  Process-wide device flag; DDAMG_SYNC_SPIN=0 leaves the runtime's default.
-    const char* e = getenv("DDAMG_SYNC_SPIN");
-    if (!e || atoi(e) != 0) { (void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError(); }
-  }
+  // the Krylov loops read one small result back per iteration: a host thread that spins on the completion signal sees it
+  // ~15 us earlier than one that sleeps (2 % of a 32^4 solve); one process per GPU owns its core anyway, as the
+  // reference's MPI ranks do.  Process-wide device flag.
+  (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
+  (void)hipGetLastError();
   std::unique_ptr<ddamg_hip_ctx> c(new ddamg_hip_ctx);
   c->par = *p;
   for (int mu = 0; mu < 4; mu++) if (c->par.process_grid[mu] < 1 && c->par.process_grid[mu] != -1) { c->par.process_grid[mu] = 1; c->par.process_coords[mu] = 0; }
@@ -137,6 +135,7 @@ int ddamg_hip_destroy(ddamg_hip_ctx* c) {
   if (c->bicg_ready) { c->bicg32.release(); c->bicg64.release(); }
   if (c->p32_in) (void)hipFree(c->p32_in);
   if (c->p32_out) (void)hipFree(c->p32_out);
+  if (c->z64) (void)hipFree(c->z64);
   for (auto& lv : c->levels) if (lv->d_lex_of_site) (void)hipFree(lv->d_lex_of_site);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->clover_base) (void)hipFree(c->clover_base);
@@ -170,8 +169,6 @@ static double gauge_fields(ddamg_hip_ctx* c, const double* gauge_lex, int anti_p
                                       "(ddamg_hip_comm_init_rccl / ddamg_hip_comm_init_host / ddamg_hip_comm_init_mpi)");
     return gauge_to_operator_dist(g, c->comm, gauge_lex, anti_pbc, c->par.m0, c->par.csw, D_out, clover_out, c->stream);
   }
-  static const bool host_clover = getenv("DDAMG_HOST_CLOVER") != nullptr;
-  if (host_clover) return gauge_to_operator(g.L, gauge_lex, anti_pbc, c->par.m0, c->par.csw, D_out, clover_out);
   return gauge_to_operator_device(g.L, gauge_lex, anti_pbc, c->par.m0, c->par.csw, D_out, clover_out, c->stream);
 }
 

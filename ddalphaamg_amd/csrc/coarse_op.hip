@@ -442,11 +442,7 @@ template <typename T>
 bool CoarseOp<T>::block_minres(T* x, T* r, T* latest, const int* blocks, int nblocks, const BlockPlan& plan, int iters, double eps, hipStream_t st) const {
   const bool off = getenv("DDAMG_COARSE_SAP_UNFUSED") != nullptr;   // read at every call: tests switch it within one process
   const int np = 8 * nt_, BS = plan.block_sites;
-  size_t lds = 48 * sizeof(double) + sizeof(T) * 2 * np * ((size_t)2 * BS + (size_t)2 * plan.nitems);
-  // workgroups per CU (experiment knob): the couplings of a block are streamed once per MinRes step; with fewer blocks in flight
-  // the steps 2.. of a block may still find them in the Infinity Cache
-  static const int wg_per_cu = getenv("DDAMG_COARSE_SAP_WG_PER_CU") ? atoi(getenv("DDAMG_COARSE_SAP_WG_PER_CU")) : 0;
-  if (wg_per_cu > 0) lds = std::max(lds, (size_t)(160 * 1024 / wg_per_cu) - 1024);
+  const size_t lds = 48 * sizeof(double) + sizeof(T) * 2 * np * ((size_t)2 * BS + (size_t)2 * plan.nitems);
   if (off || plan.nitems == 0 || (size_t)BS * n_ > (size_t)BLOCK_MINRES_THREADS * BLOCK_MINRES_MAXE || lds > 150 * 1024) return false;
   if (nblocks <= 0) return true;
   const CoarseOpDev<T> op = dev();
@@ -547,10 +543,9 @@ static void launch_site(const CoarseOpDev<T>& op, T* out, const T* in, int s0, i
   int swz = (s1 - s0) >= 64 ? 1 : 0;   // measured at 48^4, three levels: 3 % on the whole solve
   // The couplings of a level (302 MB at 8^4 x 48) are streamed once per hopping term and are larger than the 256 MB
   // Infinity Cache: walked in the same direction every time, each launch evicts what the next one needs first.  Every
-  // second hopping term therefore starts where the previous one ended.
-  static const bool alternate = getenv("DDAMG_COARSE_SWEEP_SAME_WAY") == nullptr;   // 53.3 -> 51.0 us per hopping term at 8^4 x 48
+  // second hopping term therefore starts where the previous one ended (53.3 -> 51.0 us per hopping term at 8^4 x 48).
   static unsigned hop_count = 0;
-  if (alternate && (mode == MODE_HOP || mode == MODE_HOPINV || (mode == MODE_FULL && in_self)) && site_list == nullptr && (hop_count++ & 1u)) swz |= 2;
+  if ((mode == MODE_HOP || mode == MODE_HOPINV || (mode == MODE_FULL && in_self)) && site_list == nullptr && (hop_count++ & 1u)) swz |= 2;
 #define DDAMG_LAUNCH(NTV, MODEV) hipLaunchKernelGGL((coarse_site_kernel<T, NTV, MODEV>), grid, block, 0, st, out, in, op, s0, (T)ss, (T)sh, acc ? 1 : 0, site_list, dir_mask, mask_invert ? 1 : 0, swz, in_self)
 #define DDAMG_CASE(NTV) case NTV: \
     if (mode == MODE_FULL) DDAMG_LAUNCH(NTV, MODE_FULL); else if (mode == MODE_HOP) DDAMG_LAUNCH(NTV, MODE_HOP); \
@@ -571,14 +566,10 @@ template <typename T> void CoarseOp<T>::apply(T* out, const T* in, hipStream_t s
   // On a process grid the exchange travels while everything that does not need it is computed (the reference's order of
   // events, src/coarse_oddeven_generic.c:447-581: ghost_sendrecv, interior hopping terms, ghost_wait, the rest).
   const bool dist = arena_.active();
-  static const bool no_overlap = getenv("DDAMG_COARSE_NO_OVERLAP") != nullptr;
-  const bool overlap = dist && !no_overlap;
   if (dist) pack_and_begin(in, st);
-  if (dist && !overlap) arena_.exchange_finish(comm_, st);
-  static const bool twice = getenv("DDAMG_COARSE_APPLY_TWICE") != nullptr;
   static const int min_sites = getenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES") ? atoi(getenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES")) : 2048;
-  if (twice || V_ < min_sites) {   // small (coarsest) lattices sit in the Infinity Cache: the second read is free, the extra launch is not
-    if (overlap) {
+  if (V_ < min_sites) {   // small (coarsest) lattices sit in the Infinity Cache: the second read is free, the extra launch is not
+    if (dist) {
       launch_site<T>(dev(), out, in, 0, (int)h_interior_.size(), MODE_FULL, 1.0, -1.0, false, st, d_interior_);
       arena_.exchange_finish(comm_, st);
       launch_site<T>(dev(), out, in, 0, (int)h_boundary_.size(), MODE_FULL, 1.0, -1.0, false, st, d_boundary_);
@@ -589,19 +580,19 @@ template <typename T> void CoarseOp<T>::apply(T* out, const T* in, hipStream_t s
   }
   if (!bwd_) DDAMG_HIP_CHECK(device_alloc(&bwd_, sizeof(T) * 4 * (size_t)V_ * n_ * 2));
   const CoarseOpDev<T> op = dev();
-#define DDAMG_CASE(NTV) case NTV: if (overlap) hipLaunchKernelGGL((coarse_apply_once_kernel<T, NTV, true>), dim3(V_), dim3(320), 0, st, out, bwd_, in, op); \
+#define DDAMG_CASE(NTV) case NTV: if (dist) hipLaunchKernelGGL((coarse_apply_once_kernel<T, NTV, true>), dim3(V_), dim3(320), 0, st, out, bwd_, in, op); \
                                   else hipLaunchKernelGGL((coarse_apply_once_kernel<T, NTV, false>), dim3(V_), dim3(320), 0, st, out, bwd_, in, op); break;
   switch (nt_) {
     DDAMG_CASE(1) DDAMG_CASE(2) DDAMG_CASE(3) DDAMG_CASE(4) DDAMG_CASE(5) DDAMG_CASE(6) DDAMG_CASE(7) DDAMG_CASE(8)
     default: DDAMG_REQUIRE(false, "coarse operator: more than 64 dof per site are not supported");
   }
 #undef DDAMG_CASE
-  if (overlap) arena_.exchange_finish(comm_, st);
+  if (dist) arena_.exchange_finish(comm_, st);
   const size_t total = (size_t)V_ * n_ * 2;
   hipLaunchKernelGGL(coarse_apply_once_finish_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, bwd_, op);
   DDAMG_HIP_CHECK(hipGetLastError());
   // the forward terms across the process boundary that the first pass left out
-  if (overlap && n_fwd_off_ > 0)
+  if (dist && n_fwd_off_ > 0)
     launch_site<T>(op, out, in, 0, n_fwd_off_, MODE_HOP, 0.0, -1.0, true, st, d_fwd_off_sites_, d_fwd_off_mask_, false);
 }
 // coarse_apply_schur_complement_PRECISION (src/coarse_oddeven_generic.c:1162-1189) in two launches on a lattice ordered
@@ -615,9 +606,7 @@ template <typename T> void CoarseOp<T>::schur_fused(T* out, T* t, const T* in, h
 }
 template <typename T> void CoarseOp<T>::hop(T* out, const T* in, int s0, int s1, double sign, bool accumulate, hipStream_t st) const {
   DDAMG_REQUIRE(out != in, "coarse hopping term cannot run in place");
-  static const bool no_overlap = getenv("DDAMG_COARSE_NO_OVERLAP") != nullptr;
-  if (!arena_.active() || no_overlap) {
-    halo_exchange(in, st);
+  if (!arena_.active()) {
     launch_site<T>(dev(), out, in, s0, s1, MODE_HOP, 0.0, sign, accumulate, st);
     return;
   }

@@ -1,5 +1,5 @@
 // gauge_device.hip -- clover term and plaquette on the device, for the own lattice of a single process and for the
-// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them and keeps the host form).
+// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them).
 // Reference: compute_clover_term src/dirac.c:24-58, Q / Qdiff / set_clover :304-402, calc_plaq :568-622.
 // One thread per lexicographic site; links are read straight from the reference layout [V][4][3x3] complex fp64.
 #include "gauge.h"
@@ -156,7 +156,7 @@ static double clover_and_plaquette_on_device(const double* dU, const Lat& ext, c
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
   DDAMG_HIP_CHECK(hipFree(dC)); DDAMG_HIP_CHECK(hipFree(dP));
   double plaq = 0;
-  for (size_t i = 0; i < V; i++) plaq += hp[i];   // same summation order as the host code
+  for (size_t i = 0; i < V; i++) plaq += hp[i];
   return plaq;
 }
 }  // namespace

@@ -731,19 +731,17 @@ void Multigrid<T>::build_coarse_operator(int l) {
     const int max_batch = compact ? 64 : 256 / 5;
     // the batch workspace is allocated once per setup and kept until release_setup_workspace(): allocating and
     // freeing tens of GB for every build costs more than the build itself
-    static const bool no_slab = getenv("DDAMG_GALERKIN_NO_SLABS") != nullptr;
     if (!gal_W_) {
       size_t free_b = 0, total_b = 0;
       DDAMG_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
       gal_batch_ = 2 * N;
       while (gal_batch_ > 1 && (gal_batch_ > max_batch || sizeof(T) * gal_batch_ * (wcol + 5 * cs) > free_b / 2)) gal_batch_ = (gal_batch_ + 1) / 2;
       gal_slab_aggs_ = 0;
-      const char* force_slab = getenv("DDAMG_GALERKIN_SLAB_AGGS");   // tests: slabs of this many aggregates at any volume
-      static const bool whole = getenv("DDAMG_GALERKIN_WHOLE_LATTICE") != nullptr;   // round 2: slabs only when the columns do not fit
-      if ((gal_batch_ < 2 * N || force_slab || !whole) && 2 * N <= max_batch && !lv.fop->distributed() && !no_slab) {
-        // all columns do not fit next to each other for the whole lattice.  Fewer columns per pass starve the N dimension
-        // of the restriction GEMM (64^4: 6 of 48 columns, 30 of 240 fields, 4x the time); instead keep ALL columns and walk
-        // the lattice in slabs of whole aggregates -- D P and its restriction are local to an aggregate.
+      const char* force_slab = getenv("DDAMG_GALERKIN_SLAB_AGGS");   // tests: slabs of this many aggregates
+      if (2 * N <= max_batch && !lv.fop->distributed()) {
+        // keep ALL columns and walk the lattice in slabs of whole aggregates -- D P and its restriction are local to an
+        // aggregate.  Fewer columns per pass would starve the N dimension of the restriction GEMM (64^4: 6 of 48 columns, 30 of
+        // 240 fields, 4x the time).
         // The slab is no larger than what the bootstrap borrows (Nvec fine vectors) or 512 aggregates: the time of a build does
         // not depend on the slab size from 512 aggregates on, and memory that is never allocated need not be mapped -- the first
         // process on a freshly started box pays ~20-40 ms per GB of never-used device memory (docs/design/09_rounds_2_3.md)
@@ -755,7 +753,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
         const size_t budget = free_b / 2 > coarse_b + per_agg ? free_b / 2 - coarse_b : free_b - coarse_b - (free_b - coarse_b) / 8;
         gal_slab_aggs_ = (int)std::min<size_t>((size_t)nagg, std::max<size_t>(1, budget / per_agg));
         const size_t borrow = (sizeof(T) * (size_t)N * ws + per_agg - 1) / per_agg;      // aggregates whose slab holds Nvec fine vectors
-        if (!whole) gal_slab_aggs_ = (int)std::min<size_t>((size_t)gal_slab_aggs_, std::max<size_t>(borrow, 512));
+        gal_slab_aggs_ = (int)std::min<size_t>((size_t)gal_slab_aggs_, std::max<size_t>(borrow, 512));
         if (force_slab) gal_slab_aggs_ = std::max(1, std::min(atoi(force_slab), nagg));
         DDAMG_REQUIRE(per_agg * (size_t)gal_slab_aggs_ + coarse_b < free_b, "Galerkin construction: slab workspace does not fit the free device memory");
         gal_batch_ = 2 * N;
@@ -896,7 +894,7 @@ void Multigrid<T>::initial_setup_from(int l0) {
 // them makes -- restriction of its right-hand side, interpolation of its coarse correction -- are done for all of them at
 // once: P is read twice per iteration instead of 2 Nvec times (32^4, Nvec 24: 2 x 2.4 GB instead of 115 GB), the
 // restriction on the matrix cores (restrict_mfma_kernel, the Galerkin construction's kernel).  The coarse solves and the
-// smoother calls stay one vector at a time.  Borrows the Galerkin workspace between two builds; single process, fp32.
+// smoother calls stay one vector at a time.  Borrows the Galerkin workspace between two builds; fp32.
 template <typename T>
 bool Multigrid<T>::bootstrap_vcycles_batched() {
   const bool off = getenv("DDAMG_BOOTSTRAP_UNBATCHED") != nullptr;   // read at every call: tests switch it within one process
@@ -905,11 +903,8 @@ bool Multigrid<T>::bootstrap_vcycles_batched() {
   const int N = lv.nvec;
   const size_t ws = (size_t)24 * lv.g->V, cs = (size_t)nx.g->V * nx.n * 2;
   // (on a process grid as well: restriction and interpolation are local to the aggregates, which never straddle a process
-  // boundary; the coarse solves and smoother calls in between communicate as they do one vector at a time.
-  // DDAMG_BOOTSTRAP_BATCHED_SINGLE_PROCESS_ONLY restores the round-2 restriction to one process.)
-  static const bool single_only = getenv("DDAMG_BOOTSTRAP_BATCHED_SINGLE_PROCESS_ONLY") != nullptr;
+  // boundary; the coarse solves and smoother calls in between communicate as they do one vector at a time.)
   if (off || sizeof(T) != 4 || !gal_W_ || !gal_C_) return false;
-  if (single_only && (comm_ != nullptr || lv.fop->distributed())) return false;
   if (!Interpolation<T>::restrict_batch_available(lv.fip.agg_sites, N) || !Interpolation<T>::interpolate_batch_available(lv.fip.agg_sites, N, N)) return false;
   // the borrowed workspace holds `cap` fine vectors: all Nvec in a first setup; fewer next to a context that already holds its
   // solver workspace (64^4: 17 of 24), and then the interpolation + smoothing at the end goes through it in groups

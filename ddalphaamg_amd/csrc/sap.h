@@ -53,7 +53,7 @@ class SapSmoother {
   int* d_block_list_ = nullptr;
   std::vector<int*> d_color_blocks_;               // block indices per colour
   T* latest2_ = nullptr;                           // additive method: the other generation of block updates
-  // production shape (fp32, 4^4 blocks, multiplicative schedules): two blocks per workgroup, block-boundary couplings through
+  // production shape (fp32, 4^4 blocks, multiplicative schedules): one block per workgroup, block-boundary couplings through
   // face buffers (sap_pair.h).  faces_d_: projected faces of every block's latest update; faces_x_: of the iterate x
   bool odd_even_ = true;
   bool pair_ = false;

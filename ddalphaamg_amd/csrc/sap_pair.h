@@ -1,5 +1,5 @@
-// sap_pair.h -- the production form of the fine-level Schwarz block solve: fp32, 4^4 blocks (256 sites), TWO blocks per
-// 512-thread workgroup, block-boundary couplings through face buffers.  See sap_pair.hip for the design; sap.h for the
+// sap_pair.h -- the production form of the fine-level Schwarz block solve: fp32, 4^4 blocks (256 sites), one block per
+// 256-thread workgroup, block-boundary couplings through face buffers.  See sap_pair.hip for the design; sap.h for the
 // reference functions it implements (red_black_schwarz_PRECISION, block_solve_oddeven_PRECISION, local_minres_PRECISION,
 // (n_)block_PRECISION_boundary_op).
 #pragma once

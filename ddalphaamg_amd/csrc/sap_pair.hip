@@ -1,17 +1,16 @@
-// sap_pair.hip -- Schwarz block solve, production shape: fp32, 4^4 blocks, two blocks per workgroup.
+// sap_pair.hip -- Schwarz block solve, production shape: fp32, 4^4 blocks, one block per workgroup.
 //
 // Reference: red_black_schwarz_PRECISION src/schwarz_generic.c:1260-1431, block_solve_oddeven_PRECISION and
 // apply_block_schur_complement_PRECISION src/oddeven_generic.c:1317-1360, local_minres_PRECISION
 // src/linsolve_generic.c:985-1029, block_PRECISION_boundary_op / n_block_PRECISION_boundary_op src/schwarz_generic.c:743-971.
 //
 // What is different from sap_site_kernel (sap.hip), and why:
-//  * TWO BLOCKS PER 512-THREAD WORKGROUP WITH COMPLEMENTARY ROLES.  One thread owns one site and keeps its four links and
-//    its clover matrix (D_ee on even, D_oo^-1 on odd sites) in registers, so a CU holds two blocks.  The odd-even Schur
-//    complement alternates even-site and odd-site phases; even and odd sites of a block live in different wavefronts.
-//    With one block per 256-thread workgroup both workgroups of a CU put their even wavefronts on SIMD 0/1 and their odd
-//    ones on SIMD 2/3 (wavefront w of a workgroup goes to SIMD w mod 4), so in every phase two SIMDs idle while the other
-//    two run two wavefronts each.  Here wavefronts 0-3 (block A) are [even, even, odd, odd] and wavefronts 4-7 (block B)
-//    are [odd, odd, even, even]: in every phase each of the four SIMDs has exactly one active wavefront.
+//  * ONE BLOCK PER 256-THREAD WORKGROUP, TWO WORKGROUPS PER CU.  One thread owns one site and keeps its four links and its
+//    clover matrix (D_ee on even, D_oo^-1 on odd sites) in registers, so a CU holds two blocks.  The odd-even Schur
+//    complement alternates even-site and odd-site phases; even and odd sites of a block live in different wavefronts
+//    (wavefronts 0-1 even, 2-3 odd).  The two workgroups of a CU are independent, so their load and compute phases drift
+//    apart and overlap.  (Two blocks per 512-thread workgroup with complementary roles, so that every SIMD has exactly one
+//    active wavefront per phase, was measured no faster in round 2 and removed: docs/design/04a_schwarz_block_solver.md.)
 //  * FACE BUFFERS FOR THE COUPLINGS ACROSS BLOCK FACES.  The residual update r_b -= D_{b,ext} delta_ext used to gather
 //    delta and the backward links of the neighbouring blocks site by site: 16-32 byte pieces of 128-byte lines on the x
 //    and y faces, twice the algorithmic traffic.  Now the epilogue of a block solve leaves the projected half spinors of
@@ -224,29 +223,26 @@ __device__ __forceinline__ void face_emit_dir(const cf (&v)[12], const cf (&U)[9
 #define SAP_STAMP(k) do { } while (0)
 #endif
 
-template <bool DIST, int NB, bool CMP>
-__global__ __launch_bounds__(256 * NB, 2) void sap_pair_kernel(SapPairArgs a) {
+template <bool DIST, bool CMP>
+__global__ __launch_bounds__(256, 2) void sap_pair_kernel(SapPairArgs a) {
 #ifdef DDAMG_SAP_CHAIN_DIAG
   unsigned long long stamp[SAP_DIAG_STAMPS];
 #pragma unroll
   for (int k = 0; k < SAP_DIAG_STAMPS; k++) stamp[k] = 0;
 #endif
-  __shared__ cf slots[NB][8 * 6 * HS];
-  __shared__ float red[2][NB][8];        // [generation][block of the workgroup][2 even wavefronts x 3 sums]
+  __shared__ cf sl[8 * 6 * HS];
+  __shared__ float red[2][8];            // [generation][2 even wavefronts x 3 sums]
   const FineOpDev<float>& op = a.op;
   const size_t V = op.V;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
-  const int bw = w >> 2, wb = w & 3;
-  const bool odd = (((wb >> 1) ^ bw) & 1) != 0;      // wavefront-uniform role, complementary between the two blocks
-  const int hw = wb & 1;                             // which of the two wavefronts of my parity
+  const bool odd = ((w >> 1) & 1) != 0;              // wavefront-uniform role
+  const int hw = w & 1;                              // which of the two wavefronts of my parity
   const int j = hw * 64 + lane;
   const int i = odd ? HS + j : j;
-  const int bslot = blockIdx.x * NB + bw;
-  const bool active = bslot < a.nblocks;
-  const int blk = active ? a.blocks[bslot] : a.blocks[0];
+  const bool active = (int)blockIdx.x < a.nblocks;   // (the launch has exactly nblocks workgroups: a bounds guard on the list)
+  const int blk = active ? a.blocks[blockIdx.x] : a.blocks[0];
   const size_t s = (size_t)blk * BS + i;
-  cf* sl = slots[bw];
 
   int nbk[8];   // neighbouring blocks (wavefront-uniform)
 #pragma unroll
@@ -466,7 +462,7 @@ __global__ __launch_bounds__(256 * NB, 2) void sap_pair_kernel(SapPairArgs a) {
       float nr = pr.x + pr.y, ni = pi.x - pi.y, dn = pd.x + pd.y;
       SAP_STAMP(7);
       nr = wave_sum(nr); ni = wave_sum(ni); dn = wave_sum(dn);
-      float* rd = red[it & 1][bw];
+      float* rd = red[it & 1];
       if (lane == 0) { rd[hw * 3] = nr; rd[hw * 3 + 1] = ni; rd[hw * 3 + 2] = dn; }
       SAP_STAMP(8);
       __syncthreads();                    // B4
@@ -491,7 +487,7 @@ __global__ __launch_bounds__(256 * NB, 2) void sap_pair_kernel(SapPairArgs a) {
     __syncthreads();                      // F2
   }
 #ifdef DDAMG_SAP_CHAIN_DIAG
-  if (a.diag && lane == 0 && NB == 1) {
+  if (a.diag && lane == 0) {
     unsigned long long* d = a.diag + ((size_t)blockIdx.x * 4 + w) * SAP_DIAG_STAMPS;
 #pragma unroll
     for (int k = 0; k < SAP_DIAG_STAMPS; k++) d[k] = stamp[k];
@@ -587,26 +583,12 @@ void sap_pair_launch(const SapPairArgs& a_in, bool dist, hipStream_t st) {
 #else
   const SapPairArgs& a = a_in;
 #endif
-  // blocks per workgroup: 2 (lockstep pair with complementary wavefront roles) or 1 (two independent workgroups per CU,
-  // whose load and compute phases drift apart and overlap); DDAMG_SAP_BLOCKS_PER_WG selects, see docs/design/04a_schwarz_block_solver.md for the numbers
-  static const int nb = [] { const char* e = getenv("DDAMG_SAP_BLOCKS_PER_WG"); return e ? atoi(e) : 1; }();
-  if (nb == 2) {
-    const int grid = (a.nblocks + 1) / 2;
-    if (a.op.Dc) {
-      if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, 2, true>), dim3(grid), dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((sap_pair_kernel<false, 2, true>), dim3(grid), dim3(512), 0, st, a);
-    } else {
-      if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, 2, false>), dim3(grid), dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((sap_pair_kernel<false, 2, false>), dim3(grid), dim3(512), 0, st, a);
-    }
+  if (a.op.Dc) {
+    if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, true>), dim3(a.nblocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((sap_pair_kernel<false, true>), dim3(a.nblocks), dim3(256), 0, st, a);
   } else {
-    if (a.op.Dc) {
-      if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, 1, true>), dim3(a.nblocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((sap_pair_kernel<false, 1, true>), dim3(a.nblocks), dim3(256), 0, st, a);
-    } else {
-      if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, 1, false>), dim3(a.nblocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((sap_pair_kernel<false, 1, false>), dim3(a.nblocks), dim3(256), 0, st, a);
-    }
+    if (dist) hipLaunchKernelGGL((sap_pair_kernel<true, false>), dim3(a.nblocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((sap_pair_kernel<false, false>), dim3(a.nblocks), dim3(256), 0, st, a);
   }
   DDAMG_HIP_CHECK(hipGetLastError());
 }

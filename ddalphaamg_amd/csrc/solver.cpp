@@ -45,12 +45,8 @@ static void ensure_outer(ddamg_hip_ctx* c) {
   const size_t n = (size_t)24 * c->levels[0]->geom.V;
   c->rw_outer.init(c->par.restart + 4);
   // mixed precision 1 with a multigrid preconditioner: the iterates Z_j of the outer FGMRES stay in fp32, as the
-  // V-cycle leaves them (Gmres::z_fp32); DDAMG_OUTER_Z_FP64 keeps the converted fp64 copies of rounds 1-3
-  {
-    const char* dv = getenv("DDAMG_DIRAC_VARIANT");
-    c->outer.z_fp32 = c->par.method >= 1 && c->par.method <= 4 && c->par.mixed_precision == 1 && !(dv && atoi(dv) == 0) &&
-                      !(c->levels[0]->geom.distributed() && getenv("DDAMG_HALO_DEFER")) && getenv("DDAMG_OUTER_Z_FP64") == nullptr;
-  }
+  // V-cycle leaves them (Gmres::z_fp32)
+  c->outer.z_fp32 = c->par.method >= 1 && c->par.method <= 4 && c->par.mixed_precision == 1;
   // pure CGN keeps its 8 vectors in a 4-vector Krylov structure, as the reference does (src/init.c:178-180)
   c->outer.alloc(n, c->par.method == -1 ? 4 : c->par.restart, c->par.method > 0);
   c->outer.num_restart = c->par.max_restart;
@@ -100,7 +96,12 @@ static void ensure_outer(ddamg_hip_ctx* c) {
           c->mg32->vcycle(0, z, nullptr, c->p32_in, res);
         };
         c->outer.op32 = [c](double* out, const float* z) {
-          DDAMG_REQUIRE(c->fop64.apply_f32in(out, z, c->stream), "outer solver: the fp64 operator on fp32 input is not available in this configuration");
+          if (c->fop64.apply_f32in(out, z, c->stream)) return;
+          // where that form is not built: convert and apply the fp64 operator, as apply_f32in documents
+          const size_t V = c->levels[0]->geom.V;
+          if (!c->z64) DDAMG_HIP_CHECK(device_alloc(&c->z64, sizeof(double) * 24 * V));
+          vec_convert<double, float>(c->z64, z, V, 24, c->stream);
+          c->fop64.apply(out, c->z64, c->stream);
         };
       }
     }
