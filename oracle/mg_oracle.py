@@ -452,9 +452,9 @@ class GmresSmoother:
 # ---- V-cycle and solve ------------------------------------------------------------------------------
 class TwoLevel:
     def __init__(self, L, Lc, B, D, clover, interp_vectors, coarse_D, coarse_clover, post_smooth_iter=2, block_iter=4,
-                 coarse_tol=5e-2, coarse_restart=5, coarse_iter=100, method=2):
+                 coarse_tol=5e-2, coarse_restart=5, coarse_iter=100, method=2, A=None):
         self.L, self.Lc = L, Lc
-        self.A = fine_matrix(L, D, clover)
+        self.A = fine_matrix(L, D, clover) if A is None else A      # A: the fine matrix, when the caller has it already
         self.P = interpolation_matrix(L, Lc, interp_vectors)
         self.n = 2 * np.asarray(interp_vectors).shape[0]
         self.Mc = coarse_matrix(Lc, coarse_D, coarse_clover, self.n)

@@ -480,9 +480,12 @@ def test_gram_schmidt_on_256_site_aggregates_one_wavefront_per_chirality(gold_b4
     assert abs(res[0][2] - res[1][2]) <= 1 and res[0][3] < 1e-10 and res[1][3] < 1e-10
     assert relerr(res[0][1], res[1][1]) < 1e-8
     # orthonormal on every aggregate and chirality: 2 aggregates per direction, 256 sites each, chirality = first / second 6 dof
-    P = np.asarray(res[0][0]); Pc = (P[..., 0] + 1j * P[..., 1]).reshape(P.shape[0], 8, 8, 8, 8, 12)
-    blk = Pc[:, :4, :4, :4, :4, :6].reshape(P.shape[0], -1)
-    assert np.abs(blk.conj() @ blk.T - np.eye(P.shape[0])).max() < 5e-6
+    for P in (res[0][0], res[1][0]):
+        P = np.asarray(P); N = P.shape[0]
+        Pc = (P[..., 0] + 1j * P[..., 1]).reshape(N, 2, 4, 2, 4, 2, 4, 2, 4, 2, 6)    # [vec][T blk][t][Z blk][z]...[chirality][6]
+        blk = Pc.transpose(1, 3, 5, 7, 9, 0, 2, 4, 6, 8, 10).reshape(32, N, 256 * 6)     # [aggregate, chirality][vec][site, dof]
+        gram = blk.conj() @ blk.transpose(0, 2, 1)
+        assert np.abs(gram - np.eye(N)).max() < 5e-6
 
 
 def test_test_vector_gram_schmidt_by_panels(gold_b4, gold8, monkeypatch):

@@ -131,18 +131,39 @@ def test_256_site_blocks_through_rccl_self_exchange(gold8):
     ctx.close()
 
 
+_FINE_8 = {}
+
+
+def fine_matrix_8(gold8, m0, csw):
+    """the 8^4 fine operator as a sparse fp64 matrix, from the pinned oracle (not from the library); built once"""
+    from oracle import mg_oracle as mo, orc
+    if (m0, csw) not in _FINE_8:
+        D, cl, _ = orc.gauge_to_operator([8] * 4, gold8["gauge"], 1, m0, csw)
+        _FINE_8[(m0, csw)] = mo.fine_matrix([8] * 4, D, cl)
+    return _FINE_8[(m0, csw)]
+
+
+@pytest.mark.parametrize("compression", ["default", "0"], ids=["two-row links", "full links"])
+@pytest.mark.parametrize("mp", [1, 0])
 @pytest.mark.parametrize("split", ["0123", "0", "23"])
 @pytest.mark.parametrize("kernel", ["tile", "gather"])
-def test_galerkin_operator_through_the_self_exchange_equals_the_undivided_one(gold8, split, kernel, monkeypatch):
+def test_galerkin_operator_through_the_self_exchange_equals_the_undivided_one(gold8, split, kernel, mp, compression, monkeypatch):
     """the coarse operator built on a process grid (the process its own neighbour in the directions of `split`) against the one
     of the undivided lattice, element by element: the distributed instantiations of the Galerkin construction's stencil kernels
     (LDS-tiled by default, gather form with DDAMG_AGGREGATE_DIRAC_GATHER) read the columns of the aggregate-major interpolation
     operator and take the neighbours' boundary through the transport.  (Round 4: the tiled one once came out of the compiler with
-    wrong Y and X parts -- every direction is checked by itself here.)"""
+    wrong Y and X parts -- every direction is checked by itself here.)  Every instantiation: fp32 (mixed_precision 1) and fp64
+    (0), two-row and full link storage.  The divided operator is also checked against P^H A P in fp64 (oracle/mg_oracle.py), A
+    from the pinned oracle and P the context's own interpolation, so that an error common to both forms fails too."""
     from conftest import load_golden
+    from oracle import mg_oracle as mo
     gb = load_golden("ref_8x8_b4.npz")
     if kernel == "gather":
         monkeypatch.setenv("DDAMG_AGGREGATE_DIRAC_GATHER", "1")
+    if compression == "0":
+        monkeypatch.setenv("DDAMG_LINK_COMPRESSION", "0")
+    else:
+        monkeypatch.delenv("DDAMG_LINK_COMPRESSION", raising=False)
 
     def build(selfx):
         p = api.default_params(); p.num_levels = 2
@@ -151,7 +172,7 @@ def test_galerkin_operator_through_the_self_exchange_equals_the_undivided_one(go
             if selfx and str(mu) in split:
                 p.process_grid[mu] = -1
         p.num_vect[0] = 20; p.post_smooth_iter[0] = 2; p.block_iter[0] = 4
-        p.mixed_precision, p.method, p.odd_even = 1, 2, 1
+        p.mixed_precision, p.method, p.odd_even = mp, 2, 1
         p.m0, p.csw = float(gb["meta_f64"][0]), float(gb["meta_f64"][1])
         ctx = dd.Context(p)
         if selfx:
@@ -159,12 +180,21 @@ def test_galerkin_operator_through_the_self_exchange_equals_the_undivided_one(go
         ctx.set_gauge(gold8["gauge"], anti_pbc=True)
         ctx.setup(0)
         D, cl = ctx.get_coarse_operator()
+        P = ctx.get_interpolation()
         ctx.close()
-        return np.asarray(D), np.asarray(cl)
+        return np.asarray(D), np.asarray(cl), P
 
-    D0, c0 = build(False)
-    D1, c1 = build(True)
+    D0, c0, _ = build(False)
+    D1, c1, P1 = build(True)
     for mu in range(4):
         assert np.max(np.abs(D0[:, mu] - D1[:, mu])) < 1e-6, mu
     assert np.max(np.abs(c0 - c1)) < 5e-6
+    # against P^H A P, hop by hop and the self couplings, entry by entry
+    A = fine_matrix_8(gold8, float(gb["meta_f64"][0]), float(gb["meta_f64"][1]))
+    P = mo.interpolation_matrix([8] * 4, [2] * 4, P1)
+    G = (P.conj().T @ A @ P).toarray()
+    M = mo.coarse_matrix([2] * 4, D1, c1, 40).toarray()
+    err = np.abs(G - M).max() / np.abs(G).max()
+    print(f"mixed_precision {mp}, links {compression}: divided coarse operator vs P^H A P {err:.2e}")
+    assert err < (2e-6 if mp == 1 else 1e-13), err
 
