@@ -135,7 +135,6 @@ int ddamg_hip_destroy(ddamg_hip_ctx* c) {
   if (c->bicg_ready) { c->bicg32.release(); c->bicg64.release(); }
   if (c->p32_in) (void)hipFree(c->p32_in);
   if (c->p32_out) (void)hipFree(c->p32_out);
-  if (c->z64) (void)hipFree(c->z64);
   for (auto& lv : c->levels) if (lv->d_lex_of_site) (void)hipFree(lv->d_lex_of_site);
   if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->clover_base) (void)hipFree(c->clover_base);

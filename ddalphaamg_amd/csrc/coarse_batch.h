@@ -15,8 +15,8 @@ namespace ddamg {
 
 constexpr int COARSE_BATCH_COLS = 64;
 
-// true if the batched path covers this shape (fp32, at most 64 columns, at most 64 dof per site, single process)
-bool coarse_galerkin_batch_available(int n, int ncols, bool distributed, size_t elem_size);
+// true if the batched path covers this shape (fp32, at most 64 columns, at most 64 dof per site)
+bool coarse_galerkin_batch_available(int n, int ncols, size_t elem_size);
 
 // D_{l+1} = P^H D_l P for a coarse level l: fills all five matrices of every site of `next` (self coupling and the
 // four forward links).  `agg_face` is the level's aggregate-face mask (bit d: the neighbour in direction d lies in

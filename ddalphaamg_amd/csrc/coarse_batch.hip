@@ -6,11 +6,10 @@ namespace ddamg {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int NB = COARSE_BATCH_COLS;
 
-bool coarse_galerkin_batch_available(int n, int ncols, bool distributed, size_t elem_size) {
-  // on a process grid the forward couplings across the process boundary take their operand from a halo of the batch
-  // (CoarseOp::wide_halo_exchange); DDAMG_COARSE_GALERKIN_DIST_UNBATCHED keeps the column-by-column construction there
-  static const bool dist_off = getenv("DDAMG_COARSE_GALERKIN_DIST_UNBATCHED") != nullptr;
-  return elem_size == 4 && !(distributed && dist_off) && ncols <= NB && n <= 64 && n % 4 == 0;
+bool coarse_galerkin_batch_available(int n, int ncols, size_t elem_size) {
+  // (on a process grid the forward couplings across the process boundary take their operand from a halo of the batch,
+  // CoarseOp::wide_halo_exchange)
+  return elem_size == 4 && ncols <= NB && n <= 64 && n % 4 == 0;
 }
 
 // V[x][k][j] = P_{j mod N}(x,k) if k belongs to chirality j / N (k < n/2 <-> chirality 0), else 0; columns >= 2N are 0
@@ -221,7 +220,7 @@ __global__ __launch_bounds__(256) void coarse_batch_restrict_store_mfma_kernel(f
 void coarse_galerkin_batched(CoarseOp<float>& next, const CoarseOp<float>& op, const CoarseTransfer<float>& ip,
                              const unsigned char* d_agg_face, float* work, hipStream_t st) {
   const int V = op.V(), n = op.n(), N = ip.nvec;
-  DDAMG_REQUIRE(coarse_galerkin_batch_available(n, 2 * N, op.distributed(), sizeof(float)), "batched coarse Galerkin: unsupported shape");
+  DDAMG_REQUIRE(coarse_galerkin_batch_available(n, 2 * N, sizeof(float)), "batched coarse Galerkin: unsupported shape");
   DDAMG_REQUIRE(next.n() == 2 * N && next.V() == ip.num_aggs, "batched coarse Galerkin: next level does not match the transfer operator");
   const size_t bs = (size_t)V * n * NB;           // complex numbers per batch
   float2* Vb = reinterpret_cast<float2*>(work);

@@ -251,8 +251,7 @@ void batch_scale_inv(float2* out, const float2* w, const double* d_norm2, size_t
 }
 
 bool LockstepCoarseSolver::available(const CoarseOp<float>& cop, int ncols, bool odd_even) {
-  static const bool off = getenv("DDAMG_BOOTSTRAP_NO_LOCKSTEP") != nullptr;
-  return !off && odd_even && !cop.distributed() && ncols >= 2 && ncols <= NC && cop.n() <= 64 && cop.n() % 4 == 0 && cop.V() % 2 == 0;
+  return odd_even && !cop.distributed() && ncols >= 2 && ncols <= NC && cop.n() <= 64 && cop.n() % 4 == 0 && cop.V() % 2 == 0;
 }
 
 LockstepCoarseSolver::~LockstepCoarseSolver() { release(); }
@@ -285,10 +284,7 @@ void LockstepCoarseSolver::init(const CoarseOp<float>* cop, int max_steps, doubl
 
 void LockstepCoarseSolver::gather(float2* Wb, const float* src, size_t sstride, int ncols) { batch_gather(Wb, src, sstride, ncols, (size_t)V_ * n_, st_); }
 void LockstepCoarseSolver::scatter(float* dst, size_t dstride, const float2* Wb, int ncols) { batch_scatter(dst, dstride, Wb, ncols, (size_t)V_ * n_, st_); }
-bool LockstepCoarseSolver::operand_order() const {
-  static const bool off = getenv("DDAMG_LOCKSTEP_TILE_LAYOUT") != nullptr;
-  return !off && n_ % 8 == 0;
-}
+bool LockstepCoarseSolver::operand_order() const { return n_ % 8 == 0; }
 void LockstepCoarseSolver::operands(const float4** Mop, const float4** Minv_op) const {
   const size_t me = mfma_op_matrix_elems(n_);
   if (!Mop_) {

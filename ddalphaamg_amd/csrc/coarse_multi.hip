@@ -317,8 +317,7 @@ void coarse_inverse_operands_build(float4* Minv_op, const CoarseOp<float>& op, h
 }
 
 bool CoarseMulti::available(const Geometry& g, const CoarseOp<float>& op, int method) {
-  static const bool off = getenv("DDAMG_BOOTSTRAP_NO_LOCKSTEP") != nullptr;
-  if (off || method != 2 || op.distributed() || g.distributed()) return false;
+  if (method != 2 || op.distributed() || g.distributed()) return false;
   if (op.n() % 8 != 0 || op.n() > 64 || g.block_sites > 16 || g.block_sites < 1) return false;
   for (int mu = 0; mu < 4; mu++) if (g.nblk[mu] % 2 != 0) return false;
   return true;

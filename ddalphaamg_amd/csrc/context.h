@@ -64,7 +64,6 @@ struct ddamg_hip_ctx {
   ddamg::ReduceWork rw_blas;
   bool rw_blas_ready = false;
   float *p32_in = nullptr, *p32_out = nullptr;
-  double* z64 = nullptr;        // outer FGMRES with fp32 iterates: fp64 copy of one, where FineOp::apply_f32in is not built
   // fgmres_MP (mixed_precision 2): fp32 Krylov basis, fp64 residual/solution (src/linsolve.c:153-424)
   ddamg::Gmres<float> mp_inner;
   ddamg::ReduceWork rw_mp;

@@ -1,4 +1,4 @@
-// fine_op.hip -- fine Wilson-Clover apply (gather form, one site per lane) + layout converters.
+// fine_op.hip -- fine Wilson-Clover apply (LDS-tiled, one site per lane; the fp64 operator also on fp32 inputs) + layout converters.
 // Reference: d_plus_clover_PRECISION src/dirac_generic.c:159-277 (six passes + 8 half-spinor
 // scratch fields there; one fused pass here), trans/trans_back src/schwarz_generic.c:1807-1846.
 #include "fine_op.h"
@@ -14,60 +14,6 @@
 #define DDAMG_NT_STORE true
 #endif
 namespace ddamg {
-
-template <typename T, int MU>
-__device__ __forceinline__ void hop_pair(const T* __restrict__ phi, const FineOpDev<T>& op, size_t s, T (&eta)[24]) {
-  const size_t V = op.V;
-  {
-    int j = op.nb[(size_t)MU * V + s];
-    T U[18];
-    load_site<T, 18>(op.D + (size_t)MU * 18 * V, V, s, U);
-    if (j >= 0) {
-      T pn[24];
-      load_site<T, 24>(phi, V, j, pn);
-      hop_accumulate<T, MU, true>(U, pn, eta);
-    } else {
-      halo_forward<T, MU>(op, -1 - j, U, eta);
-    }
-  }
-  {
-    int j = op.nb[(size_t)(4 + MU) * V + s];
-    if (j >= 0) {
-      T pn[24], U[18];
-      load_site<T, 24>(phi, V, j, pn);
-      load_site<T, 18>(op.D + (size_t)MU * 18 * V, V, j, U);
-      hop_accumulate<T, MU, false>(U, pn, eta);
-    } else {
-      halo_backward<T, MU>(op, -1 - j, eta);
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, (sizeof(T) == 4 ? 4 : 3)) void dirac_apply_kernel(T* __restrict__ eta, const T* __restrict__ phi, FineOpDev<T> op, const int* __restrict__ tile_list) {
-  const size_t s = (size_t)(tile_list ? tile_list[blockIdx.x] : blockIdx.x) * 256 + threadIdx.x;
-  const size_t V = op.V;
-  if (s >= V) return;
-  T e[24];
-  {
-    T p[24], cl[36];
-    load_site<T, 24>(phi, V, s, p);
-    load_site<T, 36>(op.clover, V, s, cl);
-    herm6_mul<T>(cl, p, e);
-    load_site<T, 36>(op.clover + (size_t)36 * V, V, s, cl);
-    herm6_mul<T>(cl, p + 12, e + 12);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  hop_pair<T, 0>(phi, op, s, e);
-  __builtin_amdgcn_sched_barrier(0);
-  hop_pair<T, 1>(phi, op, s, e);
-  __builtin_amdgcn_sched_barrier(0);
-  hop_pair<T, 2>(phi, op, s, e);
-  __builtin_amdgcn_sched_barrier(0);
-  hop_pair<T, 3>(phi, op, s, e);
-  __builtin_amdgcn_sched_barrier(0);
-  store_site<T, 24>(eta, V, s, e);
-}
 
 // ---- LDS-tiled variant ------------------------------------------------------------------------
 // One workgroup = one tile of 256 consecutive sites (= one 4^4 Schwarz block, or several smaller
@@ -106,13 +52,7 @@ __device__ __forceinline__ void load_site_as(const TIN* __restrict__ base, size_
   }
 }
 
-#ifdef DDAMG_FACE_DIAG
-// diagnostic build only (tools/gpu/facediag.sh: what the couplings that leave a tile cost, per direction):
-// bit mu = forward, bit 4+mu = backward coupling across the tile face is computed
-__device__ int g_face_mask = 0xff;
-#endif
-
-template <typename T, int MU, bool ARITH, bool DEFER, bool CMP, bool HB2, typename TIN = T>
+template <typename T, int MU, bool ARITH, bool CMP, bool HB2, typename TIN = T>
 __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const FineOpDev<T>& op, size_t s, bool live, int tile0, const uint4& q,
                                          const T (&p)[24], T (&e)[24], T* __restrict__ sp, T* __restrict__ hb) {
   const size_t V = op.V;
@@ -132,20 +72,15 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
     const int j = tile_neighbor<ARITH>(op.nb, V, s, MU, tile0, q, op.tile_nb, (int)(V >> 8));
     if (j >= 0) {
       T pn[24];
-      bool take = true;
       if (j - tile0 >= 0 && j - tile0 < 256) {
 #pragma unroll
         for (int c = 0; c < 24; c++) pn[c] = sp[c * 256 + (j - tile0)];
       } else {
-#ifdef DDAMG_FACE_DIAG
-        take = (g_face_mask >> MU & 1) != 0;
-        if (take)
-#endif
         load_site_as<T, TIN, 24>(phi, V, j, pn);
       }
-      if (take) hop_accumulate<T, MU, true>(U, pn, e);
+      hop_accumulate<T, MU, true>(U, pn, e);
     } else {
-      if constexpr (!DEFER) halo_forward<T, MU>(op, -1 - j, U, e);   // DEFER: added by halo_fixup_kernel after the exchange
+      halo_forward<T, MU>(op, -1 - j, U, e);
     }
   }
   __syncthreads();
@@ -153,17 +88,13 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
   if (live) {
     const int j = tile_neighbor<ARITH>(op.nb, V, s, 4 + MU, tile0, q, op.tile_nb, (int)(V >> 8));
     if (j < 0) {
-      if constexpr (!DEFER) halo_backward<T, MU>(op, -1 - j, e);
+      halo_backward<T, MU>(op, -1 - j, e);
     } else if (j - tile0 >= 0 && j - tile0 < 256) {
       T g[12];
 #pragma unroll
       for (int c = 0; c < 12; c++) g[c] = hb[c * 256 + (j - tile0)];
       spin_reconstruct_sub<T, MU, +1>(g, e);
-    } else
-#ifdef DDAMG_FACE_DIAG
-    if (g_face_mask >> (4 + MU) & 1)
-#endif
-    {
+    } else {
       T pn[24], Un[18];
       load_site_as<T, TIN, 24>(phi, V, j, pn);
       load_link<T, MU, CMP>(op, V, (size_t)j, Un);
@@ -173,7 +104,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
   if constexpr (!HB2) __syncthreads();   // HB2: the caller alternates between two hb buffers, one barrier per direction
 }
 
-template <typename T, bool ARITH, bool DEFER, bool CMP = false, typename TIN = T>
+template <typename T, bool ARITH, bool CMP = false, typename TIN = T>
 __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds_kernel(T* __restrict__ eta, const TIN* __restrict__ phi, FineOpDev<T> op, int ntiles,
                                                                   const int* __restrict__ tile_list) {
   // fp32: two buffers for the backward products, used in turn, so that one barrier per direction is enough (48 KB of LDS,
@@ -209,10 +140,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
     herm6_mul<T>(cl, p + 12, e + 12);
   }
   __syncthreads();
-  tile_dir<T, 0, ARITH, DEFER, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 1, ARITH, DEFER, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb1);
-  tile_dir<T, 2, ARITH, DEFER, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 3, ARITH, DEFER, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb1);
+  tile_dir<T, 0, ARITH, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb);
+  tile_dir<T, 1, ARITH, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb1);
+  tile_dir<T, 2, ARITH, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb);
+  tile_dir<T, 3, ARITH, CMP, HB2, TIN>(phi, op, s, live, tile0, q, p, e, sp, hb1);
   if (live) store_site<T, 24, DDAMG_NT_STORE>(eta, V, s, e);
 }
 
@@ -323,83 +254,24 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_hop_parit
   }
 }
 
-// the couplings to sites on other GPUs, added after the exchange: one thread per boundary site (a site on an edge or
-// corner of the local lattice takes all its off-process directions here, so no two threads touch the same site)
-template <typename T, int MU>
-__device__ __forceinline__ void fixup_dir(const FineOpDev<T>& op, size_t s, T (&e)[24]) {
-  const size_t V = op.V;
-  const int jf = op.nb[(size_t)MU * V + s];
-  if (jf < 0) {
-    T U[18];
-    load_site<T, 18>(op.D + (size_t)MU * 18 * V, V, s, U);
-    halo_forward<T, MU>(op, -1 - jf, U, e);
-  }
-  const int jb = op.nb[(size_t)(4 + MU) * V + s];
-  if (jb < 0) halo_backward<T, MU>(op, -1 - jb, e);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void halo_fixup_kernel(T* __restrict__ eta, FineOpDev<T> op, const int* __restrict__ sites, int nsites) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nsites) return;
-  const size_t s = (size_t)sites[i];
-  T e[24];
-  load_site<T, 24>(eta, op.V, s, e);
-  fixup_dir<T, 0>(op, s, e);
-  fixup_dir<T, 1>(op, s, e);
-  fixup_dir<T, 2>(op, s, e);
-  fixup_dir<T, 3>(op, s, e);
-  store_site<T, 24>(eta, op.V, s, e);
-}
-
-static int g_dirac_variant = -1;  // 0: gather/cache kernel, 1: LDS-tiled kernel (default)
-
 template <typename T>
 void FineOp<T>::apply(T* eta, const T* phi, hipStream_t st) const {
   DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
-  if (g_dirac_variant < 0) {
-    const char* e = getenv("DDAMG_DIRAC_VARIANT");
-    g_dirac_variant = e ? atoi(e) : 1;
-  }
-#ifdef DDAMG_FACE_DIAG
-  { static int once = 0; if (!once) { once = 1; const char* m = getenv("DDAMG_FACE_MASK"); int v = m ? (int)strtol(m, nullptr, 0) : 0xff;
-      DDAMG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_face_mask), &v, sizeof(int))); } }
-#endif
   auto launch = [&](int ntiles, const int* tile_list) {
     if (ntiles == 0) return;
-    if (g_dirac_variant == 0) hipLaunchKernelGGL(dirac_apply_kernel<T>, dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), tile_list);
-    else if (tnb_ && g_dirac_variant != 4 && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, false, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-    else if (tnb_ && g_dirac_variant != 4) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, false>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-    else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, false>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    if (tnb_ && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else if (tnb_) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
     DDAMG_HIP_CHECK(hipGetLastError());
   };
   if (!halo_.active()) {
     launch((V_ + 255) / 256, nullptr);
     return;
   }
-  // reference order of events: src/dirac_generic.c:178-262 (project+send, interior work, wait, boundary)
-  static const bool defer = getenv("DDAMG_HALO_DEFER") != nullptr;
+  // reference order of events: src/dirac_generic.c:178-262 (project+send, interior work, wait, boundary): tiles without an
+  // off-process neighbour during the exchange, the others after it
   halo_.pack(phi, D_, V_, st);
   halo_.exchange_begin(comm_, st);
-  if (g_dirac_variant != 0 && defer) {
-    // alternative (DDAMG_HALO_DEFER): the whole lattice in one launch with the off-process couplings left out -- it
-    // overlaps with the complete exchange -- then a short pass over the boundary sites adds them.  Measured with the
-    // self-exchange mode at 32^4, three directions: 249 us against 237 us for the split below in round 1, 204 against 188 us
-    // with the two-row links (full launch 154 us on the 232 CUs left to the compute stream + 28 us boundary pass), so the
-    // split is the default.  Also measured: the pack kernel on a third stream so that the interior tiles start at once --
-    // 344 us, every further cross-stream dependency costs more than the 19 us it hides; the interior tiles enqueued before
-    // the transport's send/receive group -- no change (the 6 us in front of them are the event packet, not the host).
-    const int ntiles = (V_ + 255) / 256;
-    if (tnb_ && g_dirac_variant != 4 && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, true, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, (const int*)nullptr);
-    else if (tnb_ && g_dirac_variant != 4) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, (const int*)nullptr);
-    else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, true>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, (const int*)nullptr);
-    DDAMG_HIP_CHECK(hipGetLastError());
-    halo_.exchange_finish(comm_, st);
-    const int nbs = halo_.n_boundary_sites();
-    hipLaunchKernelGGL(halo_fixup_kernel<T>, dim3((nbs + 255) / 256), dim3(256), 0, st, eta, dev(), halo_.boundary_sites(), nbs);
-    DDAMG_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  // default: tiles without an off-process neighbour during the exchange, the others after it
   launch(halo_.n_interior(), halo_.interior_tiles());
   halo_.exchange_finish(comm_, st);
   launch(halo_.n_boundary(), halo_.boundary_tiles());
@@ -408,31 +280,23 @@ void FineOp<T>::apply(T* eta, const T* phi, hipStream_t st) const {
 // eta = D phi with phi an fp32 vector (its own layout): the fp64 operator of the outer solver on the iterates that come out of the
 // fp32 V-cycle (fgmres_double + preconditioner(), src/linsolve_generic.c:219-413, src/preconditioner.c:25-69, where the iterate is
 // converted first) -- the conversion happens in the loads, the result is the one of apply() on the converted vector bit for bit.
-// false where this form is not built (a process grid, the gather variant): the caller converts and calls apply().
-template <typename T>
-bool FineOp<T>::apply_f32in(T* eta, const float* phi, hipStream_t st) const {
-  if constexpr (sizeof(T) == 8) {
-    DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
-    if (g_dirac_variant < 0) { const char* e = getenv("DDAMG_DIRAC_VARIANT"); g_dirac_variant = e ? atoi(e) : 1; }
-    static const bool defer = getenv("DDAMG_HALO_DEFER") != nullptr;
-    if (g_dirac_variant == 0 || (halo_.active() && defer)) return false;
-    auto launch = [&](int ntiles, const int* tile_list) {
-      if (ntiles == 0) return;
-      if (tnb_ && g_dirac_variant != 4 && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, false, true, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-      else if (tnb_ && g_dirac_variant != 4) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, false, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-      else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, false, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-      DDAMG_HIP_CHECK(hipGetLastError());
-    };
-    if (!halo_.active()) { launch((V_ + 255) / 256, nullptr); return true; }
-    // on a process grid: the order of events of apply()
-    halo_.pack_f32in(phi, D_, V_, st);
-    halo_.exchange_begin(comm_, st);
-    launch(halo_.n_interior(), halo_.interior_tiles());
-    halo_.exchange_finish(comm_, st);
-    launch(halo_.n_boundary(), halo_.boundary_tiles());
-    return true;
-  }
-  return false;
+template <>
+void FineOp<double>::apply_f32in(double* eta, const float* phi, hipStream_t st) const {
+  DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
+  auto launch = [&](int ntiles, const int* tile_list) {
+    if (ntiles == 0) return;
+    if (tnb_ && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, true, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else if (tnb_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else hipLaunchKernelGGL((dirac_apply_lds_kernel<double, false, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    DDAMG_HIP_CHECK(hipGetLastError());
+  };
+  if (!halo_.active()) { launch((V_ + 255) / 256, nullptr); return; }
+  // on a process grid: the order of events of apply()
+  halo_.pack_f32in(phi, D_, V_, st);
+  halo_.exchange_begin(comm_, st);
+  launch(halo_.n_interior(), halo_.interior_tiles());
+  halo_.exchange_finish(comm_, st);
+  launch(halo_.n_boundary(), halo_.boundary_tiles());
 }
 
 template <typename T>

@@ -438,19 +438,12 @@ void Halo<T>::init(const Geometry& g) {
     DDAMG_HIP_CHECK(device_alloc(&d_boundary_, sizeof(int) * n_boundary_));
     DDAMG_HIP_CHECK(hipMemcpy(d_boundary_, g.boundary_tiles.data(), sizeof(int) * n_boundary_, hipMemcpyHostToDevice));
   }
-  std::vector<int> bs;
-  for (int s = 0; s < g.V; s++)
-    for (int d = 0; d < 8; d++) if (g.nb[(size_t)d * g.V + s] < 0) { bs.push_back(s); break; }
-  n_bsites_ = (int)bs.size();
-  DDAMG_HIP_CHECK(device_alloc(&d_bsites_, sizeof(int) * n_bsites_));
-  DDAMG_HIP_CHECK(hipMemcpy(d_bsites_, bs.data(), sizeof(int) * n_bsites_, hipMemcpyHostToDevice));
 }
 
 template <typename T>
 Halo<T>::~Halo() {
   if (d_interior_) (void)hipFree(d_interior_);
   if (d_boundary_) (void)hipFree(d_boundary_);
-  if (d_bsites_) (void)hipFree(d_bsites_);
 }
 
 template <typename T>

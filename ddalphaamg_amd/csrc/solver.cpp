@@ -95,14 +95,7 @@ static void ensure_outer(ddamg_hip_ctx* c) {
           vec_convert<float, double>(c->p32_in, eta, c->levels[0]->geom.V, 24, c->stream);
           c->mg32->vcycle(0, z, nullptr, c->p32_in, res);
         };
-        c->outer.op32 = [c](double* out, const float* z) {
-          if (c->fop64.apply_f32in(out, z, c->stream)) return;
-          // where that form is not built: convert and apply the fp64 operator, as apply_f32in documents
-          const size_t V = c->levels[0]->geom.V;
-          if (!c->z64) DDAMG_HIP_CHECK(device_alloc(&c->z64, sizeof(double) * 24 * V));
-          vec_convert<double, float>(c->z64, z, V, 24, c->stream);
-          c->fop64.apply(out, c->z64, c->stream);
-        };
+        c->outer.op32 = [c](double* out, const float* z) { c->fop64.apply_f32in(out, z, c->stream); };
       }
     }
   }

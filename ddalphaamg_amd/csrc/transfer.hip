@@ -377,11 +377,8 @@ void Interpolation<T>::restrict_batch(T* phi_c, size_t out_stride, const T* phi,
     DDAMG_REQUIRE(restrict_batch_available(agg_sites, nvec) && nw >= 1 && nw <= 256, "batched restriction: unsupported shape");
     const RestrictParts parts = whole_aggregates((size_t)V, agg_sites);
     // up to 64 fields (the bootstrap's Nvec right-hand sides): the 16-wide tiles of the Galerkin construction's kernel; with P
-    // stored aggregate by aggregate they take 1.65 ms at 32^4, the 32-wide tile of round 3 (DDAMG_RESTRICT_BATCH_TILES_32) 2.25 ms
-    static const bool w16 = getenv("DDAMG_RESTRICT_BATCH_TILES_32") == nullptr;
-    if (nw <= 64 && w16) hipLaunchKernelGGL((restrict_mfma_kernel<2, true>), dim3(num_aggs), dim3(256), 0, st, phi_c, out_stride, phi, in_stride, nw, P, nvec, V, agg_sites, plane_sites(), agg_csite,
-                                     0, parts, (const unsigned short*)nullptr, 1, num_aggs, (float*)nullptr, 0, (size_t)0, 0);
-    else if (nw <= 32) hipLaunchKernelGGL(restrict_mfma_kernel<1>, dim3(num_aggs), dim3(256), 0, st, phi_c, out_stride, phi, in_stride, nw, P, nvec, V, agg_sites, plane_sites(), agg_csite,
+    // stored aggregate by aggregate they take 1.65 ms at 32^4, the 32-wide tile of round 3 2.25 ms
+    if (nw <= 64) hipLaunchKernelGGL((restrict_mfma_kernel<2, true>), dim3(num_aggs), dim3(256), 0, st, phi_c, out_stride, phi, in_stride, nw, P, nvec, V, agg_sites, plane_sites(), agg_csite,
                                      0, parts, (const unsigned short*)nullptr, 1, num_aggs, (float*)nullptr, 0, (size_t)0, 0);
     else hipLaunchKernelGGL(restrict_mfma_kernel<8>, dim3(num_aggs), dim3(256), 0, st, phi_c, out_stride, phi, in_stride, nw, P, nvec, V, agg_sites, plane_sites(), agg_csite,
                             0, parts, (const unsigned short*)nullptr, 1, num_aggs, (float*)nullptr, 0, (size_t)0, 0);
@@ -423,8 +420,6 @@ void Interpolation<T>::restrict_batch_compact(T* phi_c, size_t out_stride, const
     const dim3 grid((unsigned)((naggs + 7) / 8 * 8 * 5));
     if (ncols <= 32) hipLaunchKernelGGL(restrict_mfma_kernel<1>, grid, dim3(256), 0, st, phi_c, 5 * out_stride, W, wstride, ncols, P, nvec, V, agg_sites, plane_sites(), agg_csite,
                                         agg0, parts, af.list, 5, naggs, (float*)Mdirect, nt2, msize2, col_base);
-    else if (getenv("DDAMG_RESTRICT_TILES_32")) hipLaunchKernelGGL(restrict_mfma_kernel<2>, grid, dim3(256), 0, st, phi_c, 5 * out_stride, W, wstride, ncols, P, nvec, V, agg_sites, plane_sites(), agg_csite,
-                            agg0, parts, af.list, 5, naggs, (float*)Mdirect, nt2, msize2, col_base);
     else hipLaunchKernelGGL((restrict_mfma_kernel<2, true>), grid, dim3(256), 0, st, phi_c, 5 * out_stride, W, wstride, ncols, P, nvec, V, agg_sites, plane_sites(), agg_csite,
                             agg0, parts, af.list, 5, naggs, (float*)Mdirect, nt2, msize2, col_base);
     DDAMG_HIP_CHECK(hipGetLastError());
@@ -797,18 +792,15 @@ void Interpolation<T>::orthonormalize(hipStream_t st) {
   // columns per pass: 2 (measured at 32^4, Nvec 24: 6.8 ms with one column, 4.3 ms with two, 4.5 ms with four -- 190 registers,
   // two workgroups per CU; two columns reproduce the one-column results bit for bit, four do not: the compiler contracts
   // the products of the wider reduction differently)
-  static const int columns = getenv("DDAMG_GS_COLUMNS") ? atoi(getenv("DDAMG_GS_COLUMNS")) : 2;
   if constexpr (sizeof(T) == 4) {
-    const bool workgroup_form = getenv("DDAMG_GS_WORKGROUP") != nullptr || getenv("DDAMG_GS_COLUMNS") != nullptr;   // read at every call (tests)
+    const bool workgroup_form = getenv("DDAMG_GS_WORKGROUP") != nullptr;   // read at every call (tests)
     if (agg_sites == 256 && !workgroup_form) {
       hipLaunchKernelGGL(gs_aggregates_wave_kernel<3>, dim3((2 * num_aggs + 3) / 4), dim3(256), 0, st, P, tv, pstride, nvec, V, plane_sites(), 2 * num_aggs);
       DDAMG_HIP_CHECK(hipGetLastError());
       return;
     }
   }
-  if (spt == 1 && columns == 1) hipLaunchKernelGGL((gs_aggregates_kernel<T, 1, 1>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
-  else if (spt == 1 && columns == 4 && sizeof(T) == 4) hipLaunchKernelGGL((gs_aggregates_kernel<T, 1, 4>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
-  else if (spt == 1) hipLaunchKernelGGL((gs_aggregates_kernel<T, 1, 2>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
+  if (spt == 1) hipLaunchKernelGGL((gs_aggregates_kernel<T, 1, 2>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
   else if (spt == 2) hipLaunchKernelGGL((gs_aggregates_kernel<T, 2, 1>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
   else if (spt <= 4) hipLaunchKernelGGL((gs_aggregates_kernel<T, 4, 1>), dim3(num_aggs), dim3(nt), 0, st, P, tv, pstride, nvec, V, agg_sites, plane_sites());
   else DDAMG_REQUIRE(false, "aggregates larger than 1024 sites are not supported by the Gram-Schmidt kernel");

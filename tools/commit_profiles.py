@@ -6,7 +6,9 @@ r04) into profiles/ and derive the provenance files bench.py reads:
   profiles/<round>_strong_scaling_n1.json  the one-GPU point of the 64^4 strong-scaling solve
   profiles/<round>_mfma_busy.json          matrix-core busy fraction of the many-right-hand-side coarse operator kernels, with
                                            the hash of their sources
-Run it on the commit the profile was taken from (the working tree's kernel sources are hashed)."""
+Run it on the commit the profile was taken from (the working tree's kernel sources are hashed; a tree with uncommitted changes
+is recorded as <commit>-dirty).  Without a bench_line.json in SRC_DIR (`run.sh hashed`: only the counter passes behind the
+two hashed files) the bench line and the strong-scaling point are left as they are."""
 import json, os, shutil, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -16,10 +18,12 @@ R = sys.argv[2] if len(sys.argv) > 2 else "r04"
 src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "gpurun_out", "profile")
 dst = os.path.join(REPO, "profiles")
 for f in sorted(os.listdir(src)):
-    if f.startswith(R + "_"):
+    if f.startswith(R + "_") and not f.endswith(".err"):   # the profiler's own stderr log: timings of its phases, no measurement
         shutil.copy(os.path.join(src, f), os.path.join(dst, f))
-shutil.copy(os.path.join(src, "bench_line.json"), os.path.join(dst, R + "_bench_line.json"))
-commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+have_line = os.path.exists(os.path.join(src, "bench_line.json"))
+if have_line:
+    shutil.copy(os.path.join(src, "bench_line.json"), os.path.join(dst, R + "_bench_line.json"))
+commit = subprocess.run(["git", "-C", REPO, "describe", "--always", "--abbrev=7", "--dirty"], capture_output=True, text=True).stdout.strip()
 
 pmc = json.load(open(os.path.join(src, R + "_pmc_bench.json")))
 key = [k for k in pmc if "dirac_apply_lds_kernel<float" in k][0]
@@ -39,12 +43,14 @@ traffic = {
 }
 json.dump(traffic, open(os.path.join(dst, R + "_traffic.json"), "w"), indent=1)
 
-line = json.loads(open(os.path.join(src, "bench_line.json")).read().strip().splitlines()[-1])
-ss = line["strong_scaling"]
-n1 = {"global_lattice": [64, 64, 64, 64], "seconds_per_solve": ss["seconds_per_solve"], "setup_seconds": ss["setup_seconds"],
-      "iterations": ss["iterations"], "coarse_iterations": ss["coarse_iterations"], "true_relres": ss["true_relres"],
-      "source": "profiles/" + R + "_bench_line.json: python3 bench.py (default) on one MI355X under rocprofv3 --kernel-trace, commit " + commit}
-json.dump(n1, open(os.path.join(dst, R + "_strong_scaling_n1.json"), "w"), indent=1)
+n1 = None
+if have_line:
+    line = json.loads(open(os.path.join(src, "bench_line.json")).read().strip().splitlines()[-1])
+    ss = line["strong_scaling"]
+    n1 = {"global_lattice": [64, 64, 64, 64], "seconds_per_solve": ss["seconds_per_solve"], "setup_seconds": ss["setup_seconds"],
+          "iterations": ss["iterations"], "coarse_iterations": ss["coarse_iterations"], "true_relres": ss["true_relres"],
+          "source": "profiles/" + R + "_bench_line.json: python3 bench.py (default) on one MI355X under rocprofv3 --kernel-trace, commit " + commit}
+    json.dump(n1, open(os.path.join(dst, R + "_strong_scaling_n1.json"), "w"), indent=1)
 
 # matrix-core busy fraction of the kernels that apply a coarse operator to many right-hand sides
 def busy(fname, key):

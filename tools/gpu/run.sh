@@ -10,13 +10,25 @@ R=${1:-help}; shift
 O=gpurun_out/$R; mkdir -p "$O"
 SP="python3 tools/solve_profile.py"      # N_solves mixed_precision extent levels
 
-warm() { $SP 1 1 32 2 > /dev/null 2>&1; }   # the first process on a fresh box pays one-time allocation costs (DESIGN, setup)
+# Every GPU step of warm, stats, pmc and profile runs under a time limit of its own, and they stop at the first step that fails
+# (the failing step's status is returned; nothing further is started on the GPU).
+warm() { timeout -k 10 300 $SP 1 1 32 2 > /dev/null 2>&1 || { echo "warm-up failed"; return 1; }; }   # the first process on a fresh box pays one-time allocation costs (DESIGN, setup)
 # kernel statistics of a command: stats <label> <command...>  ->  $O/<label>_stats.csv
-stats() { local l=$1; shift; rocprofv3 --kernel-trace --stats -d $O/kt_$l -o k -- "$@" > $O/$l.log 2>&1; python3 tools/rocpd_export.py stats $O/kt_$l/k_results.db $O/${l}_stats.csv; rm -rf $O/kt_$l; }
+stats() { local l=$1; shift; timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $O/kt_$l -o k -- "$@" > $O/$l.log 2>&1 || { echo "stats $l failed"; return 1; }
+  python3 tools/rocpd_export.py stats $O/kt_$l/k_results.db $O/${l}_stats.csv; rm -rf $O/kt_$l; }
 # counter passes of a command, one rocprofv3 run per quoted group: pmc <label> "<counters>" ["<counters>" ...] -- <command...>  ->  $O/<label>.json
 pmc() { local l=$1 i=0 dbs=""; shift; local groups=(); while [ "$1" != "--" ]; do groups+=("$1"); shift; done; shift
-  for c in "${groups[@]}"; do i=$((i + 1)); timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace -d $O/pmc_${l}_$i -o p -- "$@" > /dev/null 2>> $O/$l.err || echo "pass $i ($c) failed"; dbs="$dbs $O/pmc_${l}_$i/p_results.db"; done
+  for c in "${groups[@]}"; do i=$((i + 1))
+    timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace -d $O/pmc_${l}_$i -o p -- "$@" > /dev/null 2>> $O/$l.err || { echo "pmc $l: pass $i ($c) failed"; return 1; }
+    dbs="$dbs $O/pmc_${l}_$i/p_results.db"; done
   python3 tools/rocpd_export.py pmc $dbs > $O/$l.json; rm -rf $O/pmc_${l}_*; }
+# the four counter passes behind the two profiles bench.py checks against the hash of the kernel sources they were measured on
+# (profiles/<round>_traffic.json: the fine operator's fabric bytes; <round>_mfma_busy.json: the matrix-core busy fractions)
+hashed() { local RD=$1
+  pmc ${RD}_pmc_bench FETCH_SIZE WRITE_SIZE -- python3 bench.py --steps 25 --warmup 5 --no-solve --no-strong --no-cpu-baseline &&
+  pmc ${RD}_pmc_mfma_lockstep32 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 1 1 32 2 &&
+  pmc ${RD}_pmc_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 1 1 48 3 &&
+  pmc ${RD}_pmc_mfma64 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 0 1 64 3; }
 # setup phase times and the solve of one extent: phases <extent> <levels> [label]
 phases() { DDAMG_SETUP_TIMING=1 $SP ${4:-1} 1 $1 $2 > $O/phases_${3:-$1}.log 2>&1; grep -E "ddamg setup|lattice" $O/phases_${3:-$1}.log | cut -c1-230; }
 short() { sed 's/(HIP_vector[^"]*"/"/; s/(float[^"]*"/"/; s/(ddamg::[^"]*"/"/; s/void ddamg:://; s/(anonymous namespace):://' | cut -c1-150; }
@@ -104,19 +116,18 @@ import json; d=json.loads(open('$O/line.json').read().strip().splitlines()[-1])
 print({k:d[k] for k in ('metric','value','unit','n_gpus','steps','warmup','ms_per_step','scaling','vs_baseline','dtype','data')}); print(d['roofline']); print(d['cpu_baseline']['value'], d['cpu_baseline']['kind'], d['cpu_baseline']['cores'])
 for leg in ('solve','three_level_48','strong_scaling'):
     if leg in d: print(leg, {k:v for k,v in d[leg].items() if k not in ('workload','coarse_operator','reference_32','per_level_messages')})" ;;
+hashed)       # only the counter passes behind profiles/<round>_traffic.json and <round>_mfma_busy.json: run.sh hashed r04 ; then commit_profiles.py on its output directory
+  warm && hashed ${1:-r04} && ls $O ;;
 profile)      # every artefact of profiles/<round>_* : run.sh profile r04 ; then python3 tools/commit_profiles.py gpurun_out/profile r04
-  RD=${1:-r04}; warm
-  rocprofv3 --kernel-trace --stats -d $O/bench -o bench -- python3 bench.py > $O/bench_line.json 2> $O/bench.err
+  RD=${1:-r04}; warm || exit 1
+  timeout -k 10 1200 rocprofv3 --kernel-trace --stats -d $O/bench -o bench -- python3 bench.py > $O/bench_line.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
   python3 tools/rocpd_export.py stats $O/bench/bench_results.db $O/${RD}_bench_kernel_stats.csv; rm -rf $O/bench; tail -c 400 $O/bench_line.json; echo
-  pmc ${RD}_pmc_bench FETCH_SIZE WRITE_SIZE -- python3 bench.py --steps 25 --warmup 5 --no-solve --no-strong --no-cpu-baseline
+  hashed $RD || exit 1
   export SAP_BENCH_ITERS=4
-  pmc ${RD}_pmc_sap FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" -- python3 tools/sap_bench.py
+  pmc ${RD}_pmc_sap FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" -- python3 tools/sap_bench.py || exit 1
   unset SAP_BENCH_ITERS
-  for cfg in "32 2 10" "48 3 5" "64 3 3"; do set -- $cfg; stats ${RD}_solve$1 $SP $3 1 $1 $2; mv $O/${RD}_solve$1_stats.csv $O/${RD}_solve$1_kernel_stats.csv; tail -1 $O/${RD}_solve$1.log | cut -c1-200; done
-  pmc ${RD}_pmc_mfma_lockstep32 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 1 1 32 2
-  pmc ${RD}_pmc_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 1 1 48 3
-  pmc ${RD}_pmc_mfma64 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" -- $SP 0 1 64 3
-  stats ${RD}_mass_shift python3 tools/mass_shift_trace.py; mv $O/${RD}_mass_shift_stats.csv $O/${RD}_mass_shift_kernel_stats.csv
+  for cfg in "32 2 10" "48 3 5" "64 3 3"; do set -- $cfg; stats ${RD}_solve$1 $SP $3 1 $1 $2 || exit 1; mv $O/${RD}_solve$1_stats.csv $O/${RD}_solve$1_kernel_stats.csv; tail -1 $O/${RD}_solve$1.log | cut -c1-200; done
+  stats ${RD}_mass_shift python3 tools/mass_shift_trace.py || exit 1; mv $O/${RD}_mass_shift_stats.csv $O/${RD}_mass_shift_kernel_stats.csv
   ls $O ;;
 *) echo "unknown recipe $R"; bash "$ROOT/tools/gpu/run.sh" help; exit 2 ;;
 esac
