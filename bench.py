@@ -1,20 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X DDalphaAMG hot path.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Headline (`metric`, `value`, `roofline`): a "step" is one fine Wilson-Clover apply (d_plus_clover_float, reference
 src/dirac_generic.c:159-277) over a 32^4 local lattice per GPU of synthetic random SU(3) links (BASELINE.json quotes the
 >= 40 %-of-HBM target on exactly this volume); inputs are resident in HBM before the timed region; on N GPUs every rank
 holds 32^4 sites of a decomposed lattice (weak scaling, halo exchange over RCCL overlapped with the interior tiles).
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.
 
-Secondary objects of the same JSON line:
+Secondary objects of the same JSON line, measured only with --full:
   solve           (N = 1) BASELINE configs[2]: two-level FGMRES+AMG on 32^4, next to the reference's own run of the same case
+  three_level_48  (N = 1) BASELINE configs[3]: three-level FGMRES+AMG on 48^4
   strong_scaling  BASELINE configs[4] / SURVEY 8(d) config 5: ONE global 64^4 lattice, 3-level AMG, divided over process
                   grids 1 / 2 (T) / 4 (T,Z) / 8 (T,Z,Y): same global gauge field and right-hand side at every N; seconds per
                   solve, iterations, and the speed-up against the committed N = 1 time
+  rehearsal       (N = 1) the per-GPU problem of the 8-GPU point of strong_scaling on one GPU (--rehearse)
   cpu_baseline    (N = 1) the REAL reference (oracle/_ref, SSE build) on the host cores of this box: its fp32 d_plus_clover
                   on the headline volume, and a bounded sample of the solve
+and (N > 1) config.halo_check_vs_host_transport: the RCCL halo exchange against the host transport before the timed steps.
 
 N > 1 without a launcher: `python bench.py --gpus N` starts the N ranks itself (one child process per GPU, before anything
 touches the GPU in the parent); under torchrun (WORLD_SIZE set) it is one of the ranks and checks N against the world size.
@@ -42,11 +46,14 @@ def parse_args():
     ap.add_argument("--strong-lattice", type=int, nargs=4, default=[64, 64, 64, 64],
                     help="global lattice of the strong-scaling solve (BASELINE configs[4]); every extent a multiple of 8 x the process grid")
     ap.add_argument("--precision", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solve", action="store_true", help="skip the 32^4 two-level solve (N = 1)")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling solve")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements and checks (CPU baselines, the solve legs, the "
+                         "strong-scaling solve and its rehearsal, the halo cross-check on N > 1); the options below select among them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-solve", action="store_true", help="with --full: skip the solve legs on one GPU (32^4 two-level, 48^4 three-level)")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the strong-scaling solve")
     ap.add_argument("--small-lattice", action="store_true",
-                    help="also time BASELINE configs[1] (the reference's 8^4 configuration, cache-resident)")
+                    help="with --full: also time BASELINE configs[1] (the reference's 8^4 configuration, cache-resident)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host"],
                     help="halo transport for N > 1; 'host' (gloo, staged through pinned memory) lets several processes share one "
                          "card for a rehearsal and is never the reported configuration")
@@ -54,9 +61,9 @@ def parse_args():
                     help="single GPU only, e.g. -1,-1,-1,1: run the fine operator through the multi-GPU machinery with the process "
                          "as its own neighbour in the directions marked -1 (RCCL transport); not a reported configuration")
     ap.add_argument("--rehearse", type=int, default=8, choices=[0, 2, 4, 8],
-                    help="N = 1 only: also run the PER-GPU problem of the N-GPU strong-scaling decomposition on this one GPU, every split "
+                    help="with --full, N = 1 only: also run the PER-GPU problem of the N-GPU strong-scaling decomposition on this one GPU, every split "
                          "direction through the RCCL self-exchange (0: skip); printed as `rehearsal` next to `strong_scaling`")
-    ap.add_argument("--leg-timeout", type=float, default=900.0, help="watchdog for the solve legs on N > 1 (seconds)")
+    ap.add_argument("--leg-timeout", type=float, default=900.0, help="with --full: watchdog for the solve legs on N > 1 (seconds)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the output vector of the last step as DIR/dirac_out.npy (DIR/dirac_out_rank<r>.npy "
                          "on N > 1): [sites][12][2] in the vector's precision, every site while all ranks together stay within "
@@ -605,12 +612,13 @@ def main():
     del U
     x = ctx.vector(0, args.precision).upload(phi)
     y = ctx.vector(0, args.precision)
-    if world > 1:
-        # the same exchange through the host transport (gloo) first, as a cross-check of the RCCL path
-        ctx.dirac_apply(y, x)
-        y_host = y.download()
-        if args.transport == "rccl":
-            ddist.attach_rccl(ctx, rank)
+    if world > 1 and args.transport == "rccl":
+        if args.full:
+            # the same exchange through the host transport (gloo) first, as a cross-check of the RCCL path
+            ctx.dirac_apply(y, x)
+            y_host = y.download()
+        ddist.attach_rccl(ctx, rank)
+        if args.full:
             ctx.dirac_apply(y, x)
             halo_check = float(np.abs(y.download() - y_host).max())
             if not (halo_check == 0.0 and np.isfinite(y_host).all()):
@@ -670,11 +678,11 @@ def main():
                          "kernel": "dirac_apply_lds_kernel<float>" if args.precision == 32 else "dirac_apply_lds_kernel<double>", "us_per_launch": launch_s * 1e6,
                          "algorithmic_bytes_per_site": bytes_site},
         }
-        if not args.no_cpu_baseline and world == 1:   # "on rank 0 at N=1 only"
+        if args.full and not args.no_cpu_baseline and world == 1:   # "on rank 0 at N=1 only"
             D, cl = ctx.get_operator()
             out["cpu_baseline"] = cpu_baseline(L, D, cl, phi)
             del D, cl
-        if world == 1 and not args.self_exchange and args.small_lattice:
+        if args.full and world == 1 and not args.self_exchange and args.small_lattice:
             try:
                 out["small_lattice"] = small_lattice_leg(local_rank)
             except Exception as e:
@@ -682,7 +690,7 @@ def main():
     ctx.close()
     del phi
 
-    # ---- the solve legs: the headline line must survive them.  On several GPUs a watchdog prints the headline with the
+    # ---- the solve legs (--full): the headline line must survive them.  On several GPUs a watchdog prints the headline with the
     # failure recorded and ends the process with a NON-ZERO code if a leg does not come back (a rank that failed alone would
     # leave the others waiting in a collective); an exception on one rank does the same.
     failed = False
@@ -696,7 +704,7 @@ def main():
                 emit(json.dumps(out))
             os._exit(3)
 
-    if world > 1:
+    if args.full and world > 1:
         # a launcher that lost another rank sends SIGTERM (torchrun, or spawn_ranks above).  The main thread may sit in a
         # collective inside the library and never return to the interpreter, so the signal is picked up through the wake-up
         # descriptor by a thread of its own: rank 0 still prints the headline, every rank ends non-zero.
@@ -713,7 +721,7 @@ def main():
             emit_and_die("terminated by the launcher: another rank failed or the job overran")
         threading.Thread(target=on_signal, daemon=True).start()
 
-    if world == 1 and not args.no_solve and not args.self_exchange and all(v % 8 == 0 for v in L):
+    if args.full and world == 1 and not args.no_solve and not args.self_exchange and all(v % 8 == 0 for v in L):
         try:
             res = run_solve(amg_params(api, L, 2, local_rank), L, [1, 1, 1, 1], [0, 0, 0, 0], 1, 0, args.transport, None)
             res["workload"] = (f"{'x'.join(map(str, L))}, near-unit gauge exp({GAUGE_EPS} i H) seed {GAUGE_SEED} (tools/synth_gauge.c), m0 -0.3, 2-level AMG "
@@ -732,7 +740,7 @@ def main():
         except Exception as e:
             out["solve"] = {"error": str(e)[:300]}
 
-    if world == 1 and not args.no_solve and not args.no_strong and not args.self_exchange and L == [32, 32, 32, 32]:
+    if args.full and world == 1 and not args.no_solve and not args.no_strong and not args.self_exchange and L == [32, 32, 32, 32]:
         # BASELINE configs[3]: 48^4, three levels, fp32 smoother / fp64 outer solver, one GPU (timed next to configs[2] and [4])
         try:
             L48 = [48, 48, 48, 48]
@@ -745,7 +753,7 @@ def main():
             out["three_level_48"] = {"error": str(e)[:300]}
 
     G = list(args.strong_lattice)
-    if not args.no_strong and not args.self_exchange:
+    if args.full and not args.no_strong and not args.self_exchange:
         if any(G[mu] % (grid[mu] * 8) for mu in range(4)):
             raise SystemExit("--strong-lattice: every extent must be a multiple of 8 x the process grid " + str(grid))
         import threading
@@ -800,7 +808,7 @@ def main():
             out["strong_scaling"] = {"error": str(e)[:300]}
         if dog:
             dog.cancel()
-    if world == 1 and args.rehearse > 1 and not args.no_strong and not args.self_exchange:
+    if args.full and world == 1 and args.rehearse > 1 and not args.no_strong and not args.self_exchange:
         # ---- rehearsal of the N-GPU point of the strong-scaling curve on ONE GPU (no multi-GPU node is available to the build):
         # the per-GPU problem of the decomposition -- local lattice G / grid_N, the same three-level method, the coarsest level
         # gathered -- with the process as its own neighbour in every split direction, so that every boundary coupling runs

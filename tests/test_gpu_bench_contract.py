@@ -1,8 +1,8 @@
-"""GPU tests (-m gpu) of bench.py's output contract: one JSON line with the metric, the roofline object of the dominant kernel
-and (N = 1) the CPU baseline; the N > 1 paths -- `bench.py --gpus 2` starting its own ranks, and the same under torchrun as the
-driver launches it -- rehearsed with two processes on the one GPU through the host transport (RCCL refuses two ranks on one
-device); and the failure behaviour: a rank that dies or hangs in the solve leg ends the job with a non-zero code, with the
-headline line still printed."""
+"""GPU tests (-m gpu) of bench.py's output contract: one JSON line with the metric and the roofline object of the dominant
+kernel, nothing more in a plain run, and with --full (N = 1) the CPU baseline and the solve legs; the N > 1 paths --
+`bench.py --gpus 2` starting its own ranks, and the same under torchrun as the driver launches it -- rehearsed with two
+processes on the one GPU through the host transport (RCCL refuses two ranks on one device); and the failure behaviour: a
+rank that dies or hangs in the solve leg ends the job with a non-zero code, with the headline line still printed."""
 import json, os, subprocess, sys
 import numpy as np
 import pytest
@@ -34,7 +34,7 @@ def check_common(d, n_gpus, steps, warmup, sites_per_gpu=32 ** 4):
 
 
 def test_single_gpu_line(tmp_path):
-    r = subprocess.run([sys.executable, BENCH, "--steps", "50", "--warmup", "10", "--no-strong", "--dump-outputs", str(tmp_path)],
+    r = subprocess.run([sys.executable, BENCH, "--steps", "50", "--warmup", "10", "--full", "--no-strong", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = last_json_line(r.stdout)
@@ -56,6 +56,23 @@ def test_single_gpu_line(tmp_path):
         assert abs(s["iterations"] - s["iterations_reference"]) <= 1
     if c["kind"] == "reference":
         assert c["solve"]["seconds"] > 0 and c["solve"]["iterations"] > 0 and c["solve"]["kind"] == "reference"
+
+
+SECONDARY = ("cpu_baseline", "small_lattice", "solve", "three_level_48", "strong_scaling", "north_star_strong_scaling", "rehearsal")
+
+
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """without --full the line carries the headline and its roofline and nothing that takes a run of its own"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert len(r.stdout.strip().splitlines()) == 1
+    d = last_json_line(r.stdout)
+    check_common(d, 1, 20, 5)
+    assert d["roofline"]["frac"] > 0.4
+    assert not [k for k in SECONDARY if k in d], sorted(d)
+    assert d["config"]["halo_check_vs_host_transport"] is None
+    assert os.listdir(tmp_path) == ["dirac_out.npy"]
 
 
 @pytest.mark.parametrize("precision,tol", [(32, 2e-6), (64, 1e-13)])
@@ -80,7 +97,7 @@ def test_dumped_output_is_the_operator_applied_to_the_bench_inputs(tmp_path, pre
 
 
 SMALL = ["--lattice", "16", "16", "16", "16", "--strong-lattice", "16", "16", "16", "16", "--steps", "5", "--warmup", "2",
-         "--transport", "host", "--no-cpu-baseline"]
+         "--transport", "host", "--full", "--no-cpu-baseline"]
 
 
 def test_bench_starts_its_own_ranks():
@@ -128,10 +145,10 @@ def test_failed_or_hung_rank_gives_nonzero_exit_and_keeps_the_headline(fault, ex
 
 
 def test_rehearsal_of_the_eight_gpu_point_on_one_gpu():
-    """`--rehearse 8` (the default at N = 1): the per-GPU problem of the 8-GPU decomposition -- here of a 32^4 lattice, local
+    """`--full --rehearse 8` (the default with --full at N = 1): the per-GPU problem of the 8-GPU decomposition -- here of a 32^4 lattice, local
     16x16x16x32 -- with three split directions through the RCCL self-exchange and the coarsest level gathered; the `rehearsal`
     object carries the predicted seconds per solve per GPU next to the N = 1 time of the same run"""
-    r = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--no-solve", "--no-cpu-baseline", "--rehearse", "8",
+    r = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--full", "--no-solve", "--no-cpu-baseline", "--rehearse", "8",
                         "--strong-lattice", "32", "32", "32", "32"], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = last_json_line(r.stdout)

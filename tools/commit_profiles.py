@@ -49,7 +49,7 @@ if have_line:
     ss = line["strong_scaling"]
     n1 = {"global_lattice": [64, 64, 64, 64], "seconds_per_solve": ss["seconds_per_solve"], "setup_seconds": ss["setup_seconds"],
           "iterations": ss["iterations"], "coarse_iterations": ss["coarse_iterations"], "true_relres": ss["true_relres"],
-          "source": "profiles/" + R + "_bench_line.json: python3 bench.py (default) on one MI355X under rocprofv3 --kernel-trace, commit " + commit}
+          "source": "profiles/" + R + "_bench_line.json: python3 bench.py --full on one MI355X under rocprofv3 --kernel-trace, commit " + commit}
     json.dump(n1, open(os.path.join(dst, R + "_strong_scaling_n1.json"), "w"), indent=1)
 
 # matrix-core busy fraction of the kernels that apply a coarse operator to many right-hand sides

@@ -101,26 +101,28 @@ selfx)        # fine operator through the RCCL self-exchange: 0, 1, 2, 3 split d
   for g in "1,1,1,1" "-1,1,1,1" "-1,-1,1,1" "-1,-1,-1,1"; do
     echo "grid $g: $(python3 bench.py --steps 500 --warmup 100 --no-solve --no-strong --no-cpu-baseline --self-exchange=$g 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["ms_per_step"]*1000,2), "us")')"
   done ;;
-rehearse)     # bench.py --rehearse N (default 8): the per-GPU problem of the N-GPU point on one GPU; run.sh rehearse "2 4 8" for the curve
-  for n in ${1:-8}; do python3 bench.py --steps 50 --warmup 10 --no-solve --no-cpu-baseline --rehearse $n 2> $O/err$n.log | tail -1 > $O/line$n.json
+rehearse)     # bench.py --full --rehearse N (default 8): the per-GPU problem of the N-GPU point on one GPU; run.sh rehearse "2 4 8" for the curve
+  for n in ${1:-8}; do python3 bench.py --steps 50 --warmup 10 --full --no-solve --no-cpu-baseline --rehearse $n 2> $O/err$n.log | tail -1 > $O/line$n.json
     python3 -c "
 import sys,json; d=json.loads(open('$O/line$n.json').read()); h=d['rehearsal']; s=d['strong_scaling']
 print('N', h.get('n_gpus_rehearsed'), 'local', h.get('local_lattice'), 'n1', round(s['seconds_per_solve'],4), 'per gpu', round(h['seconds_per_solve_per_gpu'],4), 'plain', round(h['same_lattice_without_the_machinery']['seconds_per_solve'],4), 'cost of the machinery', h.get('cost_of_the_machinery'), 'predicted', round(h['predicted_seconds_per_solve_per_gpu'],4), 'speedup', round(h['predicted_speedup_vs_n1'],2), 'its', h['iterations'], 'setup', round(h['setup_seconds'],2), 'err', h.get('error'))"
   done ;;
 rehearse_stats)  # kernel totals of the rehearsed N-GPU solve, through the machinery against the plain periodic lattice: run.sh rehearse_stats [N]
   for sx in 1 0; do stats r$sx python3 tools/rehearse_profile.py ${1:-8} $sx 2; tail -1 $O/r$sx.log | cut -c1-170; head -16 $O/r${sx}_stats.csv | short; done ;;
-driver_line)  # the driver's invocation of bench.py, timed, as the first process of the box
-  t0=$(date +%s.%N); python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/line.json 2> $O/err.log; echo "rc=$? wall $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s"
+driver_line)  # the driver's invocation of bench.py as the first process of the box, with its seconds outside the steps (run.sh driver_line --full: the full line)
+  t0=$(date +%s.%N); timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/line.json 2> $O/err.log; rc=$?; t1=$(date +%s.%N); echo "rc=$rc"
   python3 -c "
-import json; d=json.loads(open('$O/line.json').read().strip().splitlines()[-1])
-print({k:d[k] for k in ('metric','value','unit','n_gpus','steps','warmup','ms_per_step','scaling','vs_baseline','dtype','data')}); print(d['roofline']); print(d['cpu_baseline']['value'], d['cpu_baseline']['kind'], d['cpu_baseline']['cores'])
+import json,sys; d=json.loads(open('$O/line.json').read().strip().splitlines()[-1]); wall=float(sys.argv[2])-float(sys.argv[1])
+print('wall %.1f s, outside the steps %.1f s' % (wall, wall - (d['steps'] + d['warmup']) * d['ms_per_step'] * 1e-3))
+print({k:d[k] for k in ('metric','value','unit','n_gpus','steps','warmup','ms_per_step','scaling','vs_baseline','dtype','data')}); print(d['roofline'])
+if 'cpu_baseline' in d: print(d['cpu_baseline']['value'], d['cpu_baseline']['kind'], d['cpu_baseline']['cores'])
 for leg in ('solve','three_level_48','strong_scaling'):
-    if leg in d: print(leg, {k:v for k,v in d[leg].items() if k not in ('workload','coarse_operator','reference_32','per_level_messages')})" ;;
+    if leg in d: print(leg, {k:v for k,v in d[leg].items() if k not in ('workload','coarse_operator','reference_32','per_level_messages')})" $t0 $t1 ;;
 hashed)       # only the counter passes behind profiles/<round>_traffic.json and <round>_mfma_busy.json: run.sh hashed r04 ; then commit_profiles.py on its output directory
   warm && hashed ${1:-r04} && ls $O ;;
 profile)      # every artefact of profiles/<round>_* : run.sh profile r04 ; then python3 tools/commit_profiles.py gpurun_out/profile r04
   RD=${1:-r04}; warm || exit 1
-  timeout -k 10 1200 rocprofv3 --kernel-trace --stats -d $O/bench -o bench -- python3 bench.py > $O/bench_line.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
+  timeout -k 10 1200 rocprofv3 --kernel-trace --stats -d $O/bench -o bench -- python3 bench.py --full > $O/bench_line.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
   python3 tools/rocpd_export.py stats $O/bench/bench_results.db $O/${RD}_bench_kernel_stats.csv; rm -rf $O/bench; tail -c 400 $O/bench_line.json; echo
   hashed $RD || exit 1
   export SAP_BENCH_ITERS=4
