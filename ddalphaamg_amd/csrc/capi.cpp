@@ -57,6 +57,7 @@ void ddamg_hip_default_params(ddamg_hip_params* p) {
 
 int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
   DDAMG_API_BEGIN
+  const Knobs knobs = Knobs::from_env();   // the one read of the environment for this context
   DDAMG_REQUIRE(p && out, "null argument");
   DDAMG_REQUIRE(p->num_levels >= 1 && p->num_levels <= DDAMG_HIP_MAX_LEVELS, "1 <= num_levels <= 4");
   // the reference asserts -1 <= method <= 5 itself (src/init.c:982): its method-6 code (g5D_*) cannot be selected
@@ -75,14 +76,15 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
   // reference's MPI ranks do.  Process-wide device flag.
   (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
   (void)hipGetLastError();
-  std::unique_ptr<ddamg_hip_ctx> c(new ddamg_hip_ctx);
+  std::unique_ptr<ddamg_hip_ctx> c(new ddamg_hip_ctx(knobs));
   c->par = *p;
   for (int mu = 0; mu < 4; mu++) if (c->par.process_grid[mu] < 1 && c->par.process_grid[mu] != -1) { c->par.process_grid[mu] = 1; c->par.process_coords[mu] = 0; }
   c->device = p->device;
   {
     bool grid = false;
     for (int mu = 0; mu < 4; mu++) grid = grid || p->process_grid[mu] > 1 || p->process_grid[mu] == -1;
-    if (grid && comm_cus_for(p->num_levels) > 0) DDAMG_HIP_CHECK(create_cu_masked_stream(&c->stream, comm_cus_for(p->num_levels), false));
+    const int comm_cus = comm_cus_for(c->knobs, p->num_levels);
+    if (grid && comm_cus > 0) DDAMG_HIP_CHECK(create_cu_masked_stream(&c->stream, comm_cus, false));
     else DDAMG_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   }
   DDAMG_HIP_CHECK(hipEventCreate(&c->ev0));
@@ -153,8 +155,8 @@ static void drop_clover_base(ddamg_hip_ctx* c) {
 static void upload_operator(ddamg_hip_ctx* c) {
   drop_clover_base(c);      // a new operator is unscaled
   const Geometry& g = c->levels[0]->geom;
-  c->fop64.upload(g, c->D_host.data(), c->clover_host.data(), c->stream);
-  c->fop32.upload(g, c->D_host.data(), c->clover_host.data(), c->stream);
+  c->fop64.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
+  c->fop32.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
   c->have_operator = true;
   if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
   if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
@@ -288,7 +290,7 @@ int ddamg_hip_comm_init_rccl(ddamg_hip_ctx* c, const void* id128) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c && id128, "null argument");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  install_comm(c, comm_create_rccl(c->levels[0]->geom, id128, comm_cus_for(c->par.num_levels)));
+  install_comm(c, comm_create_rccl(c->levels[0]->geom, id128, comm_cus_for(c->knobs, c->par.num_levels)));
   DDAMG_API_END
 }
 
@@ -296,7 +298,7 @@ int ddamg_hip_comm_init_host(ddamg_hip_ctx* c, ddamg_hip_exchange_fn fn, ddamg_h
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c, "null argument");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  install_comm(c, comm_create_host(c->levels[0]->geom, fn, reduce_fn, user, comm_cus_for(c->par.num_levels)));
+  install_comm(c, comm_create_host(c->levels[0]->geom, fn, reduce_fn, user, comm_cus_for(c->knobs, c->par.num_levels)));
   DDAMG_API_END
 }
 

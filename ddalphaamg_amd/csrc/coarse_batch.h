@@ -22,7 +22,7 @@ bool coarse_galerkin_batch_available(int n, int ncols, size_t elem_size);
 // four forward links).  `agg_face` is the level's aggregate-face mask (bit d: the neighbour in direction d lies in
 // another aggregate).  work: 6 * V * n * 64 complex of scratch.
 void coarse_galerkin_batched(CoarseOp<float>& next, const CoarseOp<float>& op, const CoarseTransfer<float>& ip,
-                             const unsigned char* d_agg_face, float* work, hipStream_t st);
+                             const unsigned char* d_agg_face, float* work, const Knobs& knobs, hipStream_t st);
 inline size_t coarse_galerkin_batch_work(int V, int n) { return (size_t)6 * V * n * COARSE_BATCH_COLS * 2; }
 
 }  // namespace ddamg

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void coarse_batch_restrict_store_mfma_kernel(f
 }
 
 void coarse_galerkin_batched(CoarseOp<float>& next, const CoarseOp<float>& op, const CoarseTransfer<float>& ip,
-                             const unsigned char* d_agg_face, float* work, hipStream_t st) {
+                             const unsigned char* d_agg_face, float* work, const Knobs& knobs, hipStream_t st) {
   const int V = op.V(), n = op.n(), N = ip.nvec;
   DDAMG_REQUIRE(coarse_galerkin_batch_available(n, 2 * N, sizeof(float)), "batched coarse Galerkin: unsupported shape");
   DDAMG_REQUIRE(next.n() == 2 * N && next.V() == ip.num_aggs, "batched coarse Galerkin: next level does not match the transfer operator");
@@ -240,7 +240,7 @@ void coarse_galerkin_batched(CoarseOp<float>& next, const CoarseOp<float>& op, c
     default: hipLaunchKernelGGL((coarse_batch_apply_kernel<4>), dim3(V), dim3(256), 0, st, Y, bs, Vb, dev, d_agg_face, halo); break;
   }
   DDAMG_HIP_CHECK(hipGetLastError());
-  const bool valu = getenv("DDAMG_COARSE_RESTRICT_VALU") != nullptr;   // read at every build: tests switch it within one process
+  const bool valu = knobs.coarse_restrict_valu;
   const int KC = (ip.agg_sites / 2) * (n / 2), ldp = KC + (36 - KC % 32) % 32;   // ldp = 4 mod 32: the 16 rows x 4 k of an operand read spread over the banks
   if (!valu && (n / 2) % 4 == 0 && N <= 32 && ip.pstride % 2 == 0 && ip.agg_sites % 2 == 0 && ldp <= RS_LDP_MAX)
     hipLaunchKernelGGL(coarse_batch_restrict_store_mfma_kernel, dim3(ip.num_aggs), dim3(256), 0, st, next.matrices(), next.nt(), next.msize(), Y, bs,

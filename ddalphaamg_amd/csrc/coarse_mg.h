@@ -20,7 +20,8 @@ struct CoarseTransfer {
   T* tv = nullptr;
   T* P = nullptr;
   int* agg_csite = nullptr;
-  void alloc(const Geometry& g, const Geometry& gc, int n_, int nvec_);
+  const Knobs* knobs = nullptr;   // the context's switches (alloc): coarse_gs_global, coarse_gs_workgroup_form
+  void alloc(const Geometry& g, const Geometry& gc, int n_, int nvec_, const Knobs& knobs_);
   void release();
   T* test_vector(int j) const { return tv + pstride * j; }
   T* interp_vector(int j) const { return P + pstride * j; }

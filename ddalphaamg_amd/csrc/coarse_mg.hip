@@ -31,8 +31,8 @@ __device__ __forceinline__ void wg_allsum(double (&v)[NV], double* red /* [NV][n
 
 // ---- transfer ------------------------------------------------------------------------------------
 template <typename T>
-void CoarseTransfer<T>::alloc(const Geometry& g, const Geometry& gc, int n_, int nvec_) {
-  V = g.V; n = n_; nvec = nvec_; num_aggs = g.num_aggs; agg_sites = g.agg_sites;
+void CoarseTransfer<T>::alloc(const Geometry& g, const Geometry& gc, int n_, int nvec_, const Knobs& knobs_) {
+  knobs = &knobs_; V = g.V; n = n_; nvec = nvec_; num_aggs = g.num_aggs; agg_sites = g.agg_sites;
   DDAMG_REQUIRE(gc.V == g.num_aggs, "coarse lattice does not match the aggregate decomposition");
   pstride = (size_t)V * n * 2;
   DDAMG_HIP_CHECK(device_alloc(&agg_csite, sizeof(int) * num_aggs));
@@ -269,10 +269,10 @@ template <typename T>
 void CoarseTransfer<T>::orthonormalize(int passes, hipStream_t st) {
   DDAMG_HIP_CHECK(hipMemcpyAsync(P, tv, sizeof(T) * pstride * nvec, hipMemcpyDeviceToDevice, st));
   const int E = agg_sites * n;
-  const bool global_form = getenv("DDAMG_COARSE_GS_GLOBAL") != nullptr;   // read at every call: tests switch it within one process
+  const bool global_form = knobs->coarse_gs_global;
+  // (coarse_gs_workgroup_form: the bit-identical register form above)
+  const bool wave_form = !global_form && !knobs->coarse_gs_workgroup_form && agg_sites * (n / 2) <= 64 * 8 && n % 2 == 0;
   for (int p = 0; p < passes; p++) {
-    const char* form = getenv("DDAMG_COARSE_GS_FORM");      // "workgroup": the bit-identical register form above
-    const bool wave_form = !global_form && !(form && form[0] == 'w') && agg_sites * (n / 2) <= 64 * 8 && n % 2 == 0;
     if (wave_form) hipLaunchKernelGGL((aos_gs_wave_kernel<T, 8>), dim3((2 * num_aggs + 3) / 4), dim3(256), 0, st, P, pstride, nvec, n, agg_sites, 2 * num_aggs);
     else if (!global_form && E <= 256 * 4) hipLaunchKernelGGL((aos_gs_reg_kernel<T, 4>), dim3(num_aggs), dim3(256), 0, st, P, pstride, nvec, n, agg_sites);
     else hipLaunchKernelGGL(aos_gs_kernel<T>, dim3(num_aggs), dim3(256), 0, st, P, pstride, nvec, n, agg_sites);

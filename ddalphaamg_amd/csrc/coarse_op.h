@@ -41,7 +41,7 @@ template <typename T>
 class CoarseOp {
  public:
   ~CoarseOp();
-  void alloc(const Geometry& g, int n);
+  void alloc(const Geometry& g, int n, const Knobs& knobs);
   // import from the reference's storage (lexicographic coarse sites):
   //   D_ref [V][4][n*n] complex: blocks A,C,B,D each (n/2)^2 column-major (src/coarse_operator_generic.h:124-143)
   //   clover_ref [V][n(n+1)/2] complex: triu(A), triu(D) packed column-major, then B full column-major (src/coarse_operator_generic.c:109-111)
@@ -116,6 +116,7 @@ class CoarseOp {
   mutable HaloArena wide_arena_;      // created at the first wide_halo_exchange
   mutable size_t wide_row_bytes_ = 0;
   const Geometry* geom_ = nullptr;
+  const Knobs* knobs_ = nullptr;   // the context's switches (alloc): coarse_sap_unfused, coarse_apply_once_min_sites
   Comm* comm_ = nullptr;
   // on a process grid: sites without / with a neighbour on another process (sorted), for the overlap of the exchange with
   // the interior work (the reference's ghost_sendrecv ... interior hopping terms ... ghost_wait, src/coarse_oddeven_generic.c:

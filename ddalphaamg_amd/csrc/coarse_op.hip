@@ -422,7 +422,7 @@ void CoarseOp<T>::free_block_plan(BlockPlan& p) {
 
 template <typename T>
 bool CoarseOp<T>::block_minres(T* x, T* r, T* latest, const int* blocks, int nblocks, const BlockPlan& plan, int iters, double eps, hipStream_t st) const {
-  const bool off = getenv("DDAMG_COARSE_SAP_UNFUSED") != nullptr;   // read at every call: tests switch it within one process
+  const bool off = knobs_->coarse_sap_unfused;
   const int np = 8 * nt_, BS = plan.block_sites;
   const size_t lds = 48 * sizeof(double) + sizeof(T) * 2 * np * ((size_t)2 * BS + (size_t)2 * plan.nitems);
   if (off || plan.nitems == 0 || (size_t)BS * n_ > (size_t)BLOCK_MINRES_THREADS * BLOCK_MINRES_MAXE || lds > 150 * 1024) return false;
@@ -548,8 +548,7 @@ template <typename T> void CoarseOp<T>::apply(T* out, const T* in, hipStream_t s
   // events, src/coarse_oddeven_generic.c:447-581: ghost_sendrecv, interior hopping terms, ghost_wait, the rest).
   const bool dist = arena_.active();
   if (dist) pack_and_begin(in, st);
-  static const int min_sites = getenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES") ? atoi(getenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES")) : 2048;
-  if (V_ < min_sites) {   // small (coarsest) lattices sit in the Infinity Cache: the second read is free, the extra launch is not
+  if (V_ < knobs_->coarse_apply_once_min_sites) {   // small (coarsest) lattices sit in the Infinity Cache: the second read is free, the extra launch is not
     if (dist) {
       launch_site<T>(dev(), out, in, 0, (int)h_interior_.size(), MODE_FULL, 1.0, -1.0, false, st, d_interior_);
       arena_.exchange_finish(comm_, st);
@@ -707,8 +706,8 @@ template <typename T> CoarseOp<T>::~CoarseOp() {
   if (d_fwd_off_mask_) (void)hipFree(d_fwd_off_mask_);
 }
 template <typename T>
-void CoarseOp<T>::alloc(const Geometry& g, int n) {
-  geom_ = &g;
+void CoarseOp<T>::alloc(const Geometry& g, int n, const Knobs& knobs) {
+  geom_ = &g; knobs_ = &knobs;
   V_ = g.V; n_ = n; nt_ = (n + 7) / 8; msize_ = (size_t)nt_ * nt_ * 64;
   DDAMG_REQUIRE(n % 2 == 0 && nt_ <= 8, "coarse dof per site must be even and at most 64");
   DDAMG_HIP_CHECK(device_alloc(&M_, sizeof(T) * 2 * msize_ * 5 * V_));

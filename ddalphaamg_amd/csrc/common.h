@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include "knobs.h"
 
 #define DDAMG_HIP_CHECK(expr)                                                                  \
   do {                                                                                         \
@@ -43,8 +44,7 @@ namespace ddamg {
 template <typename P>
 inline hipError_t device_alloc(P** p, size_t bytes) {
   hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
-  static const bool poison = getenv("DDAMG_POISON") != nullptr;
-  if (e == hipSuccess && poison && bytes) {
+  if (e == hipSuccess && poison_allocations() && bytes) {
     e = hipMemset(*p, 0xFF, bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();   // the library's streams do not synchronise with the null stream
   }
@@ -86,8 +86,8 @@ inline hipError_t create_cu_masked_stream(hipStream_t* st, int n_reserved, bool 
 // the fine operator ALONE is faster with 24 reserved CUs (185 against 213 us per apply: its transport kernel does not queue
 // behind the interior tiles), the multigrid solve as a whole is faster on plain streams (106.7 against 117 ms per solve, setup
 // 2.36 against 2.66 s: every kernel of a CU-masked stream pays for the mask, whatever the number of CUs).  So contexts without
-// a hierarchy (operator, pure Krylov methods) reserve 24 CUs, multigrid contexts none; DDAMG_COMM_CUS overrides both.
-inline int comm_cus_for(int num_levels) { const char* e = getenv("DDAMG_COMM_CUS"); return e ? atoi(e) : (num_levels <= 1 ? 24 : 0); }
+// a hierarchy (operator, pure Krylov methods) reserve 24 CUs, multigrid contexts none; DDAMG_COMM_CUS overrides both
+// (comm_cus_for, knobs.h).
 
 
 enum { DIR_T = 0, DIR_Z = 1, DIR_Y = 2, DIR_X = 3 };  // reference src/clifford.h:33

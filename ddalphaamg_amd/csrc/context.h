@@ -33,6 +33,8 @@ struct Level {
 }  // namespace ddamg
 
 struct ddamg_hip_ctx {
+  explicit ddamg_hip_ctx(const ddamg::Knobs& k) : knobs(k) {}
+  const ddamg::Knobs knobs;   // the DDAMG_* switches as the environment held them at ddamg_hip_create (knobs.h)
   ddamg_hip_params par;
   int device = 0;
   hipStream_t stream = nullptr;

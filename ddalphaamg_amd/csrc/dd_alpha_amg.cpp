@@ -227,8 +227,7 @@ void common_init(const dd_alpha_amg_par& p) {
   }
   check(ddamg_hip_create(&S.hp, &S.ctx), "dd_alpha_amg_init");
   if (nproc > 1) {
-    const char* t = getenv("DDAMG_HIP_TRANSPORT");   // "host": MPI moves staged buffers; default: RCCL over xGMI
-    if (comm_init_mpi(S.ctx, comm, !(t && std::string(t) == "host"))) fatal("dd_alpha_amg_init: %s", ddamg_hip_last_error());
+    if (comm_init_mpi(S.ctx, comm, !S.ctx->knobs.host_transport)) fatal("dd_alpha_amg_init: %s", ddamg_hip_last_error());
   }
   S.V = 1; for (int mu = 0; mu < 4; mu++) S.V *= S.hp.local_lattice[0][mu];
   S.inited = true;

@@ -52,7 +52,7 @@ class FineOp {
 
   // D_ref: [V][4][9] complex (lexicographic sites), clover_ref: [V][42] complex, both fp64 as the
   // reference holds them in g.op_double (src/dirac.c:60-168)
-  void upload(const Geometry& g, const double* D_ref, const double* clover_ref, hipStream_t st);
+  void upload(const Geometry& g, const double* D_ref, const double* clover_ref, const Knobs& knobs, hipStream_t st);
   // mass shift without a new upload (shift_update_PRECISION src/dirac_generic.c:504-551): the 12 real diagonal clover entries
   // of every site become those of `clover64` plus `diff`, and the 6x6 inverses the odd-even kernels read are rebuilt from the
   // same fp64 values.  clover64: the fp64 operator's clover field (its own one for T = double, where diff is applied in

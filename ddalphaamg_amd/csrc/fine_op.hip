@@ -683,7 +683,7 @@ __global__ __launch_bounds__(128) void clover_compress_kernel(T* __restrict__ cl
 }
 
 template <typename T>
-void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clover_ref, hipStream_t st) {
+void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clover_ref, const Knobs& knobs, hipStream_t st) {
   const size_t V = g.V;
   V_ = g.V;
   if (!D_) {
@@ -708,9 +708,7 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   // two-row links (a third less link traffic in dirac_apply_lds_kernel and the Schwarz block solver) when every link allows it
   Dc_ = nullptr;
   {
-    const char* lc = getenv("DDAMG_LINK_COMPRESSION");
-    const bool off = lc != nullptr && atoi(lc) == 0;
-    if (!off && g.block_sites == 256) {
+    if (knobs.link_compression && g.block_sites == 256) {
       if (!Dc_store_) {
         DDAMG_HIP_CHECK(device_alloc(&Dc_store_, sizeof(T) * 48 * V));
         DDAMG_HIP_CHECK(device_alloc(&Dsgn_, 4 * V + sizeof(int)));
@@ -728,8 +726,7 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   // 56-real clover for the fp32 apply (dirac_apply_lds_kernel; a fifth less clover traffic) when every block allows it
   Cc_ = nullptr;
   if constexpr (sizeof(T) == 4) {
-    const char* cc = getenv("DDAMG_CLOVER_COMPRESSION");
-    if (!(cc != nullptr && atoi(cc) == 0)) {
+    if (knobs.clover_compression) {
       if (!Cc_store_) DDAMG_HIP_CHECK(device_alloc(&Cc_store_, sizeof(T) * 56 * V + sizeof(int)));
       int* d_bad = reinterpret_cast<int*>(Cc_store_ + 56 * V);   // one flag behind the field
       DDAMG_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), st));

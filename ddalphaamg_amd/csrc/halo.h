@@ -24,7 +24,7 @@ struct HaloDev {
 
 struct Comm;  // transport state (RCCL communicator or host callback), shared by both precisions
 
-// comm_cus: compute units reserved for the transport stream (0: a plain high-priority stream), see common.h comm_cus_for
+// comm_cus: compute units reserved for the transport stream (0: a plain high-priority stream), see comm_cus_for (knobs.h)
 Comm* comm_create_rccl(const Geometry& g, const void* id128, int comm_cus);
 Comm* comm_create_host(const Geometry& g, ddamg_hip_exchange_fn fn, ddamg_hip_allreduce_fn reduce_fn, void* user, int comm_cus);
 void comm_destroy(Comm* c);

@@ -38,7 +38,8 @@ struct Gmres {
   bool prec_gives_Dphi = false;  // preconditioner also returns A*phi in Dphi (src/linsolve_generic.c:832-835)
   // the reference's SINGLE_ALLREDUCE_ARNOLDI build option (src/linsolve_generic.c:735-800): the new vector's norm comes out
   // of the same reduction as the Gram-Schmidt coefficients, ||w||^2 - sum |h_i|^2 -- one global sum per step instead of two
-  bool single_allreduce = getenv("DDAMG_SINGLE_ALLREDUCE_ARNOLDI") != nullptr;
+  // (DDAMG_SINGLE_ALLREDUCE_ARNOLDI); set by the owner where the solver is allocated
+  bool single_allreduce = false;
   // the reference's PIPELINED_ARNOLDI build option (src/linsolve_generic.c:668-733; coarsest level only, no preconditioner):
   // the global sum of step k travels while the operator is applied for step k+1.  Needs the Z vectors (alloc with_Z) and
   // one more of them; set by the owner before alloc.

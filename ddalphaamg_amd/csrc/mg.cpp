@@ -13,8 +13,8 @@
 namespace ddamg {
 
 template <typename T>
-Multigrid<T>::Multigrid(const ddamg_hip_params& par, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st)
-    : par_(par), st_(st) {
+Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st)
+    : par_(par), knobs_(knobs), st_(st) {
   const int L = par.num_levels;
   DDAMG_REQUIRE(L >= 2 && L <= DDAMG_HIP_MAX_LEVELS && (int)geoms.size() == L, "multigrid needs 2..4 levels");
   size_t max_coarse = 0;
@@ -33,13 +33,14 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const std::vector<const Geo
     const Geometry& g = *lv.g;
     for (int i = 0; i < 4; i++) { DDAMG_HIP_CHECK(device_alloc(&lv.buf[i], sizeof(T) * lv.nel)); DDAMG_HIP_CHECK(device_zero(lv.buf[i], sizeof(T) * lv.nel)); }
     if (d == 0) lv.fop = fop;
-    else lv.cop.alloc(g, lv.n);
+    else lv.cop.alloc(g, lv.n, knobs_);
     if (!lv.coarsest) {
       if (par.method == 4) {
         // smoother = GMRES on the odd-even Schur complement of this level (schwarz_PRECISION_alloc, src/schwarz_generic.c:78-83:
         // restart length block_iter, tolerance EPS_PRECISION, no preconditioner; the V-cycle sets the number of restarts)
         for (int i = 0; i < 3; i++) { DDAMG_HIP_CHECK(device_alloc(&lv.sbuf[i], sizeof(T) * lv.nel)); DDAMG_HIP_CHECK(device_zero(lv.sbuf[i], sizeof(T) * lv.nel)); }
         lv.srw.init(par.block_iter[d] + 8);
+        lv.sgm.single_allreduce = knobs_.single_allreduce_arnoldi;
         lv.sgm.alloc(lv.nel, par.block_iter[d], false);
         lv.sgm.tol = sizeof(T) == 4 ? 1e-6 : 1e-14;
         // fine level: the Krylov vectors live on the even sites, which the site order keeps as the first half of every
@@ -60,8 +61,8 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const std::vector<const Geo
           }
         }
       }
-      if (d == 0) { if (par.method != 4) lv.fsap.setup(g, fop, par.block_iter[0], par.method, st_, par.odd_even != 0); lv.fip.alloc(g, *geoms[1], lv.nvec); }
-      else { if (par.method != 4) lv.csap.setup(g, &lv.cop, par.block_iter[d], par.method, st_); lv.cip.alloc(g, *geoms[d + 1], lv.n, lv.nvec); }
+      if (d == 0) { if (par.method != 4) lv.fsap.setup(g, fop, par.block_iter[0], par.method, knobs_, st_, par.odd_even != 0); lv.fip.alloc(g, *geoms[1], lv.nvec, knobs_); }
+      else { if (par.method != 4) lv.csap.setup(g, &lv.cop, par.block_iter[d], par.method, st_); lv.cip.alloc(g, *geoms[d + 1], lv.n, lv.nvec, knobs_); }
       DDAMG_HIP_CHECK(device_alloc(&lv.d_agg_face, g.V));
       DDAMG_HIP_CHECK(hipMemcpy(lv.d_agg_face, g.agg_face.data(), g.V, hipMemcpyHostToDevice));
       if (d == 0) {
@@ -97,6 +98,7 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const std::vector<const Geo
     if (d > 0 && !lv.coarsest) {
       // K-cycle FGMRES of this level (src/init_generic.c:155-160): restart kcycle_restart, kcycle_max_restart cycles
       lv.rw.init(std::max(par.kcycle_restart, PANEL_COLUMNS * lv.nvec) + 8);    // the Gram-Schmidt panels project on up to nvec vectors
+      lv.gm.single_allreduce = knobs_.single_allreduce_arnoldi;
       lv.gm.alloc(lv.nel, par.kcycle_restart, true);
       lv.gm.num_restart = par.kcycle_max_restart;
       lv.gm.tol = par.kcycle_tol;
@@ -125,7 +127,8 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const std::vector<const Geo
     if (lv.coarsest) {
       // coarsest-level GMRES on the even-site Schur complement (src/init_generic.c:148-154)
       lv.rw.init(std::max(par.coarse_iter, 8) + 4);
-      lv.gm.pipelined = getenv("DDAMG_PIPELINED_ARNOLDI") != nullptr;   // the reference's -DPIPELINED_ARNOLDI build, at run time
+      lv.gm.pipelined = knobs_.pipelined_arnoldi;
+      lv.gm.single_allreduce = knobs_.single_allreduce_arnoldi;
       lv.gm.alloc(lv.nel, par.coarse_iter, lv.gm.pipelined);
       lv.gm.num_restart = par.coarse_restart;
       lv.gm.tol = par.coarse_tol;
@@ -210,7 +213,7 @@ void Multigrid<T>::setup_gathered_coarsest() {
   DDAMG_HIP_CHECK(device_alloc(&G.d_d2g, sizeof(int) * gd.V));
   DDAMG_HIP_CHECK(hipMemcpy(G.d_g2d, g2d.data(), sizeof(int) * V, hipMemcpyHostToDevice));
   DDAMG_HIP_CHECK(hipMemcpy(G.d_d2g, d2g.data(), sizeof(int) * gd.V, hipMemcpyHostToDevice));
-  G.cop.alloc(G.g, n);
+  G.cop.alloc(G.g, n, knobs_);
   const size_t nel = (size_t)V * n * 2;
   for (int i = 0; i < 2; i++) { DDAMG_HIP_CHECK(device_alloc(&G.buf[i], sizeof(T) * nel)); DDAMG_HIP_CHECK(device_zero(G.buf[i], sizeof(T) * nel)); }
   // landing zone of the all-gathers: the operator is the larger payload (5 matrices per site)
@@ -218,6 +221,7 @@ void Multigrid<T>::setup_gathered_coarsest() {
   DDAMG_HIP_CHECK(device_alloc(&G.raw, sizeof(T) * raw_elems));
   G.rw.init(std::max(par_.coarse_iter, 8) + 4);
   G.gm.pipelined = false;     // nothing to hide: the reductions are local
+  G.gm.single_allreduce = knobs_.single_allreduce_arnoldi;
   G.gm.alloc(nel, par_.coarse_iter, false);
   G.gm.num_restart = par_.coarse_restart;
   G.gm.tol = par_.coarse_tol;
@@ -480,7 +484,7 @@ bool Multigrid<T>::level1_multi_ready(int ncols) {
       DDAMG_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
       const size_t need = CoarseMulti::workspace_bytes(*l1.g, l1.n, l1.gm.restart_length);
       if (need + need / 8 > free_b) {
-        if (getenv("DDAMG_SETUP_TIMING")) fprintf(stderr, "[ddamg setup] level 1 one vector at a time: %zu bytes free, %zu needed\n", free_b, need);
+        if (knobs_.setup_timing) fprintf(stderr, "[ddamg setup] level 1 one vector at a time: %zu bytes free, %zu needed\n", free_b, need);
         return false;
       }
       multi1_.init(*l1.g, &l1.cop, &l1.cip, par_.block_iter[1], st_);
@@ -593,8 +597,7 @@ void Multigrid<T>::vcycle(int l, T* phi, T* Dphi, const T* eta, int res) {
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 template <typename T>
 double Multigrid<T>::tick(const char* phase, double t0) {
-  static const bool on = getenv("DDAMG_SETUP_TIMING") != nullptr;
-  if (!on) return 0;
+  if (!knobs_.setup_timing) return 0;
   DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
   const double t = now_s();
   if (phase) {
@@ -707,19 +710,19 @@ void Multigrid<T>::build_coarse_operator(int l) {
   MGLevel<T>& nx = *lv_[l + 1];
   const int N = lv.nvec;
   const double t_start = tick(nullptr, 0);
-  static const bool no_batch = getenv("DDAMG_GALERKIN_UNBATCHED") != nullptr;
+  const bool no_batch = knobs_.galerkin_unbatched;
   if (l == 0 && !no_batch && Interpolation<T>::restrict_batch_available(lv.fip.agg_sites, N)) {
     // batched form: D P for a whole batch of columns (5 fields each), then ONE restriction on the matrix cores
     const size_t ws = (size_t)24 * lv.g->V;             // one fine vector
     const size_t cs = (size_t)nx.g->V * nx.n * 2;       // one coarse vector
     // the four forward parts of a column on the aggregate faces only (AggFaces, transfer.h): 2 instead of 5 fields per column
     // to write and to restrict with 4^4 aggregates
-    const bool no_compact = getenv("DDAMG_GALERKIN_FULL_FIELDS") != nullptr;   // read at every build: tests switch it within one process
+    const bool no_compact = knobs_.galerkin_full_fields;
     const AggFaces& af = lv.agg_faces;
     const bool compact = !no_compact && 2 * N <= 64 && Interpolation<T>::restrict_compact_available(lv.fip.agg_sites, N, af);
     // ... and their restriction written straight into the next level's matrices (DDAMG_GALERKIN_STORE_COLUMNS: through coarse
     // column vectors and one store launch per column, as the full-field path does)
-    const bool direct = compact && getenv("DDAMG_GALERKIN_STORE_COLUMNS") == nullptr;
+    const bool direct = compact && !knobs_.galerkin_store_columns;
     const int nagg = lv.fip.num_aggs, as = lv.fip.agg_sites;
     const size_t wcol = compact ? (size_t)24 * af.column_sites(nagg) : 5 * ws;          // one column of W, whole lattice
     const size_t wcol_agg = compact ? (size_t)24 * af.column_sites(1) : (size_t)5 * 24 * as;   // ... one aggregate of it
@@ -732,7 +735,6 @@ void Multigrid<T>::build_coarse_operator(int l) {
       gal_batch_ = 2 * N;
       while (gal_batch_ > 1 && (gal_batch_ > max_batch || sizeof(T) * gal_batch_ * (wcol + 5 * cs) > free_b / 2)) gal_batch_ = (gal_batch_ + 1) / 2;
       gal_slab_aggs_ = 0;
-      const char* force_slab = getenv("DDAMG_GALERKIN_SLAB_AGGS");   // tests: slabs of this many aggregates
       if (2 * N <= max_batch && !lv.fop->distributed()) {
         // keep ALL columns and walk the lattice in slabs of whole aggregates -- D P and its restriction are local to an
         // aggregate.  Fewer columns per pass would starve the N dimension of the restriction GEMM (64^4: 6 of 48 columns, 30 of
@@ -749,7 +751,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
         gal_slab_aggs_ = (int)std::min<size_t>((size_t)nagg, std::max<size_t>(1, budget / per_agg));
         const size_t borrow = (sizeof(T) * (size_t)N * ws + per_agg - 1) / per_agg;      // aggregates whose slab holds Nvec fine vectors
         gal_slab_aggs_ = (int)std::min<size_t>((size_t)gal_slab_aggs_, std::max<size_t>(borrow, 512));
-        if (force_slab) gal_slab_aggs_ = std::max(1, std::min(atoi(force_slab), nagg));
+        if (knobs_.galerkin_slab_aggs.set) gal_slab_aggs_ = std::max(1, std::min(knobs_.galerkin_slab_aggs.value, nagg));   // tests
         DDAMG_REQUIRE(per_agg * (size_t)gal_slab_aggs_ + coarse_b < free_b, "Galerkin construction: slab workspace does not fit the free device memory");
         gal_batch_ = 2 * N;
         DDAMG_HIP_CHECK(device_alloc(&gal_W_, per_agg * (size_t)gal_slab_aggs_));
@@ -766,9 +768,6 @@ void Multigrid<T>::build_coarse_operator(int l) {
     }
     const int batch = gal_batch_;
     DDAMG_REQUIRE(direct || gal_C_elems_ >= (size_t)5 * gal_batch_ * cs, "Galerkin construction: the workspace of this context was sized for the direct store of the restriction");
-    // ... and for face-compacted or full fields: the knobs are read at every build, the workspace is sized at the first one of a setup
-    DDAMG_REQUIRE(gal_W_elems_ >= (gal_slab_aggs_ > 0 ? (size_t)2 * N * wcol_agg * std::min(gal_slab_aggs_, nagg) : (size_t)batch * wcol),
-                  "Galerkin construction: the workspace of this context was sized for another field layout (DDAMG_GALERKIN_FULL_FIELDS changed between two builds of one setup)");
     T *Wb = gal_W_, *Cb = gal_C_;
     if (gal_slab_aggs_ > 0) {
       for (int a0 = 0; a0 < nagg; a0 += gal_slab_aggs_) {
@@ -776,7 +775,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
         const size_t wss = (size_t)24 * na * as;        // one field of this slab
         if (compact) {
           for (int c = 0; c < 2 * N; c++)
-            aggregate_dirac_compact<T>(Wb + (size_t)c * na * wcol_agg, interpolation_column(lv.fip, c % N), c / N, *lv.fop, lv.d_agg_face, af, a0, na, st_);
+            aggregate_dirac_compact<T>(Wb + (size_t)c * na * wcol_agg, interpolation_column(lv.fip, c % N), c / N, *lv.fop, lv.d_agg_face, af, a0, na, knobs_, st_);
           lv.fip.restrict_batch_compact(Cb, cs, Wb, 2 * N, af, a0, na, st_, direct ? nx.cop.matrices() : nullptr, nx.cop.nt(), nx.cop.msize(), 0);
         } else {
           for (int c = 0; c < 2 * N; c++)
@@ -790,7 +789,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
       const int nb = std::min(batch, 2 * N - c0);
       if (compact) {
         for (int c = 0; c < nb; c++)
-          aggregate_dirac_compact<T>(Wb + (size_t)c * wcol, interpolation_column(lv.fip, (c0 + c) % N), (c0 + c) / N, *lv.fop, lv.d_agg_face, af, 0, nagg, st_);
+          aggregate_dirac_compact<T>(Wb + (size_t)c * wcol, interpolation_column(lv.fip, (c0 + c) % N), (c0 + c) / N, *lv.fop, lv.d_agg_face, af, 0, nagg, knobs_, st_);
         lv.fip.restrict_batch_compact(Cb, cs, Wb, nb, af, 0, nagg, st_, direct ? nx.cop.matrices() : nullptr, nx.cop.nt(), nx.cop.msize(), c0);
       } else {
         for (int c = 0; c < nb; c++)
@@ -810,7 +809,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
     if (!no_batch && coarse_galerkin_batch_available(lv.n, 2 * N, sizeof(T))) {
       // all 2*Nvec columns at once on the matrix cores (coarse_batch.hip)
       if (!gal_cwork_) DDAMG_HIP_CHECK(device_alloc(&gal_cwork_, sizeof(T) * coarse_galerkin_batch_work(lv_[1]->g->V, lv_[1]->n)));
-      coarse_galerkin_batched(nx.cop, lv.cop, lv.cip, lv.d_agg_face, gal_cwork_, st_);
+      coarse_galerkin_batched(nx.cop, lv.cop, lv.cip, lv.d_agg_face, gal_cwork_, knobs_, st_);
       if (nx.coarsest || par_.method == 4) nx.cop.compute_self_inverse(st_);   // D_oo^-1 of the Schur complements
       if (nx.coarsest) regather_coarsest_operator();
       DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
@@ -892,7 +891,7 @@ void Multigrid<T>::initial_setup_from(int l0) {
 // smoother calls stay one vector at a time.  Borrows the Galerkin workspace between two builds; fp32.
 template <typename T>
 bool Multigrid<T>::bootstrap_vcycles_batched() {
-  const bool off = getenv("DDAMG_BOOTSTRAP_UNBATCHED") != nullptr;   // read at every call: tests switch it within one process
+  const bool off = knobs_.bootstrap_unbatched;
   MGLevel<T>& lv = *lv_[0];
   MGLevel<T>& nx = *lv_[1];
   const int N = lv.nvec;
@@ -904,9 +903,9 @@ bool Multigrid<T>::bootstrap_vcycles_batched() {
   // the borrowed workspace holds `cap` fine vectors: all Nvec in a first setup; fewer next to a context that already holds its
   // solver workspace (64^4: 17 of 24), and then the interpolation + smoothing at the end goes through it in groups
   int cap = (int)std::min<size_t>((size_t)N, gal_W_elems_ / ws);
-  if (const char* e = getenv("DDAMG_BOOTSTRAP_GROUP")) cap = std::max(1, std::min(cap, atoi(e)));   // tests: groups at any volume
+  if (knobs_.bootstrap_group.set) cap = std::max(1, std::min(cap, knobs_.bootstrap_group.value));   // tests: groups at any volume
   if (cap < 1 || gal_C_elems_ < (size_t)2 * N * cs) {
-    if (getenv("DDAMG_SETUP_TIMING"))
+    if (knobs_.setup_timing)
       fprintf(stderr, "[ddamg setup] bootstrap one vector at a time: workspace %zu / %zu elements, needed %zu / %zu\n", gal_W_elems_, gal_C_elems_, (size_t)N * ws, (size_t)2 * N * cs);
     return false;
   }
@@ -989,7 +988,7 @@ void Multigrid<T>::bootstrap(int l, int iters) {
     // the order 0 .. i-1; the ones on the earlier vectors of its own panel are taken from the vector as the first pass left it
     // (classical Gram-Schmidt takes all of them from the original vector: the same in exact arithmetic, differences of the order
     // of the rounding of the dots).  A quarter of the vector reads of the column-by-column form (DDAMG_TV_GS_COLUMNWISE).
-    const bool columnwise = getenv("DDAMG_TV_GS_COLUMNWISE") != nullptr;   // read at every call: tests switch it within one process
+    const bool columnwise = knobs_.tv_gs_columnwise;
     const int CBp = columnwise ? 1 : PANEL_COLUMNS;
     for (int i0 = 0; i0 < lv.nvec; i0 += CBp) {
       const int nb = std::min(CBp, lv.nvec - i0);

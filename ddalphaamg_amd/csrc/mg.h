@@ -77,7 +77,8 @@ struct GatheredCoarsest {
 template <typename T>
 class Multigrid {
  public:
-  Multigrid(const ddamg_hip_params& par, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st);
+  // knobs: the context's switches (knobs.h); they outlive the hierarchy and reach every object created for it
+  Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st);
   ~Multigrid();
 
   // ---- setup -------------------------------------------------------------------------------
@@ -123,6 +124,7 @@ class Multigrid {
 
  private:
   ddamg_hip_params par_;
+  const Knobs& knobs_;
   hipStream_t st_;
   Comm* comm_ = nullptr;
   unsigned long long rng_stream_ = 0;

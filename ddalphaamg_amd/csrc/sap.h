@@ -35,7 +35,7 @@ class SapSmoother {
   ~SapSmoother();
   // method: 1 additive, 2 red-black, 3 sixteen colours (g.method of the reference, src/vcycle_generic.c:33-39)
   // odd_even == false: MinRes on the whole block instead of its even-site Schur complement (g.odd_even == 0)
-  void setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, hipStream_t st, bool odd_even = true);
+  void setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, const Knobs& knobs, hipStream_t st, bool odd_even = true);
   // phi = smoothed iterate after `cycles` red-black sweeps.  res==NO_RES: start from phi=0, r=eta;
   // res==RES: start from the given phi.  (Dphi output of the reference's mixed_precision==2 path is
   // produced when Dphi != nullptr.)
@@ -47,6 +47,7 @@ class SapSmoother {
  private:
   const FineOp<T>* op_ = nullptr;
   int V_ = 0, BS_ = 0, HS_ = 0, nblocks_ = 0, block_iter_ = 4;
+  int variant_ = 3;   // block-solver kernel (Knobs::sap_variant), fixed at setup
   enum Schedule { ADDITIVE, RED_BLACK, SIXTEEN, TWO_COLOR } schedule_ = RED_BLACK;
   std::vector<int> ncol_, ncol_interior_;          // blocks per colour; the first ncol_interior_[c] of them have no site next to another process
   int* d_blk_nb_ = nullptr;

@@ -656,9 +656,6 @@ __global__ __launch_bounds__((BS < 64 ? 64 : BS), (sizeof(T) == 4 ? 2 : 1)) void
 #undef DDAMG_EMIT
 #undef DDAMG_COLLECT
 
-static int g_sap_variant = -1;  // 1: site-pair kernel, 2: thread-per-site kernel with resident operator, 3 (default): two blocks per
-                                // workgroup + face buffers where the shape allows (fp32, 4^4 blocks), else 2
-
 template <typename T>
 SapSmoother<T>::~SapSmoother() {
   if (r) (void)hipFree(r);
@@ -677,8 +674,8 @@ SapSmoother<T>::~SapSmoother() {
 }
 
 template <typename T>
-void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, hipStream_t st, bool odd_even) {
-  odd_even_ = odd_even;
+void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, const Knobs& knobs, hipStream_t st, bool odd_even) {
+  odd_even_ = odd_even; variant_ = knobs.sap_variant;
   op_ = op; V_ = g.V; BS_ = g.block_sites; HS_ = g.block_sites / 2; nblocks_ = g.num_blocks; block_iter_ = block_iter;
   DDAMG_REQUIRE(method >= 1 && method <= 3, "Schwarz smoother: method must be 1 (additive), 2 (red-black) or 3 (sixteen colours)");
   DDAMG_REQUIRE(g.block_even_sites * 2 == g.block_sites, "Schwarz blocks need as many even as odd sites (even block extents)");
@@ -726,8 +723,7 @@ void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_ite
     DDAMG_HIP_CHECK(hipMemcpyAsync(d_color_blocks_[c], cb[c].data(), sizeof(int) * ncol_[c], hipMemcpyHostToDevice, st));
   }
   // production shape: paired-block kernel with face buffers (sap_pair.hip)
-  if (g_sap_variant < 0) { const char* e = getenv("DDAMG_SAP_VARIANT"); g_sap_variant = e ? atoi(e) : 3; }
-  pair_ = sizeof(T) == 4 && BS_ == 256 && schedule_ != ADDITIVE && g_sap_variant == 3 && odd_even_;
+  pair_ = sizeof(T) == 4 && BS_ == 256 && schedule_ != ADDITIVE && variant_ == 3 && odd_even_;
   for (int mu = 0; mu < 4 && pair_; mu++) if (g.B[mu] != 4) pair_ = false;
   if (pair_) {
     // rank of every block site among the sites of its parity class on its face, in transverse lexicographic order: the
@@ -771,11 +767,10 @@ void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_ite
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
 }
 
-static bool g_sap_plain = false;   // set per launch from the smoother: g.odd_even == 0
-
+// plain: MinRes on the whole block (g.odd_even == 0); variant: Knobs::sap_variant
 template <typename T, int HS>
-static void launch_hs(const SapArgs<T>& a, hipStream_t st) {
-  if (g_sap_plain) {
+static void launch_hs(const SapArgs<T>& a, bool plain, int variant, hipStream_t st) {
+  if (plain) {
     if constexpr (2 * HS <= 256) {
       constexpr int BS = 2 * HS;
       constexpr int NT = BS < 64 ? 64 : BS;
@@ -789,12 +784,11 @@ static void launch_hs(const SapArgs<T>& a, hipStream_t st) {
       DDAMG_REQUIRE(false, "Schwarz blocks of more than 256 sites need odd_even = 1");
     }
   }
-  if (g_sap_variant < 0) { const char* e = getenv("DDAMG_SAP_VARIANT"); g_sap_variant = e ? atoi(e) : 3; }
   // the resident-operator kernel addresses the operator through buffer descriptors (32-bit offsets, 2 GiB of records):
   // the largest field (72 reals per site) must stay below that, i.e. V < 7.4e6 sites in fp32 -- beyond it (e.g. 64^4 on
   // one GPU) the site-pair kernel with 64-bit addressing takes over
   const bool fits_descriptor = (size_t)a.s.op.V * 72 * sizeof(T) < ((size_t)1 << 31);
-  if (g_sap_variant == 1 || 2 * HS > 256 || !fits_descriptor) {
+  if (variant == 1 || 2 * HS > 256 || !fits_descriptor) {
     constexpr int NT = HS < 64 ? 64 : HS;
     constexpr int BPW = NT / HS;
     const int grid = (a.nblocks + BPW - 1) / BPW;
@@ -840,7 +834,6 @@ void SapSmoother<T>::launch(int color, int mode, unsigned skip_mask, const T* et
       return;
     }
   }
-  g_sap_plain = !odd_even_;
   SapArgs<T> a;
   a.s.op = op_->dev(); a.s.blk_nb = d_blk_nb_; a.s.block_list = d_block_list_;
   a.s.block_sites = BS_; a.s.half_sites = HS_; a.s.block_iter = block_iter_;
@@ -854,13 +847,13 @@ void SapSmoother<T>::launch(int color, int mode, unsigned skip_mask, const T* et
     if (n <= 0) return;
     a.blocks = blocks; a.nblocks = n;
     switch (HS_) {
-      case 8: launch_hs<T, 8>(a, st); break;
-      case 16: launch_hs<T, 16>(a, st); break;
-      case 32: launch_hs<T, 32>(a, st); break;
-      case 64: launch_hs<T, 64>(a, st); break;
-      case 128: launch_hs<T, 128>(a, st); break;
+      case 8: launch_hs<T, 8>(a, !odd_even_, variant_, st); break;
+      case 16: launch_hs<T, 16>(a, !odd_even_, variant_, st); break;
+      case 32: launch_hs<T, 32>(a, !odd_even_, variant_, st); break;
+      case 64: launch_hs<T, 64>(a, !odd_even_, variant_, st); break;
+      case 128: launch_hs<T, 128>(a, !odd_even_, variant_, st); break;
       case 256:
-        if constexpr (sizeof(T) == 4) { launch_hs<T, 256>(a, st); break; }
+        if constexpr (sizeof(T) == 4) { launch_hs<T, 256>(a, !odd_even_, variant_, st); break; }
         DDAMG_REQUIRE(false, "512-site Schwarz blocks are only supported in fp32 (LDS budget)");
         break;
       default: DDAMG_REQUIRE(false, "unsupported Schwarz block volume");

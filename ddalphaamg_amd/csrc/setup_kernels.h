@@ -41,7 +41,8 @@ void aggregate_dirac_slab(T* W, const ColumnView<T>& v, int chir, const FineOp<T
 // column in the layout of AggFaces (transfer.h) -- self part on all sites, then the forward part of direction mu on the sites
 // whose forward neighbour in mu lies in another aggregate.  2/5 of the bytes of the full form (4^4 aggregates).
 template <typename T>
-void aggregate_dirac_compact(T* W, const ColumnView<T>& v, int chir, const FineOp<T>& op, const unsigned char* d_agg_face, const AggFaces& af, int agg0, int naggs, hipStream_t st);
+void aggregate_dirac_compact(T* W, const ColumnView<T>& v, int chir, const FineOp<T>& op, const unsigned char* d_agg_face, const AggFaces& af, int agg0, int naggs, const Knobs& knobs,
+                             hipStream_t st);
 
 // column `col` of the five coarse matrices of every coarse site <- P^H W[part]
 template <typename T>

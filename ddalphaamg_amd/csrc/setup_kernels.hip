@@ -275,9 +275,10 @@ static void launch_aggregate_dirac_tile(T* W, const ColumnView<T>& v, int chir, 
 }
 
 template <typename T>
-void aggregate_dirac_compact(T* W, const ColumnView<T>& v, int chir, const FineOp<T>& op, const unsigned char* d_agg_face, const AggFaces& af, int agg0, int naggs, hipStream_t st) {
+void aggregate_dirac_compact(T* W, const ColumnView<T>& v, int chir, const FineOp<T>& op, const unsigned char* d_agg_face, const AggFaces& af, int agg0, int naggs, const Knobs& knobs,
+                             hipStream_t st) {
   const size_t site0 = (size_t)agg0 * af.agg_sites, nsites = (size_t)naggs * af.agg_sites;
-  const bool gather = getenv("DDAMG_AGGREGATE_DIRAC_GATHER") != nullptr;   // read at every call: tests switch it within one process
+  const bool gather = knobs.aggregate_dirac_gather;
   if (op.distributed()) {
     DDAMG_REQUIRE(agg0 == 0 && nsites == (size_t)op.V(), "Galerkin construction on a process grid: whole lattice only");
     // the self part of the column serves as scratch for the chirality-masked copy whose boundary is sent to the neighbours
@@ -291,8 +292,8 @@ void aggregate_dirac_compact(T* W, const ColumnView<T>& v, int chir, const FineO
   }
   DDAMG_HIP_CHECK(hipGetLastError());
 }
-template void aggregate_dirac_compact<float>(float*, const ColumnView<float>&, int, const FineOp<float>&, const unsigned char*, const AggFaces&, int, int, hipStream_t);
-template void aggregate_dirac_compact<double>(double*, const ColumnView<double>&, int, const FineOp<double>&, const unsigned char*, const AggFaces&, int, int, hipStream_t);
+template void aggregate_dirac_compact<float>(float*, const ColumnView<float>&, int, const FineOp<float>&, const unsigned char*, const AggFaces&, int, int, const Knobs&, hipStream_t);
+template void aggregate_dirac_compact<double>(double*, const ColumnView<double>&, int, const FineOp<double>&, const unsigned char*, const AggFaces&, int, int, const Knobs&, hipStream_t);
 
 // work: 5 coarse AoS vectors [part][Vc][n]; write column `col` of matrix `part` of every coarse site
 template <typename T>

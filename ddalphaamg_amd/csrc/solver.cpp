@@ -34,9 +34,9 @@ static void ensure_mg(ddamg_hip_ctx* c) {
   std::vector<const Geometry*> geoms;
   for (auto& lv : c->levels) geoms.push_back(&lv->geom);
   if (c->par.mixed_precision == 0) {
-    if (!c->mg64) { c->mg64.reset(new Multigrid<double>(c->par, geoms, &c->fop64, c->stream)); c->mg64->set_comm(c->comm); }
+    if (!c->mg64) { c->mg64.reset(new Multigrid<double>(c->par, c->knobs, geoms, &c->fop64, c->stream)); c->mg64->set_comm(c->comm); }
   } else {
-    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); }
+    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, c->knobs, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); }
   }
 }
 
@@ -46,6 +46,7 @@ static void ensure_outer(ddamg_hip_ctx* c) {
   c->rw_outer.init(c->par.restart + 4);
   // mixed precision 1 with a multigrid preconditioner: the iterates Z_j of the outer FGMRES stay in fp32, as the
   // V-cycle leaves them (Gmres::z_fp32)
+  c->outer.single_allreduce = c->knobs.single_allreduce_arnoldi;
   c->outer.z_fp32 = c->par.method >= 1 && c->par.method <= 4 && c->par.mixed_precision == 1;
   // pure CGN keeps its 8 vectors in a 4-vector Krylov structure, as the reference does (src/init.c:178-180)
   c->outer.alloc(n, c->par.method == -1 ? 4 : c->par.restart, c->par.method > 0);
@@ -186,6 +187,7 @@ static void ensure_mp(ddamg_hip_ctx* c) {
   if (c->mp_ready) return;
   const size_t n = (size_t)24 * c->levels[0]->geom.V;
   c->rw_mp.init(c->par.restart + 4);
+  c->mp_inner.single_allreduce = c->knobs.single_allreduce_arnoldi;
   c->mp_inner.alloc(n, c->par.restart, c->par.method > 0);
   c->mp_inner.num_restart = 1;
   c->mp_inner.view = whole(n);

@@ -45,7 +45,8 @@ struct Interpolation {
   T* tv = nullptr;         // test vectors   [nvec][24*V]
   T* P = nullptr;          // orthonormalised interpolation vectors, aggregate by aggregate: [aggregate][nvec][24 * plane_sites()]
   int* agg_csite = nullptr; // [num_aggs] coarse-level site index of every aggregate
-  void alloc(const Geometry& g, const Geometry& gc, int nvec_);
+  const Knobs* knobs = nullptr;   // the context's switches (alloc): gs_workgroup
+  void alloc(const Geometry& g, const Geometry& gc, int nvec_, const Knobs& knobs_);
   void release();
   T* test_vector(int j) const { return tv + pstride * j; }
   // column j of P from / into a vector in lattice order (import, export, the Galerkin construction's fall-back paths)

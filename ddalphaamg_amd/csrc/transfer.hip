@@ -25,8 +25,8 @@ static inline int wg_threads(int agg_sites) {
 template <typename T>
 __device__ __forceinline__ T* p_block(T* P, int a, int j, int nvec, int aps) { return P + ((size_t)a * nvec + j) * 24 * aps; }
 template <typename T>
-void Interpolation<T>::alloc(const Geometry& g, const Geometry& gc, int nvec_) {
-  V = g.V; nvec = nvec_; num_aggs = g.num_aggs; agg_sites = g.agg_sites;
+void Interpolation<T>::alloc(const Geometry& g, const Geometry& gc, int nvec_, const Knobs& knobs_) {
+  knobs = &knobs_; V = g.V; nvec = nvec_; num_aggs = g.num_aggs; agg_sites = g.agg_sites;
   DDAMG_REQUIRE(gc.V == g.num_aggs, "coarse lattice does not match the aggregate decomposition");
   // aggregate a (lexicographic in aggregate coordinates) is coarse lattice point with the same
   // coordinates; its index in the coarse level's own site ordering:
@@ -793,8 +793,7 @@ void Interpolation<T>::orthonormalize(hipStream_t st) {
   // two workgroups per CU; two columns reproduce the one-column results bit for bit, four do not: the compiler contracts
   // the products of the wider reduction differently)
   if constexpr (sizeof(T) == 4) {
-    const bool workgroup_form = getenv("DDAMG_GS_WORKGROUP") != nullptr;   // read at every call (tests)
-    if (agg_sites == 256 && !workgroup_form) {
+    if (agg_sites == 256 && !knobs->gs_workgroup) {
       hipLaunchKernelGGL(gs_aggregates_wave_kernel<3>, dim3((2 * num_aggs + 3) / 4), dim3(256), 0, st, P, tv, pstride, nvec, V, plane_sites(), 2 * num_aggs);
       DDAMG_HIP_CHECK(hipGetLastError());
       return;

@@ -346,33 +346,49 @@ def make_ctx_b4(gold_b4, gold8):
     return ctx
 
 
+def smoother_outputs_b4(ctx, g):
+    """the four smoother comparisons of the 4^4-block fixture: from zero with 1-3 cycles, and with an initial guess"""
+    eta = ctx.vector(0, 32).upload(g["smoother_eta"]); phi = ctx.vector(0, 32)
+    out = []
+    for c in (1, 2, 3):
+        ctx.smoother(phi, eta, c, initial_guess_zero=True)
+        out.append(phi.download())
+        assert relerr(out[-1], g[f"smoother_nores_out_c{c}"]) < TOL_SWEEP, c
+    phi.upload(g["smoother_phi0"])
+    ctx.smoother(phi, eta, 2, initial_guess_zero=False)
+    out.append(phi.download())
+    assert relerr(out[-1], g["smoother_res_out_c2"]) < TOL_SWEEP
+    eta.free(); phi.free()
+    return out
+
+
 @pytest.mark.parametrize("variant", ["2", "1"])
 def test_smoother_with_256_site_blocks_vs_reference(gold_b4, gold8, variant, monkeypatch):
     """red_black_schwarz on 4^4 blocks, both block-solver kernels (resident operator / site pairs), against the
     reference's dumps: from zero with 1-3 cycles (list-4/5 rule: with 2 blocks per direction every block touches both
     lattice boundaries) and with an initial guess"""
-    import subprocess, sys, os, textwrap
-    # the kernel variant is read once per process: run the comparison in a child with the variable set
-    code = textwrap.dedent(f"""
-        import sys, os, numpy as np
-        sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r}); sys.path.insert(0, {os.path.dirname(os.path.abspath(__file__))!r})
-        import test_gpu_multigrid as t
-        from conftest import load_golden, relerr
-        g = load_golden("ref_8x8_b4.npz"); g8 = load_golden("ref_8x8_dirac.npz")
-        ctx = t.make_ctx_b4(g, g8)
-        ctx.setup(0)
-        eta = ctx.vector(0, 32).upload(g["smoother_eta"]); phi = ctx.vector(0, 32)
-        for c in (1, 2, 3):
-            ctx.smoother(phi, eta, c, initial_guess_zero=True)
-            assert relerr(phi.download(), g[f"smoother_nores_out_c{{c}}"]) < t.TOL_SWEEP, c
-        phi.upload(g["smoother_phi0"])
-        ctx.smoother(phi, eta, 2, initial_guess_zero=False)
-        assert relerr(phi.download(), g["smoother_res_out_c2"]) < t.TOL_SWEEP
-        print("B4_SMOOTHER_OK")
-    """)
-    env = dict(os.environ, DDAMG_SAP_VARIANT=variant)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "B4_SMOOTHER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    monkeypatch.setenv("DDAMG_SAP_VARIANT", variant)     # a context's switches are the environment at its creation
+    ctx = make_ctx_b4(gold_b4, gold8)
+    ctx.setup(0)
+    smoother_outputs_b4(ctx, gold_b4)
+    ctx.close()
+
+
+def test_two_live_contexts_with_different_switches(gold_b4, gold8, monkeypatch):
+    """every context keeps the switches its own creation found in the environment: A under DDAMG_SAP_VARIANT=1 (site-pair
+    block solver), B without it (paired-block kernel with face buffers), both alive, smoothed in the order A, B, A.  All within
+    the tolerance of the reference's dumps; A gives the same bits both times; A and B differ -- two kernels did run"""
+    monkeypatch.setenv("DDAMG_SAP_VARIANT", "1")
+    A = make_ctx_b4(gold_b4, gold8); A.setup(0)
+    monkeypatch.delenv("DDAMG_SAP_VARIANT")
+    B = make_ctx_b4(gold_b4, gold8); B.setup(0)
+    a1 = smoother_outputs_b4(A, gold_b4)
+    b1 = smoother_outputs_b4(B, gold_b4)
+    a2 = smoother_outputs_b4(A, gold_b4)
+    A.close(); B.close()
+    for x, y, z in zip(a1, a2, b1):
+        assert np.array_equal(x, y)
+        assert not np.array_equal(x, z)
 
 
 def test_setup_and_solve_with_256_site_blocks_vs_reference(gold_b4, gold8):
@@ -640,27 +656,14 @@ def test_coarse_operator_single_read_form(gold4, monkeypatch):
     """CoarseOp::apply has two forms: small lattices read every link from both of its end points in one launch, large ones
     read it once (coarse_apply_once_kernel + finish).  The second form, forced here onto the golden lattices, must give the
     reference's coarse apply as well."""
-    monkeypatch.setenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES", "0")
-    import subprocess, sys, os, textwrap
-    # the threshold is read once per process: run the comparison in a child
-    name = "ref_4x4.npz" if volume(gold4) == 256 else "ref_ragged.npz"
-    code = textwrap.dedent(f'''
-        import sys, numpy as np
-        sys.path.insert(0, {os.path.dirname(os.path.abspath(__file__))!r}); sys.path.insert(0, {os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")!r})
-        from conftest import load_golden, relerr
-        import test_gpu_multigrid as t
-        g = load_golden({name!r})
-        ctx = t.make_ctx(g)
-        ctx.set_test_vectors(g["interp_vectors"], orthonormalised=True)
-        ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"])
-        vi = ctx.vector(1, 32).upload(g["coarse_apply_in"]); vo = ctx.vector(1, 32)
-        ctx.coarse_apply(vo, vi)
-        err = relerr(vo.download(), g["coarse_apply_out"])
-        print("ERR", err)
-        assert err < t.TOL_KERNEL, err
-    ''')
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ), timeout=300)
-    assert r.returncode == 0 and "ERR" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    monkeypatch.setenv("DDAMG_COARSE_APPLY_ONCE_MIN_SITES", "0")     # a context's switches are the environment at its creation
+    ctx = make_ctx(gold4)
+    ctx.set_test_vectors(gold4["interp_vectors"], orthonormalised=True)
+    ctx.set_coarse_operator(gold4["coarse_D"], gold4["coarse_clover"])
+    vi = ctx.vector(1, 32).upload(gold4["coarse_apply_in"]); vo = ctx.vector(1, 32)
+    ctx.coarse_apply(vo, vi)
+    assert relerr(vo.download(), gold4["coarse_apply_out"]) < TOL_KERNEL
+    ctx.close()
 
 
 def test_coarsest_solves_of_many_right_hand_sides_in_lockstep(gold_b4, gold8):

@@ -76,13 +76,22 @@ def test_second_coarse_operator_element_by_element(ref3):
 
 
 def test_second_coarse_operator_column_by_column_form(monkeypatch):
-    g, ctx = make_ctx("ref_16x8_3lvl_prod.npz")
-    monkeypatch.setenv("DDAMG_GALERKIN_UNBATCHED", "1")
-    ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"], level=1)
-    ctx.set_interpolation(g["l1_interp_vectors"], level=1)
-    D2, cl2 = ctx.get_coarse_operator(level=2)
-    assert maxerr(D2, g["l2_coarse_D"]) < 1e-5 and maxerr(cl2, g["l2_coarse_clover"]) < 1e-5
-    ctx.close()
+    """the level-2 Galerkin operator in its column-by-column form (DDAMG_GALERKIN_UNBATCHED: masked gather + restriction + one
+    store per column and part) and in the default matrix-core form, both from the reference's level-1 operator and
+    interpolation vectors, both against the reference's level-2 operator.  A context's switches are the environment at its
+    creation, so the variable is set before the context exists"""
+    res = []
+    for unbatched in (False, True):
+        if unbatched:
+            monkeypatch.setenv("DDAMG_GALERKIN_UNBATCHED", "1")
+        g, ctx = make_ctx("ref_16x8_3lvl_prod.npz")
+        ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"], level=1)
+        ctx.set_interpolation(g["l1_interp_vectors"], level=1)
+        D2, cl2 = ctx.get_coarse_operator(level=2)
+        assert maxerr(D2, g["l2_coarse_D"]) < 1e-5 and maxerr(cl2, g["l2_coarse_clover"]) < 1e-5, unbatched
+        res.append((D2, cl2))
+        ctx.close()
+    assert not np.array_equal(res[0][0], res[1][0])     # two code paths did run
 
 
 @pytest.mark.parametrize("name", ["ref_8x8_3lvl_small.npz", "ref_16x8_3lvl_prod.npz"])
