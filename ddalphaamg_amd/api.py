@@ -136,6 +136,7 @@ def load_library():
         "ddamg_hip_timer_begin": [vp],
         "ddamg_hip_timer_end": [vp, ctypes.POINTER(ctypes.c_float)],
         "ddamg_hip_sync": [vp],
+        "ddamg_hip_memory_in_use": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -143,6 +144,13 @@ def load_library():
         fn.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+def memory_in_use():
+    """(device bytes, pinned host bytes) the library's own buffers hold right now, over all contexts of this process"""
+    dev = ctypes.c_size_t(0); pin = ctypes.c_size_t(0)
+    load_library().ddamg_hip_memory_in_use(ctypes.byref(dev), ctypes.byref(pin))
+    return dev.value, pin.value
 
 
 class VectorHeader(ctypes.Structure):

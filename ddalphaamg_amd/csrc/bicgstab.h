@@ -21,7 +21,7 @@ struct OddEvenBicgstab {
   ReduceWork rw;
   View ev{1, 0, 0, 0};      // the even sites of a full-length fine vector (first half of every Schwarz block)
   size_t nel = 0;
-  T* buf[11] = {nullptr};
+  DeviceBuffer<T> buf[11];
   int last_iter = 0, total_iter = 0;
 
   void init(const Geometry& g, const FineOp<T>* op, hipStream_t stream) {
@@ -29,13 +29,9 @@ struct OddEvenBicgstab {
     DDAMG_REQUIRE(g.block_even_sites * 2 == g.block_sites, "odd-even BiCGstab needs as many even as odd sites per block");
     ev = View{(24 / Chunk<T>::CH) * g.num_blocks, (size_t)g.block_sites * Chunk<T>::CH, 0, (size_t)g.block_even_sites * Chunk<T>::CH};
     rw.init(8);
-    for (auto& p : buf) { DDAMG_HIP_CHECK(device_alloc(&p, sizeof(T) * nel)); DDAMG_HIP_CHECK(device_zero(p, sizeof(T) * nel)); }
+    for (auto& p : buf) { p.alloc(nel); DDAMG_HIP_CHECK(device_zero(p, sizeof(T) * nel)); }
   }
   void set_comm(Comm* c) { rw.comm = c; }
-  void release() {
-    for (auto& p : buf) if (p) { (void)hipFree(p); p = nullptr; }
-    if (rw.d_partial) rw.destroy();
-  }
 
   cd dot(const T* a, const T* b) {      // <a, b>, conjugate-linear in a (global_inner_product_PRECISION)
     vec_multi_dot<T>(a, 0, 1, b, ev, rw, rw.d_result, st);

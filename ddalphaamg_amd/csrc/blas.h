@@ -38,20 +38,19 @@ void comm_allreduce_end(Comm* c, double* d_buf, int n, hipStream_t st);
 
 struct ReduceWork {
   Comm* comm = nullptr;         // set on a process grid: every reduction below becomes a global one
-  double* d_partial = nullptr;  // [max_blocks][2*max_m]
-  double* d_result = nullptr;   // [2*max_m + 2]
-  double* h_result = nullptr;   // pinned mirror
-  double* d_coef = nullptr;     // [2*max_m] coefficients uploaded from the host
-  double* h_coef = nullptr;     // pinned
+  DeviceBuffer<double> d_partial;  // [max_blocks][2*max_m]
+  DeviceBuffer<double> d_result;   // [2*max_m + 2]
+  PinnedBuffer<double> h_result;   // pinned mirror
+  DeviceBuffer<double> d_coef;     // [2*max_m] coefficients uploaded from the host
+  PinnedBuffer<double> h_coef;     // pinned
   int max_m = 0, max_blocks = 0;
   // read-back without a copy engine in the way: the last kernel of a Krylov step writes its few numbers straight into
   // h_result (pinned, device-visible) and then a sequence number; the host spins on the sequence number.  A DMA copy plus
   // hipStreamSynchronize costs ~19 us per Arnoldi step, which is 7 % of a 32^4 solve (one step of the coarsest level is
   // ~150 us of kernels).
-  unsigned long long* h_seq = nullptr;   // pinned
+  PinnedBuffer<unsigned long long> h_seq;
   unsigned long long seq = 0;
   void init(int max_m_);
-  void destroy();
 };
 // h_result[0..n) <- d_src[0..n), visible to the host once wait_published returns (enqueued on st; n <= 2*max_m + 8)
 void publish_to_host(const double* d_src, int n, ReduceWork& rw, hipStream_t st);

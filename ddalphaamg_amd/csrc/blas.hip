@@ -16,22 +16,13 @@ static inline int grid_for(size_t nchunks) {
 
 void ReduceWork::init(int max_m_) {
   max_m = max_m_; max_blocks = MAX_GRID;
-  DDAMG_HIP_CHECK(device_alloc(&d_partial, sizeof(double) * (size_t)max_blocks * 2 * (max_m + 2)));
-  DDAMG_HIP_CHECK(device_alloc(&d_result, sizeof(double) * (2 * max_m + 8)));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_result, sizeof(double) * (2 * max_m + 8), hipHostMallocDefault));
-  DDAMG_HIP_CHECK(device_alloc(&d_coef, sizeof(double) * (2 * max_m + 8)));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_coef, sizeof(double) * (2 * max_m + 8), hipHostMallocDefault));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_seq, sizeof(unsigned long long), hipHostMallocDefault));
+  d_partial.alloc((size_t)max_blocks * 2 * (max_m + 2));
+  d_result.alloc(2 * max_m + 8);
+  h_result.alloc(2 * max_m + 8);
+  d_coef.alloc(2 * max_m + 8);
+  h_coef.alloc(2 * max_m + 8);
+  h_seq.alloc(1);
   *h_seq = 0; seq = 0;
-}
-void ReduceWork::destroy() {
-  if (d_partial) (void)hipFree(d_partial);
-  if (d_result) (void)hipFree(d_result);
-  if (h_result) (void)hipHostFree(h_result);
-  if (d_coef) (void)hipFree(d_coef);
-  if (h_coef) (void)hipHostFree(h_coef);
-  if (h_seq) (void)hipHostFree(h_seq);
-  d_partial = d_result = h_result = d_coef = h_coef = nullptr; h_seq = nullptr;
 }
 
 __global__ __launch_bounds__(64) void publish_kernel(const double* __restrict__ src, int n, double* __restrict__ hdst,

@@ -22,12 +22,15 @@ thread_local std::string g_ddamg_last_error;
   }                                                    \
   return 0;
 
+ddamg_hip_ctx::~ddamg_hip_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  mg32.reset(); mg64.reset();
+  if (comm) comm_destroy(comm);
+}
+
 double* ddamg_hip_ctx::stage(size_t bytes) {
-  if (bytes > stage_bytes) {
-    if (d_stage) DDAMG_HIP_CHECK(hipFree(d_stage));
-    DDAMG_HIP_CHECK(device_alloc(&d_stage, bytes));
-    stage_bytes = bytes;
-  }
+  if (bytes > d_stage.bytes()) d_stage.alloc(bytes / sizeof(double));   // every caller stages fp64 numbers
   return d_stage;
 }
 
@@ -115,7 +118,7 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
       }
     }
     lv->geom.build(p->local_lattice[d], B, A, c->par.process_grid, c->par.process_coords);
-    DDAMG_HIP_CHECK(device_alloc(&lv->d_lex_of_site, sizeof(int) * lv->geom.V));
+    lv->d_lex_of_site.alloc(lv->geom.V);
     DDAMG_HIP_CHECK(hipMemcpy(lv->d_lex_of_site, lv->geom.lex_of_site.data(), sizeof(int) * lv->geom.V, hipMemcpyHostToDevice));
     c->levels.push_back(std::move(lv));
   }
@@ -126,29 +129,18 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
 
 int ddamg_hip_destroy(ddamg_hip_ctx* c) {
   DDAMG_API_BEGIN
-  if (!c) return 0;
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  (void)hipStreamSynchronize(c->stream);
-  c->mg32.reset(); c->mg64.reset();
-  if (c->comm) { comm_destroy(c->comm); c->comm = nullptr; }
-  if (c->outer_ready) { c->outer.release(); c->rw_outer.destroy(); }
-  if (c->rw_blas_ready) c->rw_blas.destroy();
-  if (c->mp_ready) { c->mp_inner.release(); c->rw_mp.destroy(); (void)hipFree(c->mp_x); (void)hipFree(c->mp_b); (void)hipFree(c->mp_r); }
-  if (c->bicg_ready) { c->bicg32.release(); c->bicg64.release(); }
-  if (c->p32_in) (void)hipFree(c->p32_in);
-  if (c->p32_out) (void)hipFree(c->p32_out);
-  for (auto& lv : c->levels) if (lv->d_lex_of_site) (void)hipFree(lv->d_lex_of_site);
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  if (c->clover_base) (void)hipFree(c->clover_base);
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipStreamDestroy(c->stream);
   delete c;
   DDAMG_API_END
 }
 
+int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes) {
+  if (device_bytes) *device_bytes = DeviceMemory::in_use.load();
+  if (pinned_bytes) *pinned_bytes = PinnedMemory::in_use.load();
+  return 0;
+}
+
 static void drop_clover_base(ddamg_hip_ctx* c) {
-  if (c->clover_base) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->clover_base); c->clover_base = nullptr; }
+  if (c->clover_base) { (void)hipStreamSynchronize(c->stream); c->clover_base.reset(); }
   c->scale_even = c->scale_odd = 1.0;
 }
 
@@ -241,7 +233,7 @@ int ddamg_hip_scale_clover(ddamg_hip_ctx* c, double scale_even, double scale_odd
   if (scale_even == c->scale_even && scale_odd == c->scale_odd) return 0;
   const size_t bytes = sizeof(double) * 72 * (size_t)c->levels[0]->geom.V;
   if (!c->clover_base) {
-    DDAMG_HIP_CHECK(device_alloc(&c->clover_base, bytes));
+    c->clover_base.alloc(bytes / sizeof(double));
     DDAMG_HIP_CHECK(hipMemcpyAsync(c->clover_base, c->fop64.clover_field(), bytes, hipMemcpyDeviceToDevice, c->stream));
   }
   c->fop64.scale_clover(c->clover_base, scale_even, scale_odd, c->stream);
@@ -250,7 +242,7 @@ int ddamg_hip_scale_clover(ddamg_hip_ctx* c, double scale_even, double scale_odd
   if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
   if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (scale_even == 1.0 && scale_odd == 1.0) { (void)hipFree(c->clover_base); c->clover_base = nullptr; }
+  if (scale_even == 1.0 && scale_odd == 1.0) c->clover_base.reset();
   DDAMG_API_END
 }
 
@@ -340,9 +332,8 @@ int ddamg_hip_vec_create(ddamg_hip_ctx* c, int level, int precision, ddamg_hip_v
   v->ndof = c->levels[level]->ndof;
   v->V = c->levels[level]->geom.V;
   v->aos = level > 0 ? 1 : 0;
-  v->bytes = (size_t)v->V * v->ndof * 2 * (precision / 8);
-  DDAMG_HIP_CHECK(device_alloc(&v->data, v->bytes));
-  DDAMG_HIP_CHECK(hipMemsetAsync(v->data, 0, v->bytes, c->stream));
+  v->data.alloc((size_t)v->V * v->ndof * 2 * (precision / 8));
+  DDAMG_HIP_CHECK(hipMemsetAsync(v->data.get(), 0, v->data.bytes(), c->stream));
   *out = v.release();
   DDAMG_API_END
 }
@@ -352,7 +343,6 @@ int ddamg_hip_vec_destroy(ddamg_hip_ctx* c, ddamg_hip_vec* v) {
   if (!v) return 0;
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   (void)hipStreamSynchronize(c->stream);
-  if (v->data) (void)hipFree(v->data);
   delete v;
   DDAMG_API_END
 }
@@ -366,11 +356,11 @@ int ddamg_hip_vec_upload(ddamg_hip_ctx* c, ddamg_hip_vec* v, const double* host_
   DDAMG_HIP_CHECK(hipMemcpyAsync(st, host_lex, nb, hipMemcpyHostToDevice, c->stream));
   const int* tab = c->levels[v->level]->d_lex_of_site;
   if (v->aos) {
-    if (v->precision == 32) aos_from_lex<float>((float*)v->data, st, tab, v->V, v->ndof, c->stream);
-    else aos_from_lex<double>((double*)v->data, st, tab, v->V, v->ndof, c->stream);
+    if (v->precision == 32) aos_from_lex<float>((float*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
+    else aos_from_lex<double>((double*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
   } else {
-    if (v->precision == 32) vec_from_lex<float>((float*)v->data, st, tab, v->V, v->ndof, c->stream);
-    else vec_from_lex<double>((double*)v->data, st, tab, v->V, v->ndof, c->stream);
+    if (v->precision == 32) vec_from_lex<float>((float*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
+    else vec_from_lex<double>((double*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
@@ -384,11 +374,11 @@ int ddamg_hip_vec_download(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* hos
   double* st = c->stage(nb);
   const int* tab = c->levels[v->level]->d_lex_of_site;
   if (v->aos) {
-    if (v->precision == 32) aos_to_lex<float>(st, (const float*)v->data, tab, v->V, v->ndof, c->stream);
-    else aos_to_lex<double>(st, (const double*)v->data, tab, v->V, v->ndof, c->stream);
+    if (v->precision == 32) aos_to_lex<float>(st, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
+    else aos_to_lex<double>(st, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
   } else {
-    if (v->precision == 32) vec_to_lex<float>(st, (const float*)v->data, tab, v->V, v->ndof, c->stream);
-    else vec_to_lex<double>(st, (const double*)v->data, tab, v->V, v->ndof, c->stream);
+    if (v->precision == 32) vec_to_lex<float>(st, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
+    else vec_to_lex<double>(st, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
   }
   DDAMG_HIP_CHECK(hipMemcpyAsync(host_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -401,10 +391,10 @@ int ddamg_hip_dirac_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_
   DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
   DDAMG_REQUIRE(out->level == 0 && in->level == 0, "fine-level vectors expected");
   DDAMG_REQUIRE(out->precision == in->precision, "precision mismatch");
-  DDAMG_REQUIRE(out->data != in->data, "in-place apply is not supported");
+  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place apply is not supported");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (in->precision == 32) c->fop32.apply((float*)out->data, (const float*)in->data, c->stream);
-  else c->fop64.apply((double*)out->data, (const double*)in->data, c->stream);
+  if (in->precision == 32) c->fop32.apply((float*)out->data.get(), (const float*)in->data.get(), c->stream);
+  else c->fop64.apply((double*)out->data.get(), (const double*)in->data.get(), c->stream);
   DDAMG_API_END
 }
 

@@ -36,7 +36,6 @@ void batch_scale_inv(float2* out, const float2* w, const double* d_norm2, size_t
 
 class LockstepCoarseSolver {
  public:
-  ~LockstepCoarseSolver();
   static bool available(const CoarseOp<float>& cop, int ncols, bool odd_even);
   void init(const CoarseOp<float>* cop, int max_steps, double tol, hipStream_t st);
   void release();                            // the batches are setup workspace: freed with the Galerkin workspace after a setup
@@ -62,14 +61,14 @@ class LockstepCoarseSolver {
   int V_ = 0, Ve_ = 0, n_ = 0, max_steps_ = 0;
   double tol_ = 5e-2;
   hipStream_t st_ = nullptr;
-  float2* W_[4] = {nullptr, nullptr, nullptr, nullptr};   // x, b, two temporaries (whole lattice)
-  float2* basis_ = nullptr;                               // (max_steps + 1) even-site batches
-  float2* w_ = nullptr;                                   // even-site batch
-  double *d_partial_ = nullptr, *d_h_ = nullptr, *d_coef_ = nullptr;
-  double *h_h_ = nullptr, *h_coef_ = nullptr;             // pinned
+  DeviceBuffer<float2> W_[4];                             // x, b, two temporaries (whole lattice)
+  DeviceBuffer<float2> basis_;                            // (max_steps + 1) even-site batches
+  DeviceBuffer<float2> w_;                                // even-site batch
+  DeviceBuffer<double> d_partial_, d_h_, d_coef_;
+  PinnedBuffer<double> h_h_, h_coef_;
   // the couplings and the inverted self couplings in A-operand order (coarse_multi.h), refreshed when the operator has moved;
   // n % 8 == 0, else the kernels read the tile layout of the solve path
-  mutable float4 *Mop_ = nullptr, *Minv_op_ = nullptr;
+  mutable DeviceBuffer<float4> Mop_, Minv_op_;
   mutable unsigned Mop_version_ = 0, Minv_version_ = 0;
   mutable bool Mop_valid_ = false;
   bool operand_order() const;

@@ -254,32 +254,23 @@ bool LockstepCoarseSolver::available(const CoarseOp<float>& cop, int ncols, bool
   return odd_even && !cop.distributed() && ncols >= 2 && ncols <= NC && cop.n() <= 64 && cop.n() % 4 == 0 && cop.V() % 2 == 0;
 }
 
-LockstepCoarseSolver::~LockstepCoarseSolver() { release(); }
 void LockstepCoarseSolver::release() {
-  for (int i = 0; i < 4; i++) if (W_[i]) { (void)hipFree(W_[i]); W_[i] = nullptr; }
-  if (basis_) (void)hipFree(basis_);
-  if (w_) (void)hipFree(w_);
-  if (Mop_) (void)hipFree(Mop_);
-  if (Minv_op_) (void)hipFree(Minv_op_);
-  Mop_ = Minv_op_ = nullptr; Mop_valid_ = false;
-  if (d_partial_) (void)hipFree(d_partial_);
-  if (d_h_) (void)hipFree(d_h_);
-  if (d_coef_) (void)hipFree(d_coef_);
-  if (h_h_) (void)hipHostFree(h_h_);
-  if (h_coef_) (void)hipHostFree(h_coef_);
-  basis_ = nullptr; w_ = nullptr; d_partial_ = d_h_ = d_coef_ = h_h_ = h_coef_ = nullptr; cop_ = nullptr;
+  for (auto& w : W_) w.reset();
+  Mop_.reset(); Minv_op_.reset(); Mop_valid_ = false;
+  basis_.reset(); w_.reset(); d_partial_.reset(); d_h_.reset(); d_coef_.reset(); h_h_.reset(); h_coef_.reset();
+  cop_ = nullptr;
 }
 
 void LockstepCoarseSolver::init(const CoarseOp<float>* cop, int max_steps, double tol, hipStream_t st) {
   cop_ = cop; V_ = cop->V(); Ve_ = V_ / 2; n_ = cop->n(); max_steps_ = max_steps; tol_ = tol; st_ = st;
-  for (int i = 0; i < 4; i++) DDAMG_HIP_CHECK(device_alloc(&W_[i], sizeof(float2) * batch_elems()));
-  DDAMG_HIP_CHECK(device_alloc(&basis_, sizeof(float2) * even_elems() * (size_t)(max_steps_ + 1)));
-  DDAMG_HIP_CHECK(device_alloc(&w_, sizeof(float2) * even_elems()));
-  DDAMG_HIP_CHECK(device_alloc(&d_partial_, sizeof(double) * 2 * DOT_BLOCKS * DOT_CHUNK * NC));
-  DDAMG_HIP_CHECK(device_alloc(&d_h_, sizeof(double) * 2 * (max_steps_ + 2) * NC));
-  DDAMG_HIP_CHECK(device_alloc(&d_coef_, sizeof(double) * 2 * (max_steps_ + 2) * NC));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_h_, sizeof(double) * 2 * (max_steps_ + 2) * NC));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_coef_, sizeof(double) * 2 * (max_steps_ + 2) * NC));
+  for (int i = 0; i < 4; i++) W_[i].alloc(batch_elems());
+  basis_.alloc(even_elems() * (size_t)(max_steps_ + 1));
+  w_.alloc(even_elems());
+  d_partial_.alloc(2 * DOT_BLOCKS * DOT_CHUNK * NC);
+  d_h_.alloc(2 * (max_steps_ + 2) * NC);
+  d_coef_.alloc(2 * (max_steps_ + 2) * NC);
+  h_h_.alloc(2 * (max_steps_ + 2) * NC);
+  h_coef_.alloc(2 * (max_steps_ + 2) * NC);
 }
 
 void LockstepCoarseSolver::gather(float2* Wb, const float* src, size_t sstride, int ncols) { batch_gather(Wb, src, sstride, ncols, (size_t)V_ * n_, st_); }
@@ -288,8 +279,8 @@ bool LockstepCoarseSolver::operand_order() const { return n_ % 8 == 0; }
 void LockstepCoarseSolver::operands(const float4** Mop, const float4** Minv_op) const {
   const size_t me = mfma_op_matrix_elems(n_);
   if (!Mop_) {
-    DDAMG_HIP_CHECK(device_alloc(&Mop_, sizeof(float4) * (size_t)V_ * 9 * me));
-    DDAMG_HIP_CHECK(device_alloc(&Minv_op_, sizeof(float4) * (size_t)V_ * me));
+    Mop_.alloc((size_t)V_ * 9 * me);
+    Minv_op_.alloc((size_t)V_ * me);
   }
   if (!Mop_valid_ || Mop_version_ != cop_->version()) { coarse_operands_build(Mop_, *cop_, st_); Mop_version_ = cop_->version(); }
   if (!Mop_valid_ || Minv_version_ != cop_->inverse_version()) { coarse_inverse_operands_build(Minv_op_, *cop_, st_); Minv_version_ = cop_->inverse_version(); }
@@ -413,7 +404,7 @@ int LockstepCoarseSolver::solve_batch(float2* Xb, const float2* Bb, int ncols, i
   }
   // compute_solution_PRECISION (:943-982) per column; a column that is still open gets no update here (iters = -1)
   const int m = steps_taken;
-  std::fill(h_coef_, h_coef_ + (size_t)2 * NC * std::max(m, 1), 0.0);
+  std::fill(h_coef_.get(), h_coef_ + (size_t)2 * NC * std::max(m, 1), 0.0);
   int total = 0;
   for (int c = 0; c < ncols; c++) {
     Col& q = cols[c];

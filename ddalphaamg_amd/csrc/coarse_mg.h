@@ -17,12 +17,10 @@ template <typename T>
 struct CoarseTransfer {
   int V = 0, n = 0, nvec = 0, num_aggs = 0, agg_sites = 0;
   size_t pstride = 0;
-  T* tv = nullptr;
-  T* P = nullptr;
-  int* agg_csite = nullptr;
+  DeviceBuffer<T> tv, P;
+  DeviceBuffer<int> agg_csite;
   const Knobs* knobs = nullptr;   // the context's switches (alloc): coarse_gs_global, coarse_gs_workgroup_form
   void alloc(const Geometry& g, const Geometry& gc, int n_, int nvec_, const Knobs& knobs_);
-  void release();
   T* test_vector(int j) const { return tv + pstride * j; }
   T* interp_vector(int j) const { return P + pstride * j; }
   void orthonormalize(int passes, hipStream_t st);   // P <- tv; `passes` Gram-Schmidt sweeps (2 on depth > 0, src/setup_generic.c:291-292)
@@ -33,10 +31,9 @@ struct CoarseTransfer {
 template <typename T>
 class CoarseSap {
  public:
-  ~CoarseSap();
   void setup(const Geometry& g, const CoarseOp<T>* op, int block_iter, int method, hipStream_t st);
   void smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st);
-  T *r = nullptr, *latest = nullptr, *x = nullptr, *tmp = nullptr;
+  DeviceBuffer<T> r, latest, x, tmp;
 
  private:
   const CoarseOp<T>* op_ = nullptr;
@@ -44,8 +41,8 @@ class CoarseSap {
   enum Schedule { ADDITIVE, RED_BLACK, SIXTEEN, TWO_COLOR } schedule_ = RED_BLACK;
   int ncolors_ = 2;
   std::vector<int> nblk_;         // per colour (+ for red-black: colour 1 without the reference's lists 4 and 5)
-  std::vector<int*> d_blocks_, d_sites_;
-  unsigned char* d_blk_face_ = nullptr;
+  std::vector<DeviceBuffer<int>> d_blocks_, d_sites_;
+  DeviceBuffer<unsigned char> d_blk_face_;
   typename CoarseOp<T>::BlockPlan plan_;   // fused block solver (CoarseOp<T>::block_minres)
 };
 

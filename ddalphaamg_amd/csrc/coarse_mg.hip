@@ -35,19 +35,12 @@ void CoarseTransfer<T>::alloc(const Geometry& g, const Geometry& gc, int n_, int
   knobs = &knobs_; V = g.V; n = n_; nvec = nvec_; num_aggs = g.num_aggs; agg_sites = g.agg_sites;
   DDAMG_REQUIRE(gc.V == g.num_aggs, "coarse lattice does not match the aggregate decomposition");
   pstride = (size_t)V * n * 2;
-  DDAMG_HIP_CHECK(device_alloc(&agg_csite, sizeof(int) * num_aggs));
+  agg_csite.alloc(num_aggs);
   DDAMG_HIP_CHECK(hipMemcpy(agg_csite, gc.site_of_lex.data(), sizeof(int) * num_aggs, hipMemcpyHostToDevice));
-  DDAMG_HIP_CHECK(device_alloc(&tv, sizeof(T) * pstride * nvec));
-  DDAMG_HIP_CHECK(device_alloc(&P, sizeof(T) * pstride * nvec));
+  tv.alloc(pstride * nvec);
+  P.alloc(pstride * nvec);
   DDAMG_HIP_CHECK(device_zero(tv, sizeof(T) * pstride * nvec));
   DDAMG_HIP_CHECK(device_zero(P, sizeof(T) * pstride * nvec));
-}
-template <typename T>
-void CoarseTransfer<T>::release() {
-  if (tv) (void)hipFree(tv);
-  if (P) (void)hipFree(P);
-  if (agg_csite) (void)hipFree(agg_csite);
-  tv = P = nullptr; agg_csite = nullptr;
 }
 
 // phi_c[a][h*N + j] = sum over the aggregate's elements of chirality h of conj(P_j) phi
@@ -355,14 +348,6 @@ __global__ void block_minres_kernel(T* __restrict__ lphi, T* __restrict__ r, con
   }
 }
 
-template <typename T> CoarseSap<T>::~CoarseSap() {
-  for (T* p : {r, latest, x, tmp}) if (p) (void)hipFree(p);
-  for (int* p : d_blocks_) if (p) (void)hipFree(p);
-  for (int* p : d_sites_) if (p) (void)hipFree(p);
-  if (d_blk_face_) (void)hipFree(d_blk_face_);
-  CoarseOp<T>::free_block_plan(plan_);
-}
-
 template <typename T>
 void CoarseSap<T>::setup(const Geometry& g, const CoarseOp<T>* op, int block_iter, int method, hipStream_t st) {
   op_ = op; V_ = g.V; n_ = op->n(); BS_ = g.block_sites; block_iter_ = block_iter;
@@ -373,7 +358,7 @@ void CoarseSap<T>::setup(const Geometry& g, const CoarseOp<T>* op, int block_ite
   if (schedule_ != ADDITIVE)
     for (int mu = 0; mu < 4; mu++) DDAMG_REQUIRE((g.nblk[mu] * g.P[mu]) % 2 == 0, "multiplicative SAP needs an even number of blocks per direction of the global lattice");
   const size_t nel = (size_t)V_ * n_ * 2;
-  for (T** p : {&r, &latest, &x, &tmp}) { DDAMG_HIP_CHECK(device_alloc(p, sizeof(T) * nel)); DDAMG_HIP_CHECK(hipMemsetAsync(*p, 0, sizeof(T) * nel, st)); }
+  for (DeviceBuffer<T>* p : {&r, &latest, &x, &tmp}) { p->alloc(nel); DDAMG_HIP_CHECK(hipMemsetAsync(*p, 0, sizeof(T) * nel, st)); }
   // one list per colour; red-black keeps a second list of colour 1 without the reference's lists 4 and 5
   const int nlists = ncolors_ + (schedule_ == RED_BLACK ? 1 : 0);
   std::vector<std::vector<int>> bl(nlists), sl(nlists);
@@ -382,18 +367,17 @@ void CoarseSap<T>::setup(const Geometry& g, const CoarseOp<T>* op, int block_ite
     bl[c].push_back(b);
     if (schedule_ == RED_BLACK && c == 1 && g.block_list[b] != 4 && g.block_list[b] != 5) bl[2].push_back(b);
   }
-  nblk_.assign(nlists, 0); d_blocks_.assign(nlists, nullptr); d_sites_.assign(nlists, nullptr);
+  nblk_.assign(nlists, 0);
+  d_blocks_ = std::vector<DeviceBuffer<int>>(nlists); d_sites_ = std::vector<DeviceBuffer<int>>(nlists);
   for (int i = 0; i < nlists; i++) {
     for (int b : bl[i]) for (int k = 0; k < BS_; k++) sl[i].push_back(b * BS_ + k);
     nblk_[i] = (int)bl[i].size();
     if (nblk_[i] == 0) continue;
-    DDAMG_HIP_CHECK(device_alloc(&d_blocks_[i], sizeof(int) * bl[i].size()));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_blocks_[i], bl[i].data(), sizeof(int) * bl[i].size(), hipMemcpyHostToDevice, st));
-    DDAMG_HIP_CHECK(device_alloc(&d_sites_[i], sizeof(int) * sl[i].size()));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_sites_[i], sl[i].data(), sizeof(int) * sl[i].size(), hipMemcpyHostToDevice, st));
+    d_blocks_[i].upload(bl[i], st);
+    d_sites_[i].upload(sl[i], st);
   }
   for (int c = 0; c < ncolors_; c++) DDAMG_REQUIRE(nblk_[c] > 0, "SAP needs blocks of every colour");
-  DDAMG_HIP_CHECK(device_alloc(&d_blk_face_, V_));
+  d_blk_face_.alloc(V_);
   DDAMG_HIP_CHECK(hipMemcpyAsync(d_blk_face_, g.blk_face.data(), V_, hipMemcpyHostToDevice, st));
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
   plan_ = CoarseOp<T>::make_block_plan(g);

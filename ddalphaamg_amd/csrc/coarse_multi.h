@@ -33,7 +33,6 @@ void coarse_inverse_operands_build(float4* Minv_op, const CoarseOp<float>& op, h
 
 class CoarseMulti {
  public:
-  ~CoarseMulti();
   // true if the batched path covers this level: fp32 operator on one process, at most 16 sites per Schwarz block, dof counts the
   // matrix-core kernels tile (n % 8 == 0, n <= 64), a red-black colouring
   static bool available(const Geometry& g, const CoarseOp<float>& op, int method);
@@ -88,18 +87,19 @@ class CoarseMulti {
   hipStream_t st_ = nullptr;
   int V_ = 0, n_ = 0, BS_ = 0, block_iter_ = 4, Vc_ = 0, nc_ = 0;
   int nblk_[4] = {0, 0, 0, 0};            // colour 0, colour 1, colour 1 without the reference's lists 4 and 5, colour 1 in lists 4 and 5
-  int* d_blocks_[4] = {nullptr, nullptr, nullptr, nullptr};
-  short* d_blk_nb_ = nullptr;             // [8][BS] in-block neighbour or -1
-  float2 *r_ = nullptr, *latest_ = nullptr, *x_ = nullptr;   // smoother state (batches)
-  std::vector<float2*> work_, next_work_;
-  float2* kslab_ = nullptr;               // K-cycle: r, w, V[0..m], Z[0..m-1] in one slab
+  DeviceBuffer<int> d_blocks_[4];
+  DeviceBuffer<short> d_blk_nb_;          // [8][BS] in-block neighbour or -1
+  DeviceBuffer<float2> r_, latest_, x_;   // smoother state (batches)
+  std::vector<DeviceBuffer<float2>> work_, next_work_;
+  DeviceBuffer<float2> kslab_;            // K-cycle: r, w, V[0..m], Z[0..m-1] in one slab
   int kslab_m_ = 0;
-  mutable double* d_partial_ = nullptr;
-  double *d_h_ = nullptr, *d_coef_ = nullptr, *h_h_ = nullptr, *h_coef_ = nullptr;
+  mutable DeviceBuffer<double> d_partial_;
+  DeviceBuffer<double> d_h_, d_coef_;
+  PinnedBuffer<double> h_h_, h_coef_;
   int ld_h_ = 0;
   void block_solve(int list, int mode, const float2* eta);
   // the couplings in the A-operand order of the matrix instruction (mfma_tile.h), refreshed when the operator has changed
-  mutable float4* Mop_ = nullptr;
+  mutable DeviceBuffer<float4> Mop_;
   mutable unsigned Mop_version_ = 0;
   mutable bool Mop_valid_ = false;
   const float4* operands() const;

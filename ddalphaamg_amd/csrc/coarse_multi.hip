@@ -323,24 +323,14 @@ bool CoarseMulti::available(const Geometry& g, const CoarseOp<float>& op, int me
   return true;
 }
 
-CoarseMulti::~CoarseMulti() { release(); }
 void CoarseMulti::release() {
-  for (int i = 0; i < 4; i++) if (d_blocks_[i]) { (void)hipFree(d_blocks_[i]); d_blocks_[i] = nullptr; }
-  if (d_blk_nb_) (void)hipFree(d_blk_nb_);
-  for (float2* p : {r_, latest_, x_}) if (p) (void)hipFree(p);
-  for (float2* p : work_) if (p) (void)hipFree(p);
-  for (float2* p : next_work_) if (p) (void)hipFree(p);
+  for (auto& b : d_blocks_) b.reset();
   work_.clear(); next_work_.clear();
-  if (kslab_) (void)hipFree(kslab_);
-  kslab_ = nullptr; kslab_m_ = 0;
-  if (Mop_) (void)hipFree(Mop_);
-  Mop_ = nullptr; Mop_valid_ = false;
-  if (d_partial_) (void)hipFree(d_partial_);
-  if (d_h_) (void)hipFree(d_h_);
-  if (d_coef_) (void)hipFree(d_coef_);
-  if (h_h_) (void)hipHostFree(h_h_);
-  if (h_coef_) (void)hipHostFree(h_coef_);
-  d_blk_nb_ = nullptr; r_ = latest_ = x_ = nullptr; d_partial_ = d_h_ = d_coef_ = h_h_ = h_coef_ = nullptr; op_ = nullptr; ip_ = nullptr;
+  kslab_.reset(); kslab_m_ = 0;
+  Mop_.reset(); Mop_valid_ = false;
+  d_blk_nb_.reset(); r_.reset(); latest_.reset(); x_.reset();
+  d_partial_.reset(); d_h_.reset(); d_coef_.reset(); h_h_.reset(); h_coef_.reset();
+  op_ = nullptr; ip_ = nullptr;
 }
 
 void CoarseMulti::init(const Geometry& g, const CoarseOp<float>* op, const CoarseTransfer<float>* ip, int block_iter, hipStream_t st) {
@@ -357,20 +347,18 @@ void CoarseMulti::init(const Geometry& g, const CoarseOp<float>* op, const Coars
   for (int i = 0; i < 4; i++) {
     nblk_[i] = (int)bl[i].size();
     if (!nblk_[i]) continue;
-    DDAMG_HIP_CHECK(device_alloc(&d_blocks_[i], sizeof(int) * bl[i].size()));
-    DDAMG_HIP_CHECK(hipMemcpy(d_blocks_[i], bl[i].data(), sizeof(int) * bl[i].size(), hipMemcpyHostToDevice));
+    d_blocks_[i].upload(bl[i]);
   }
   std::vector<short> nb((size_t)8 * BS_);
   for (size_t i = 0; i < nb.size(); i++) nb[i] = (short)g.blk_nb[i];
-  DDAMG_HIP_CHECK(device_alloc(&d_blk_nb_, sizeof(short) * nb.size()));
-  DDAMG_HIP_CHECK(hipMemcpy(d_blk_nb_, nb.data(), sizeof(short) * nb.size(), hipMemcpyHostToDevice));
-  for (float2** p : {&r_, &latest_, &x_}) { DDAMG_HIP_CHECK(device_alloc(p, sizeof(float2) * batch_elems())); DDAMG_HIP_CHECK(hipMemsetAsync(*p, 0, sizeof(float2) * batch_elems(), st)); }
-  DDAMG_HIP_CHECK(device_alloc(&d_partial_, sizeof(double) * batch_dots_workspace()));
+  d_blk_nb_.upload(nb);
+  for (DeviceBuffer<float2>* p : {&r_, &latest_, &x_}) { p->alloc(batch_elems()); DDAMG_HIP_CHECK(hipMemsetAsync(*p, 0, sizeof(float2) * batch_elems(), st)); }
+  d_partial_.alloc(batch_dots_workspace());
   ld_h_ = 64;
-  DDAMG_HIP_CHECK(device_alloc(&d_h_, sizeof(double) * 2 * ld_h_ * NC));
-  DDAMG_HIP_CHECK(device_alloc(&d_coef_, sizeof(double) * 2 * ld_h_ * NC));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_h_, sizeof(double) * 2 * ld_h_ * NC));
-  DDAMG_HIP_CHECK(hipHostMalloc(&h_coef_, sizeof(double) * 2 * ld_h_ * NC));
+  d_h_.alloc(2 * ld_h_ * NC);
+  d_coef_.alloc(2 * ld_h_ * NC);
+  h_h_.alloc(2 * ld_h_ * NC);
+  h_coef_.alloc(2 * ld_h_ * NC);
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
 }
 
@@ -381,13 +369,13 @@ size_t CoarseMulti::workspace_bytes(const Geometry& g, int n, int restart_length
 }
 
 float2* CoarseMulti::work(int i) {
-  if ((int)work_.size() <= i) work_.resize(i + 1, nullptr);
-  if (!work_[i]) DDAMG_HIP_CHECK(device_alloc(&work_[i], sizeof(float2) * batch_elems()));
+  if ((int)work_.size() <= i) work_.resize(i + 1);
+  if (!work_[i]) work_[i].alloc(batch_elems());
   return work_[i];
 }
 float2* CoarseMulti::next_work(int i) {
-  if ((int)next_work_.size() <= i) next_work_.resize(i + 1, nullptr);
-  if (!next_work_[i]) DDAMG_HIP_CHECK(device_alloc(&next_work_[i], sizeof(float2) * next_batch_elems()));
+  if ((int)next_work_.size() <= i) next_work_.resize(i + 1);
+  if (!next_work_[i]) next_work_[i].alloc(next_batch_elems());
   return next_work_[i];
 }
 
@@ -397,7 +385,7 @@ float2* CoarseMulti::next_work(int i) {
 // the copy of the couplings in A-operand order follows the operator: refreshed when CoarseOp::version() has moved
 const float4* CoarseMulti::operands() const {
   const size_t elems = (size_t)V_ * 9 * mfma_op_matrix_elems(n_);
-  if (!Mop_) DDAMG_HIP_CHECK(device_alloc(&Mop_, sizeof(float4) * elems));
+  if (!Mop_) Mop_.alloc(elems);
   if (Mop_version_ != op_->version() || !Mop_valid_) {
     hipLaunchKernelGGL(cm_relayout_kernel, dim3(V_, 9), dim3(256), 0, st_, Mop_, op_->dev(), (n_ + 15) / 16, 0);
     DDAMG_HIP_CHECK(hipGetLastError());
@@ -460,13 +448,13 @@ void CoarseMulti::smooth(float2* phi, const float2* eta, int cycles, int res) {
 
 void CoarseMulti::restrict_to(float2* phi_c, const float2* phi) const {
   DDAMG_REQUIRE(ip_ != nullptr, "batched restriction: no transfer operator on this level");
-  hipLaunchKernelGGL(cm_restrict_kernel, dim3(ip_->num_aggs), dim3(256), 0, st_, phi_c, phi, reinterpret_cast<const float2*>(ip_->P), ip_->pstride / 2, ip_->nvec, n_,
+  hipLaunchKernelGGL(cm_restrict_kernel, dim3(ip_->num_aggs), dim3(256), 0, st_, phi_c, phi, reinterpret_cast<const float2*>(ip_->P.get()), ip_->pstride / 2, ip_->nvec, n_,
                      ip_->agg_sites, ip_->agg_csite);
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 void CoarseMulti::interpolate(float2* phi, const float2* phi_c, bool add) const {
   DDAMG_REQUIRE(ip_ != nullptr, "batched interpolation: no transfer operator on this level");
-  const float2* P = reinterpret_cast<const float2*>(ip_->P);
+  const float2* P = reinterpret_cast<const float2*>(ip_->P.get());
   const size_t ps2 = ip_->pstride / 2;
   if (n_ / 2 <= 16) hipLaunchKernelGGL((cm_interpolate_kernel<1>), dim3(V_), dim3(256), 0, st_, phi, phi_c, P, ps2, ip_->nvec, n_, ip_->agg_sites, ip_->agg_csite, add ? 1 : 0);
   else hipLaunchKernelGGL((cm_interpolate_kernel<2>), dim3(V_), dim3(256), 0, st_, phi, phi_c, P, ps2, ip_->nvec, n_, ip_->agg_sites, ip_->agg_csite, add ? 1 : 0);
@@ -507,8 +495,7 @@ int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles
   DDAMG_REQUIRE(ready() && ncols <= NC && m + 2 <= ld_h_, "lockstep K-cycle: not set up, or restart length too large");
   const size_t el = batch_elems(), bytes = sizeof(float2) * el;
   if (!kslab_ || kslab_m_ < m) {
-    if (kslab_) DDAMG_HIP_CHECK(hipFree(kslab_));
-    DDAMG_HIP_CHECK(device_alloc(&kslab_, bytes * (size_t)(2 * m + 3)));
+    kslab_.alloc(el * (size_t)(2 * m + 3));
     kslab_m_ = m;
   }
   float2 *r = kslab_, *w = kslab_ + el, *Vb = kslab_ + 2 * el, *Zb = Vb + (size_t)(m + 1) * el;
@@ -582,7 +569,7 @@ int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles
     }
     // compute_solution_PRECISION per column: x += sum_{i <= j} y_i Z_i
     if (steps > 0) {
-      std::fill(h_coef_, h_coef_ + (size_t)2 * NC * steps, 0.0);
+      std::fill(h_coef_.get(), h_coef_ + (size_t)2 * NC * steps, 0.0);
       for (int c = 0; c < ncols; c++) {
         Col& q = cols[c];
         if (q.j < 0) continue;

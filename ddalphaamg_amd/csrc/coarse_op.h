@@ -40,7 +40,6 @@ struct CoarseOpDev {
 template <typename T>
 class CoarseOp {
  public:
-  ~CoarseOp();
   void alloc(const Geometry& g, int n, const Knobs& knobs);
   // import from the reference's storage (lexicographic coarse sites):
   //   D_ref [V][4][n*n] complex: blocks A,C,B,D each (n/2)^2 column-major (src/coarse_operator_generic.h:124-143)
@@ -91,9 +90,8 @@ class CoarseOp {
   // then latest = lphi, x += lphi.  One workgroup per block keeps r and lphi in LDS and streams every coupling of the
   // block ONCE per step (a link serves both of its end points).  plan: see make_block_plan.  Returns false when the
   // block does not fit the kernel's LDS / register budget (the caller then runs the step-by-step path).
-  struct BlockPlan { int* d_items = nullptr; int* d_contrib = nullptr; int nitems = 0, block_sites = 0; };
+  struct BlockPlan { DeviceBuffer<int> d_items, d_contrib; int nitems = 0, block_sites = 0; };
   static BlockPlan make_block_plan(const Geometry& g);
-  static void free_block_plan(BlockPlan& p);
   bool block_minres(T* x, T* r, T* latest, const int* blocks, int nblocks, const BlockPlan& plan, int iters, double eps, hipStream_t st) const;
   // out[s0,s1) = M0 in   or   M0^-1 in
   void self_mul(T* out, const T* in, int s0, int s1, bool inverse, hipStream_t st) const;
@@ -101,14 +99,13 @@ class CoarseOp {
   void self_mul_list(T* out, const T* in, const int* site_list, int nsites, bool inverse, hipStream_t st) const;
 
  private:
-  T* M_ = nullptr;
-  T* Minv_ = nullptr;
-  mutable T* bwd_ = nullptr;   // [4][V][n] backward products of apply()'s first phase
-  int* nb_ = nullptr;
+  DeviceBuffer<T> M_, Minv_;
+  mutable DeviceBuffer<T> bwd_;   // [4][V][n] backward products of apply()'s first phase
+  DeviceBuffer<int> nb_;
   int V_ = 0, n_ = 0, nt_ = 0;
   unsigned version_ = 0;
   unsigned inverse_version_ = 0;
-  T* diag_base_ = nullptr;          // [V][n] the self couplings' diagonal (real parts) before any shift
+  DeviceBuffer<T> diag_base_;       // [V][n] the self couplings' diagonal (real parts) before any shift
   unsigned diag_base_version_ = 0;  // version_ the base belongs to (0: none)
   double shift_total_ = 0.0;
   size_t msize_ = 0;
@@ -122,8 +119,8 @@ class CoarseOp {
   // the interior work (the reference's ghost_sendrecv ... interior hopping terms ... ghost_wait, src/coarse_oddeven_generic.c:
   // 447-581); the sites whose FORWARD neighbour is on another process and the directions concerned
   std::vector<int> h_interior_, h_boundary_;
-  int *d_interior_ = nullptr, *d_boundary_ = nullptr, *d_fwd_off_sites_ = nullptr;
-  unsigned char* d_fwd_off_mask_ = nullptr;
+  DeviceBuffer<int> d_interior_, d_boundary_, d_fwd_off_sites_;
+  DeviceBuffer<unsigned char> d_fwd_off_mask_;
   int n_fwd_off_ = 0;
   void pack_and_begin(const T* in, hipStream_t st) const;
 };

@@ -407,17 +407,9 @@ typename CoarseOp<T>::BlockPlan CoarseOp<T>::make_block_plan(const Geometry& g) 
     for (size_t q = 0; q < slots_of[i].size(); q++) contrib[(size_t)i * 10 + 1 + q] = slots_of[i][q];
   }
   p.nitems = (int)(items.size() / 3); p.block_sites = BS;
-  DDAMG_HIP_CHECK(device_alloc(&p.d_items, sizeof(int) * items.size()));
-  DDAMG_HIP_CHECK(hipMemcpy(p.d_items, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
-  DDAMG_HIP_CHECK(device_alloc(&p.d_contrib, sizeof(int) * contrib.size()));
-  DDAMG_HIP_CHECK(hipMemcpy(p.d_contrib, contrib.data(), sizeof(int) * contrib.size(), hipMemcpyHostToDevice));
+  p.d_items.upload(items);
+  p.d_contrib.upload(contrib);
   return p;
-}
-template <typename T>
-void CoarseOp<T>::free_block_plan(BlockPlan& p) {
-  if (p.d_items) (void)hipFree(p.d_items);
-  if (p.d_contrib) (void)hipFree(p.d_contrib);
-  p = BlockPlan();
 }
 
 template <typename T>
@@ -558,7 +550,7 @@ template <typename T> void CoarseOp<T>::apply(T* out, const T* in, hipStream_t s
     }
     return;
   }
-  if (!bwd_) DDAMG_HIP_CHECK(device_alloc(&bwd_, sizeof(T) * 4 * (size_t)V_ * n_ * 2));
+  if (!bwd_) bwd_.alloc(4 * (size_t)V_ * n_ * 2);
   const CoarseOpDev<T> op = dev();
 #define DDAMG_CASE(NTV) case NTV: if (dist) hipLaunchKernelGGL((coarse_apply_once_kernel<T, NTV, true>), dim3(V_), dim3(320), 0, st, out, bwd_, in, op); \
                                   else hipLaunchKernelGGL((coarse_apply_once_kernel<T, NTV, false>), dim3(V_), dim3(320), 0, st, out, bwd_, in, op); break;
@@ -684,7 +676,7 @@ template <typename T>
 void CoarseOp<T>::shift_diagonal(double diff, hipStream_t st) {
   const size_t tot = (size_t)V_ * n_;
   const bool capture = diag_base_ == nullptr || diag_base_version_ != version_;    // the couplings were rewritten since the last shift
-  if (!diag_base_) DDAMG_HIP_CHECK(device_alloc(&diag_base_, sizeof(T) * tot));
+  if (!diag_base_) diag_base_.alloc(tot);
   if (capture) shift_total_ = 0.0;
   shift_total_ += diff;
   hipLaunchKernelGGL(shift_self_diagonal_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, M_, diag_base_, V_, n_, nt_, msize_, (T)shift_total_, capture ? 1 : 0);
@@ -694,27 +686,16 @@ void CoarseOp<T>::shift_diagonal(double diff, hipStream_t st) {
 }
 
 // ---- allocation / import / export ---------------------------------------------------------------
-template <typename T> CoarseOp<T>::~CoarseOp() {
-  if (M_) (void)hipFree(M_);
-  if (Minv_) (void)hipFree(Minv_);
-  if (bwd_) (void)hipFree(bwd_);
-  if (diag_base_) (void)hipFree(diag_base_);
-  if (nb_) (void)hipFree(nb_);
-  if (d_interior_) (void)hipFree(d_interior_);
-  if (d_boundary_) (void)hipFree(d_boundary_);
-  if (d_fwd_off_sites_) (void)hipFree(d_fwd_off_sites_);
-  if (d_fwd_off_mask_) (void)hipFree(d_fwd_off_mask_);
-}
 template <typename T>
 void CoarseOp<T>::alloc(const Geometry& g, int n, const Knobs& knobs) {
   geom_ = &g; knobs_ = &knobs;
   V_ = g.V; n_ = n; nt_ = (n + 7) / 8; msize_ = (size_t)nt_ * nt_ * 64;
   DDAMG_REQUIRE(n % 2 == 0 && nt_ <= 8, "coarse dof per site must be even and at most 64");
-  DDAMG_HIP_CHECK(device_alloc(&M_, sizeof(T) * 2 * msize_ * 5 * V_));
-  DDAMG_HIP_CHECK(device_alloc(&Minv_, sizeof(T) * 2 * msize_ * V_));
+  M_.alloc(2 * msize_ * 5 * V_);
+  Minv_.alloc(2 * msize_ * V_);
   DDAMG_HIP_CHECK(device_zero(M_, sizeof(T) * 2 * msize_ * 5 * V_));
   DDAMG_HIP_CHECK(device_zero(Minv_, sizeof(T) * 2 * msize_ * V_));
-  DDAMG_HIP_CHECK(device_alloc(&nb_, sizeof(int) * 8 * V_));
+  nb_.alloc((size_t)8 * V_);
   DDAMG_HIP_CHECK(hipMemcpy(nb_, g.nb.data(), sizeof(int) * 8 * V_, hipMemcpyHostToDevice));
   if (g.distributed()) {
     arena_.init(g, sizeof(T) * 2 * n);
@@ -726,15 +707,11 @@ void CoarseOp<T>::alloc(const Geometry& g, int n, const Knobs& knobs) {
       (off ? h_boundary_ : h_interior_).push_back(s);
       if (mask[s]) fwd.push_back(s);
     }
-    auto up = [](int** d, const std::vector<int>& h) {
-      if (h.empty()) return;
-      DDAMG_HIP_CHECK(device_alloc(d, sizeof(int) * h.size()));
-      DDAMG_HIP_CHECK(hipMemcpy(*d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
-    };
-    up(&d_interior_, h_interior_); up(&d_boundary_, h_boundary_); up(&d_fwd_off_sites_, fwd);
+    if (!h_interior_.empty()) d_interior_.upload(h_interior_);
+    if (!h_boundary_.empty()) d_boundary_.upload(h_boundary_);
+    if (!fwd.empty()) d_fwd_off_sites_.upload(fwd);
     n_fwd_off_ = (int)fwd.size();
-    DDAMG_HIP_CHECK(device_alloc(&d_fwd_off_mask_, V_));
-    DDAMG_HIP_CHECK(hipMemcpy(d_fwd_off_mask_, mask.data(), V_, hipMemcpyHostToDevice));
+    d_fwd_off_mask_.upload(mask);
   }
 }
 

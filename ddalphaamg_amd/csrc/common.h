@@ -36,29 +36,9 @@
     }                                                                                          \
   } while (0)
 
+#include "device_buffer.h"   // DeviceBuffer / PinnedBuffer, device_alloc, device_zero: needs the macros above
+
 namespace ddamg {
-
-// Every device allocation of the library goes through here.  DDAMG_POISON=1 fills fresh allocations with 0xFF bytes
-// (NaN as float/double, -1 as int): a read of memory the library has not written itself then poisons the result
-// instead of going unnoticed (device memory handed out by the driver is usually zero, sometimes recycled).
-template <typename P>
-inline hipError_t device_alloc(P** p, size_t bytes) {
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
-  if (e == hipSuccess && poison_allocations() && bytes) {
-    e = hipMemset(*p, 0xFF, bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // the library's streams do not synchronise with the null stream
-  }
-  return e;
-}
-
-// zero-fill at allocation time.  hipMemset runs on the null stream, which the library's non-blocking streams do NOT
-// wait for: without the synchronisation a long fill (a Krylov slab of many GB) overlaps with the first kernels that
-// write into the same memory and wipes their results.
-inline hipError_t device_zero(void* p, size_t bytes) {
-  hipError_t e = hipMemset(p, 0, bytes);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  return e;
-}
 
 // Streams confined to a subset of the compute units, used on a process grid: the transport stream gets n CUs of its own
 // and the compute stream the rest, so that the transport's copy kernels do not wait for CU slots behind the kernels they

@@ -17,8 +17,7 @@ struct ddamg_hip_vec {
   int ndof = 12;
   int V = 0;
   int aos = 0;  // 0: chunked SoA (fine level), 1: site-major AoS (coarse levels)
-  void* data = nullptr;
-  size_t bytes = 0;
+  ddamg::DeviceBuffer<char> data;
 };
 
 namespace ddamg {
@@ -27,32 +26,42 @@ struct Level {
   int depth = 0;
   int ndof = 12;  // complex dof per site
   Geometry geom;
-  int* d_lex_of_site = nullptr;
+  DeviceBuffer<int> d_lex_of_site;
 };
 
 }  // namespace ddamg
 
-struct ddamg_hip_ctx {
+// the stream and the timer events: a base, so that they are destroyed after every member of the context that may still use them
+struct ddamg_hip_ctx_handles {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~ddamg_hip_ctx_handles() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   explicit ddamg_hip_ctx(const ddamg::Knobs& k) : knobs(k) {}
+  // selects the device, waits for the stream, then drops the hierarchies and the transport before the operators they point into;
+  // the remaining members free themselves in reverse order of declaration, the stream and the events go last
+  ~ddamg_hip_ctx();
   const ddamg::Knobs knobs;   // the DDAMG_* switches as the environment held them at ddamg_hip_create (knobs.h)
   ddamg_hip_params par;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<std::unique_ptr<ddamg::Level>> levels;
   // fine operator in the reference's host storage (fp64) + device copies in both precisions
   std::vector<double> D_host, clover_host;
   bool have_operator = false;
   // scale_clover: unscaled fp64 copy of the clover field on the device while the operator is scaled (ddamg_hip_scale_clover)
-  double* clover_base = nullptr;
+  ddamg::DeviceBuffer<double> clover_base;
   double scale_even = 1.0, scale_odd = 1.0;
   ddamg::FineOp<float> fop32;
   ddamg::FineOp<double> fop64;
   ddamg::Comm* comm = nullptr;  // halo transport of a decomposed lattice (halo.h)
   // staging buffer for host<->device vector transfers (lexicographic fp64)
-  double* d_stage = nullptr;
-  size_t stage_bytes = 0;
-
+  ddamg::DeviceBuffer<double> d_stage;
   double* stage(size_t bytes);
 
   // multigrid preconditioner (V-cycle precision float when mixed_precision >= 1, double otherwise)
@@ -65,12 +74,12 @@ struct ddamg_hip_ctx {
   bool outer_ready = false;
   ddamg::ReduceWork rw_blas;
   bool rw_blas_ready = false;
-  float *p32_in = nullptr, *p32_out = nullptr;
+  ddamg::DeviceBuffer<float> p32_in, p32_out;
   // fgmres_MP (mixed_precision 2): fp32 Krylov basis, fp64 residual/solution (src/linsolve.c:153-424)
   ddamg::Gmres<float> mp_inner;
   ddamg::ReduceWork rw_mp;
   bool mp_ready = false;
-  double *mp_x = nullptr, *mp_b = nullptr, *mp_r = nullptr;
+  ddamg::DeviceBuffer<double> mp_x, mp_b, mp_r;
   // method 5: FGMRES preconditioned by BiCGstab on the odd-even Schur complement of the fine operator, no multigrid
   ddamg::OddEvenBicgstab<float> bicg32;
   ddamg::OddEvenBicgstab<double> bicg64;

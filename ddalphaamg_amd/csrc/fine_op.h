@@ -46,9 +46,6 @@ template <typename T>
 class FineOp {
  public:
   FineOp() = default;
-  ~FineOp();
-  FineOp(const FineOp&) = delete;
-  FineOp& operator=(const FineOp&) = delete;
 
   // D_ref: [V][4][9] complex (lexicographic sites), clover_ref: [V][42] complex, both fp64 as the
   // reference holds them in g.op_double (src/dirac.c:60-168)
@@ -90,19 +87,17 @@ class FineOp {
   void parity_select(T* out, const T* a, const T* b, int keep, hipStream_t st) const;
 
  private:
-  T* D_ = nullptr;
-  T* clover_ = nullptr;
-  T* clover_inv_ = nullptr;
-  int* nb_ = nullptr;
-  int* lex_ = nullptr;      // lexicographic index of every device site (for the layout kernel)
-  unsigned char* parity_ = nullptr;   // [V] global parity of every site
-  int* tile_nb_ = nullptr;
-  T* Dc_ = nullptr;            // two-row links (operators whose links are +-1/2 SU(3) only)
-  T* Dc_store_ = nullptr;
-  signed char* Dsgn_ = nullptr;
-  T* Cc_ = nullptr;            // 56-real clover (fp32 operators whose clover blocks have the chiral structure)
-  T* Cc_store_ = nullptr;
-  unsigned short* tnb_ = nullptr;
+  DeviceBuffer<T> D_, clover_, clover_inv_;
+  DeviceBuffer<int> nb_;
+  DeviceBuffer<int> lex_;      // lexicographic index of every device site (for the layout kernel)
+  DeviceBuffer<unsigned char> parity_;   // [V] global parity of every site
+  DeviceBuffer<int> tile_nb_;
+  T* Dc_ = nullptr;            // two-row links (operators whose links are +-1/2 SU(3) only): Dc_store_ or null
+  DeviceBuffer<T> Dc_store_;
+  DeviceBuffer<signed char> Dsgn_;
+  T* Cc_ = nullptr;            // 56-real clover (fp32 operators whose clover blocks have the chiral structure): Cc_store_ or null
+  DeviceBuffer<T> Cc_store_;
+  DeviceBuffer<unsigned short> tnb_;
   int V_ = 0;
   mutable Halo<T> halo_;
   Comm* comm_ = nullptr;

@@ -350,21 +350,6 @@ void FineOp<T>::halo_exchange(const T* v, hipStream_t st) const {
   halo_finish(st);
 }
 
-template <typename T>
-FineOp<T>::~FineOp() {
-  if (D_) (void)hipFree(D_);
-  if (clover_) (void)hipFree(clover_);
-  if (clover_inv_) (void)hipFree(clover_inv_);
-  if (nb_) (void)hipFree(nb_);
-  if (tile_nb_) (void)hipFree(tile_nb_);
-  if (tnb_) (void)hipFree(tnb_);
-  if (lex_) (void)hipFree(lex_);
-  if (parity_) (void)hipFree(parity_);
-  if (Dc_store_) (void)hipFree(Dc_store_);
-  if (Dsgn_) (void)hipFree(Dsgn_);
-  if (Cc_store_) (void)hipFree(Cc_store_);
-}
-
 // ---- operator data: reference storage (lexicographic fp64) -> device layouts, on the device -----------------------
 // One thread per site: links into the chunked-SoA rows, both Hermitian 6x6 clover blocks into the packed form (real
 // diagonal + strict upper triangle) and their inverses (Gauss-Jordan with partial pivoting in fp64, as the host code
@@ -687,20 +672,19 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   const size_t V = g.V;
   V_ = g.V;
   if (!D_) {
-    DDAMG_HIP_CHECK(device_alloc(&D_, sizeof(T) * 72 * V));
-    DDAMG_HIP_CHECK(device_alloc(&clover_, sizeof(T) * 72 * V));
-    DDAMG_HIP_CHECK(device_alloc(&clover_inv_, sizeof(T) * 72 * V));
-    DDAMG_HIP_CHECK(device_alloc(&nb_, sizeof(int) * 8 * V));
-    DDAMG_HIP_CHECK(device_alloc(&lex_, sizeof(int) * V));
+    D_.alloc(72 * V);
+    clover_.alloc(72 * V);
+    clover_inv_.alloc(72 * V);
+    nb_.alloc(8 * V);
+    lex_.alloc(V);
     DDAMG_HIP_CHECK(hipMemcpyAsync(lex_, g.lex_of_site.data(), sizeof(int) * V, hipMemcpyHostToDevice, st));
     std::vector<unsigned char> par(V);
     for (size_t i = 0; i < V; i++) par[i] = (unsigned char)g.parity[i];
-    DDAMG_HIP_CHECK(device_alloc(&parity_, V));
-    DDAMG_HIP_CHECK(hipMemcpy(parity_, par.data(), V, hipMemcpyHostToDevice));
+    parity_.upload(par);
   }
-  double *dD = nullptr, *dC = nullptr;   // staging of the lexicographic fp64 arrays
-  DDAMG_HIP_CHECK(device_alloc(&dD, sizeof(double) * 72 * V));
-  DDAMG_HIP_CHECK(device_alloc(&dC, sizeof(double) * 84 * V));
+  DeviceBuffer<double> dD, dC;   // staging of the lexicographic fp64 arrays
+  dD.alloc(72 * V);
+  dC.alloc(84 * V);
   DDAMG_HIP_CHECK(hipMemcpyAsync(dD, D_ref, sizeof(double) * 72 * V, hipMemcpyHostToDevice, st));
   DDAMG_HIP_CHECK(hipMemcpyAsync(dC, clover_ref, sizeof(double) * 84 * V, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(operator_layout_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, D_, clover_, clover_inv_, dD, dC, lex_, (int)V);
@@ -710,10 +694,10 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   {
     if (knobs.link_compression && g.block_sites == 256) {
       if (!Dc_store_) {
-        DDAMG_HIP_CHECK(device_alloc(&Dc_store_, sizeof(T) * 48 * V));
-        DDAMG_HIP_CHECK(device_alloc(&Dsgn_, 4 * V + sizeof(int)));
+        Dc_store_.alloc(48 * V);
+        Dsgn_.alloc(4 * V, sizeof(int));
       }
-      int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(Dsgn_) + 4 * V);   // one flag behind the signs
+      int* d_bad = reinterpret_cast<int*>(Dsgn_ + 4 * V);   // one flag behind the signs
       DDAMG_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), st));
       hipLaunchKernelGGL(link_compress_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, Dc_store_, Dsgn_, d_bad, dD, lex_, (int)V);
       DDAMG_HIP_CHECK(hipGetLastError());
@@ -727,7 +711,7 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   Cc_ = nullptr;
   if constexpr (sizeof(T) == 4) {
     if (knobs.clover_compression) {
-      if (!Cc_store_) DDAMG_HIP_CHECK(device_alloc(&Cc_store_, sizeof(T) * 56 * V + sizeof(int)));
+      if (!Cc_store_) Cc_store_.alloc(56 * V, sizeof(int));
       int* d_bad = reinterpret_cast<int*>(Cc_store_ + 56 * V);   // one flag behind the field
       DDAMG_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), st));
       hipLaunchKernelGGL(clover_compress_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, Cc_store_, d_bad, dC, lex_, (int)V);
@@ -740,14 +724,13 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
   }
   DDAMG_HIP_CHECK(hipMemcpyAsync(nb_, g.nb.data(), sizeof(int) * 8 * V, hipMemcpyHostToDevice, st));
   if (g.block_sites == 256 && !tnb_) {   // one tile of the LDS kernel == one Schwarz block: arithmetic neighbours
-    DDAMG_HIP_CHECK(device_alloc(&tile_nb_, sizeof(int) * 8 * g.num_blocks));
-    DDAMG_HIP_CHECK(device_alloc(&tnb_, sizeof(unsigned short) * 8 * 256));
+    tile_nb_.alloc(8 * g.num_blocks);
+    tnb_.alloc(8 * 256);
     DDAMG_HIP_CHECK(hipMemcpyAsync(tile_nb_, g.block_nb.data(), sizeof(int) * 8 * g.num_blocks, hipMemcpyHostToDevice, st));
     DDAMG_HIP_CHECK(hipMemcpyAsync(tnb_, g.blk_wrap_nb.data(), sizeof(unsigned short) * 8 * 256, hipMemcpyHostToDevice, st));
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
-  DDAMG_HIP_CHECK(hipFree(dD));
-  DDAMG_HIP_CHECK(hipFree(dC));
+  dD.reset(); dC.reset();   // before the halo buffers are allocated
   if (g.distributed() && !halo_.active()) halo_.init(g);
 }
 

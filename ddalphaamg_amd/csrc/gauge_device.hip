@@ -145,16 +145,15 @@ static GammaProducts gamma_products() {
 // `ext` on the device
 static double clover_and_plaquette_on_device(const double* dU, const Lat& ext, const Lat& loc, const Lat& halo, double m0, double csw, double* clover_out, hipStream_t st) {
   const size_t V = (size_t)loc.L[0] * loc.L[1] * loc.L[2] * loc.L[3];
-  double *dC = nullptr, *dP = nullptr;
-  DDAMG_HIP_CHECK(device_alloc(&dC, sizeof(double) * 84 * V));
-  DDAMG_HIP_CHECK(device_alloc(&dP, sizeof(double) * V));
+  DeviceBuffer<double> dC, dP;
+  dC.alloc(84 * V);
+  dP.alloc(V);
   hipLaunchKernelGGL(clover_kernel, dim3((unsigned)((V + 63) / 64)), dim3(64), 0, st, dC, dP, dU, ext, loc, halo, (int)V, m0, csw, gamma_products());
   DDAMG_HIP_CHECK(hipGetLastError());
   std::vector<double> hp(V);
   DDAMG_HIP_CHECK(hipMemcpyAsync(clover_out, dC, sizeof(double) * 84 * V, hipMemcpyDeviceToHost, st));
   DDAMG_HIP_CHECK(hipMemcpyAsync(hp.data(), dP, sizeof(double) * V, hipMemcpyDeviceToHost, st));
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
-  DDAMG_HIP_CHECK(hipFree(dC)); DDAMG_HIP_CHECK(hipFree(dP));
   double plaq = 0;
   for (size_t i = 0; i < V; i++) plaq += hp[i];
   return plaq;
@@ -164,9 +163,9 @@ static double clover_and_plaquette_on_device(const double* dU, const Lat& ext, c
 double gauge_to_operator_device(const int L[4], const double* gauge_in, int anti_pbc, double m0, double csw, double* D_out, double* clover_out,
                                 hipStream_t st) {
   const size_t V = (size_t)L[0] * L[1] * L[2] * L[3];
-  double *dU = nullptr, *dD = nullptr;
-  DDAMG_HIP_CHECK(device_alloc(&dU, sizeof(double) * 72 * V));
-  DDAMG_HIP_CHECK(device_alloc(&dD, sizeof(double) * 72 * V));
+  DeviceBuffer<double> dU, dD;
+  dU.alloc(72 * V);
+  dD.alloc(72 * V);
   DDAMG_HIP_CHECK(hipMemcpyAsync(dU, gauge_in, sizeof(double) * 72 * V, hipMemcpyHostToDevice, st));
   const size_t vol3 = (size_t)L[1] * L[2] * L[3];
   hipLaunchKernelGGL(scale_links_kernel, dim3((unsigned)((72 * V + 255) / 256)), dim3(256), 0, st, dD, dU, 72 * V, anti_pbc,
@@ -174,18 +173,16 @@ double gauge_to_operator_device(const int L[4], const double* gauge_in, int anti
   DDAMG_HIP_CHECK(hipMemcpyAsync(D_out, dD, sizeof(double) * 72 * V, hipMemcpyDeviceToHost, st));
   Lat g, none; for (int mu = 0; mu < 4; mu++) { g.L[mu] = L[mu]; none.L[mu] = 0; }
   const double plaq = clover_and_plaquette_on_device(dU, g, g, none, m0, csw, clover_out, st);
-  DDAMG_HIP_CHECK(hipFree(dU)); DDAMG_HIP_CHECK(hipFree(dD));
   return plaq / ((double)V * 6.0);
 }
 
 double clover_and_plaquette_extended_device(const int L[4], const int halo[4], const double* U_ext_host, double m0, double csw, double* clover_out, hipStream_t st) {
   Lat ext, loc, h; size_t Ve = 1;
   for (int mu = 0; mu < 4; mu++) { loc.L[mu] = L[mu]; h.L[mu] = halo[mu]; ext.L[mu] = L[mu] + 2 * halo[mu]; Ve *= ext.L[mu]; }
-  double* dU = nullptr;
-  DDAMG_HIP_CHECK(device_alloc(&dU, sizeof(double) * 72 * Ve));
+  DeviceBuffer<double> dU;
+  dU.alloc(72 * Ve);
   DDAMG_HIP_CHECK(hipMemcpyAsync(dU, U_ext_host, sizeof(double) * 72 * Ve, hipMemcpyHostToDevice, st));
   const double plaq = clover_and_plaquette_on_device(dU, ext, loc, h, m0, csw, clover_out, st);
-  DDAMG_HIP_CHECK(hipFree(dU));
   return plaq;
 }
 

@@ -43,7 +43,7 @@ int comm_size(const Comm* c);
 // send / receive arenas of the 8 face messages of one field type and their exchange (any payload)
 class HaloArena {
  public:
-  ~HaloArena();
+  ~HaloArena();   // the two events
   void init(const Geometry& g, size_t bytes_per_face_site);
   bool active() const { return total_sites_ > 0; }
   int total_sites() const { return total_sites_; }
@@ -62,15 +62,15 @@ class HaloArena {
   size_t bpfs_ = 0;
   int F_[4] = {0, 0, 0, 0}, soff_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nbr_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int total_sites_ = 0;
-  int* d_face_sites_ = nullptr;  // [total_sites] concatenated face_sites[d] in arena order
-  char *send_ = nullptr, *recv_ = nullptr, *h_send_ = nullptr, *h_recv_ = nullptr;
+  DeviceBuffer<int> d_face_sites_;  // [total_sites] concatenated face_sites[d] in arena order
+  DeviceBuffer<char> send_, recv_;
+  PinnedBuffer<char> h_send_, h_recv_;   // host transport only
   hipEvent_t ev_packed_ = nullptr, ev_done_ = nullptr;
 };
 
 template <typename T>
 class Halo {
  public:
-  ~Halo();
   void init(const Geometry& g);
   bool active() const { return arena_.active(); }
   const HaloDev& dev() const { return hd_; }
@@ -88,7 +88,7 @@ class Halo {
  private:
   HaloDev hd_{};
   HaloArena arena_;
-  int* d_interior_ = nullptr; int* d_boundary_ = nullptr;
+  DeviceBuffer<int> d_interior_, d_boundary_;
   int n_interior_ = 0, n_boundary_ = 0;
 };
 

@@ -34,10 +34,8 @@ struct Comm {
   hipStream_t stream_red = nullptr;
   hipEvent_t ev_ra = nullptr, ev_rb = nullptr;
   bool red_tried = false;
-  double* h_red = nullptr;                      // pinned staging for the host transport's reductions
-  int h_red_n = 0;
-  char* h_gather = nullptr;                     // pinned staging for the host transport's all-gather
-  size_t h_gather_bytes = 0;
+  PinnedBuffer<double> h_red;                   // staging for the host transport's reductions
+  PinnedBuffer<char> h_gather;                  // staging for the host transport's all-gather
   // what travelled since the last reset (ddamg_hip_comm_stats): halo exchanges by payload (bytes per face site), reductions
   // and all-gathers with the time their collective kernels took on the transport stream (RCCL: event pairs around the call,
   // read when the pair comes round again or at the report)
@@ -112,11 +110,7 @@ void comm_allgather(Comm* c, const void* d_send, void* d_recv, size_t bytes, hip
   // host transport: staged, one message to and from every other process
   c->allgather_stats.calls++; c->allgather_stats.bytes += bytes;
   const size_t total = bytes * (size_t)c->nranks;
-  if (total > c->h_gather_bytes) {
-    if (c->h_gather) DDAMG_HIP_CHECK(hipHostFree(c->h_gather));
-    DDAMG_HIP_CHECK(hipHostMalloc(&c->h_gather, total));
-    c->h_gather_bytes = total;
-  }
+  if (total > c->h_gather.bytes()) c->h_gather.alloc(total);
   char* mine = c->h_gather + bytes * (size_t)c->rank;
   DDAMG_HIP_CHECK(hipMemcpyAsync(mine, d_send, bytes, hipMemcpyDeviceToHost, st));
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
@@ -142,11 +136,7 @@ void comm_allreduce(Comm* c, double* d_buf, int n, hipStream_t st) {
   } else {
     DDAMG_REQUIRE(c->reduce_fn != nullptr, "host transport without an allreduce callback");
     c->allreduce_stats.calls++; c->allreduce_stats.bytes += sizeof(double) * (size_t)n;
-    if (n > c->h_red_n) {
-      if (c->h_red) DDAMG_HIP_CHECK(hipHostFree(c->h_red));
-      DDAMG_HIP_CHECK(hipHostMalloc(&c->h_red, sizeof(double) * n));
-      c->h_red_n = n;
-    }
+    if ((size_t)n > c->h_red.size()) c->h_red.alloc(n);
     DDAMG_HIP_CHECK(hipMemcpyAsync(c->h_red, d_buf, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     DDAMG_HIP_CHECK(hipStreamSynchronize(st));
     c->reduce_fn(c->user, c->h_red, n);
@@ -203,9 +193,9 @@ void comm_sendrecv_host(Comm* c, const void* send, int send_peer, void* recv, in
     c->fn(c->user, 1, &m);
     return;
   }
-  char *ds = nullptr, *dr = nullptr;   // RCCL moves device memory: stage
-  DDAMG_HIP_CHECK(device_alloc(&ds, bytes));
-  DDAMG_HIP_CHECK(device_alloc(&dr, bytes));
+  DeviceBuffer<char> ds, dr;   // RCCL moves device memory: stage
+  ds.alloc(bytes);
+  dr.alloc(bytes);
   DDAMG_HIP_CHECK(hipMemcpyAsync(ds, send, bytes, hipMemcpyHostToDevice, c->stream));
   DDAMG_NCCL_CHECK(ncclGroupStart());
   DDAMG_NCCL_CHECK(ncclSend(ds, bytes, ncclChar, send_peer, c->nccl, c->stream));
@@ -213,8 +203,6 @@ void comm_sendrecv_host(Comm* c, const void* send, int send_peer, void* recv, in
   DDAMG_NCCL_CHECK(ncclGroupEnd());
   DDAMG_HIP_CHECK(hipMemcpyAsync(recv, dr, bytes, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  DDAMG_HIP_CHECK(hipFree(ds));
-  DDAMG_HIP_CHECK(hipFree(dr));
 }
 
 void comm_allreduce_host(Comm* c, double* buf, int n) {
@@ -224,13 +212,12 @@ void comm_allreduce_host(Comm* c, double* buf, int n) {
     c->reduce_fn(c->user, buf, n);
     return;
   }
-  double* d = nullptr;
-  DDAMG_HIP_CHECK(device_alloc(&d, sizeof(double) * n));
+  DeviceBuffer<double> d;
+  d.alloc(n);
   DDAMG_HIP_CHECK(hipMemcpyAsync(d, buf, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   DDAMG_NCCL_CHECK(ncclAllReduce(d, d, (size_t)n, ncclDouble, ncclSum, c->nccl, c->stream));
   DDAMG_HIP_CHECK(hipMemcpyAsync(buf, d, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  DDAMG_HIP_CHECK(hipFree(d));
 }
 
 void rccl_unique_id(void* id128) {
@@ -272,8 +259,6 @@ void comm_destroy(Comm* c) {
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->ev_a) (void)hipEventDestroy(c->ev_a);
   if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-  if (c->h_red) (void)hipHostFree(c->h_red);
-  if (c->h_gather) (void)hipHostFree(c->h_gather);
   c->allreduce_stats.destroy(); c->allgather_stats.destroy();
   delete c;
 }
@@ -346,22 +331,16 @@ void HaloArena::init(const Geometry& g, size_t bytes_per_face_site) {
   }
   if (total_sites_ == 0) return;
   for (int s : fs) DDAMG_REQUIRE(s >= 0 && s < g.V, "face table holds an invalid site");
-  DDAMG_HIP_CHECK(device_alloc(&d_face_sites_, sizeof(int) * total_sites_));
-  DDAMG_HIP_CHECK(hipMemcpy(d_face_sites_, fs.data(), sizeof(int) * total_sites_, hipMemcpyHostToDevice));
+  d_face_sites_.upload(fs);
   const size_t bytes = bpfs_ * (size_t)total_sites_;
-  DDAMG_HIP_CHECK(device_alloc(&send_, bytes));
-  DDAMG_HIP_CHECK(device_alloc(&recv_, bytes));
+  send_.alloc(bytes);
+  recv_.alloc(bytes);
   DDAMG_HIP_CHECK(device_zero(recv_, bytes));
   DDAMG_HIP_CHECK(hipEventCreateWithFlags(&ev_packed_, hipEventDisableTiming));
   DDAMG_HIP_CHECK(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
 }
 
 HaloArena::~HaloArena() {
-  if (d_face_sites_) (void)hipFree(d_face_sites_);
-  if (send_) (void)hipFree(send_);
-  if (recv_) (void)hipFree(recv_);
-  if (h_send_) (void)hipHostFree(h_send_);
-  if (h_recv_) (void)hipHostFree(h_recv_);
   if (ev_packed_) (void)hipEventDestroy(ev_packed_);
   if (ev_done_) (void)hipEventDestroy(ev_done_);
 }
@@ -394,8 +373,8 @@ void HaloArena::exchange_begin(Comm* c, hipStream_t st) {
     DDAMG_HIP_CHECK(hipEventRecord(ev_done_, c->stream));
   } else {
     if (!h_send_) {
-      DDAMG_HIP_CHECK(hipHostMalloc(&h_send_, bytes));
-      DDAMG_HIP_CHECK(hipHostMalloc(&h_recv_, bytes));
+      h_send_.alloc(bytes);
+      h_recv_.alloc(bytes);
     }
     DDAMG_HIP_CHECK(hipMemcpyAsync(h_send_, send_, bytes, hipMemcpyDeviceToHost, c->stream));
   }
@@ -431,19 +410,11 @@ void Halo<T>::init(const Geometry& g) {
   n_interior_ = (int)g.interior_tiles.size();
   n_boundary_ = (int)g.boundary_tiles.size();
   if (n_interior_) {
-    DDAMG_HIP_CHECK(device_alloc(&d_interior_, sizeof(int) * n_interior_));
-    DDAMG_HIP_CHECK(hipMemcpy(d_interior_, g.interior_tiles.data(), sizeof(int) * n_interior_, hipMemcpyHostToDevice));
+    d_interior_.upload(g.interior_tiles);
   }
   if (n_boundary_) {
-    DDAMG_HIP_CHECK(device_alloc(&d_boundary_, sizeof(int) * n_boundary_));
-    DDAMG_HIP_CHECK(hipMemcpy(d_boundary_, g.boundary_tiles.data(), sizeof(int) * n_boundary_, hipMemcpyHostToDevice));
+    d_boundary_.upload(g.boundary_tiles);
   }
-}
-
-template <typename T>
-Halo<T>::~Halo() {
-  if (d_interior_) (void)hipFree(d_interior_);
-  if (d_boundary_) (void)hipFree(d_boundary_);
 }
 
 template <typename T>

@@ -96,7 +96,7 @@ struct Knobs {
 // pure Krylov methods) reserve 24, multigrid contexts none; DDAMG_COMM_CUS overrides both (the measurements: common.h)
 inline int comm_cus_for(const Knobs& knobs, int num_levels) { return knobs.comm_cus.set ? knobs.comm_cus.value : (num_levels <= 1 ? 24 : 0); }
 
-// DDAMG_POISON: fill fresh device allocations with 0xFF bytes (device_alloc, common.h).  Per process, not per context.
+// DDAMG_POISON: fill fresh device allocations with 0xFF bytes (device_alloc, device_buffer.h).  Per process, not per context.
 inline bool poison_allocations() {
   static const bool on = getenv("DDAMG_POISON") != nullptr;
   return on;

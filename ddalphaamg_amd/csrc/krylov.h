@@ -50,13 +50,13 @@ struct Gmres {
   // the basis' memory and traffic go.  prec32 writes Z_j in fp32, op32 applies the fp64 operator to it (conversion in its
   // loads), the solution update reads the fp32 vectors with fp64 arithmetic.  Set by the owner before alloc (z_fp32) / solve.
   bool z_fp32 = false;
-  float* Zb32 = nullptr;
+  DeviceBuffer<float> Zb32;
   std::function<void(float* z, const T* v, int res)> prec32;
   std::function<void(T* out, const float* z)> op32;
   size_t sites32 = 0; int nreal32 = 0;      // shape of the vectors (fp32 and fp64 chunk layouts differ)
   float* Z32(int i) const { return Zb32 + vstride * i; }
   // storage (owned)
-  T* slab = nullptr;
+  DeviceBuffer<T> slab;
   T *x = nullptr, *b = nullptr, *r = nullptr, *w = nullptr, *Vb = nullptr, *Zb = nullptr;
   size_t vstride = 0;
   // results
@@ -71,20 +71,19 @@ struct Gmres {
     vstride = (vec_elems + 63) / 64 * 64;
     const bool z64 = with_Z && !z_fp32;
     size_t nvec = 4 + (restart_length + 1) + (z64 ? restart_length + 2 : 0);
-    DDAMG_HIP_CHECK(device_alloc(&slab, sizeof(T) * vstride * nvec));
+    slab.alloc(vstride * nvec);
     DDAMG_HIP_CHECK(device_zero(slab, sizeof(T) * vstride * nvec));
     x = slab; b = x + vstride; r = b + vstride; w = r + vstride;
     Vb = w + vstride;
     Zb = z64 ? Vb + vstride * (restart_length + 1) : nullptr;
     if (with_Z && z_fp32) {
-      DDAMG_HIP_CHECK(device_alloc(&Zb32, sizeof(float) * vstride * (restart_length + 2)));
+      Zb32.alloc(vstride * (restart_length + 2));
       DDAMG_HIP_CHECK(device_zero(Zb32, sizeof(float) * vstride * (restart_length + 2)));
     }
     H.assign((size_t)(restart_length + 1) * (restart_length + 2), cd(0));
     y.assign(restart_length + 2, cd(0)); gamma.assign(restart_length + 2, cd(0));
     c.assign(restart_length + 2, cd(0)); s.assign(restart_length + 2, cd(0));
   }
-  void release() { if (slab) (void)hipFree(slab); slab = nullptr; if (Zb32) (void)hipFree(Zb32); Zb32 = nullptr; }
   T* V(int i) const { return Vb + vstride * i; }
   T* Z(int i) const { return Zb + vstride * i; }
 

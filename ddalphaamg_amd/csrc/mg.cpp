@@ -31,14 +31,14 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
   for (int d = 0; d < L; d++) {
     MGLevel<T>& lv = *lv_[d];
     const Geometry& g = *lv.g;
-    for (int i = 0; i < 4; i++) { DDAMG_HIP_CHECK(device_alloc(&lv.buf[i], sizeof(T) * lv.nel)); DDAMG_HIP_CHECK(device_zero(lv.buf[i], sizeof(T) * lv.nel)); }
+    for (int i = 0; i < 4; i++) { lv.buf[i].alloc(lv.nel); DDAMG_HIP_CHECK(device_zero(lv.buf[i], sizeof(T) * lv.nel)); }
     if (d == 0) lv.fop = fop;
     else lv.cop.alloc(g, lv.n, knobs_);
     if (!lv.coarsest) {
       if (par.method == 4) {
         // smoother = GMRES on the odd-even Schur complement of this level (schwarz_PRECISION_alloc, src/schwarz_generic.c:78-83:
         // restart length block_iter, tolerance EPS_PRECISION, no preconditioner; the V-cycle sets the number of restarts)
-        for (int i = 0; i < 3; i++) { DDAMG_HIP_CHECK(device_alloc(&lv.sbuf[i], sizeof(T) * lv.nel)); DDAMG_HIP_CHECK(device_zero(lv.sbuf[i], sizeof(T) * lv.nel)); }
+        for (int i = 0; i < 3; i++) { lv.sbuf[i].alloc(lv.nel); DDAMG_HIP_CHECK(device_zero(lv.sbuf[i], sizeof(T) * lv.nel)); }
         lv.srw.init(par.block_iter[d] + 8);
         lv.sgm.single_allreduce = knobs_.single_allreduce_arnoldi;
         lv.sgm.alloc(lv.nel, par.block_iter[d], false);
@@ -56,14 +56,13 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
           for (int s = 0; s < g.V; s++) ps[g.parity[s]].push_back(s);
           for (int q = 0; q < 2; q++) {
             lv.n_parity_sites[q] = (int)ps[q].size();
-            DDAMG_HIP_CHECK(device_alloc(&lv.d_parity_sites[q], sizeof(int) * ps[q].size()));
-            DDAMG_HIP_CHECK(hipMemcpy(lv.d_parity_sites[q], ps[q].data(), sizeof(int) * ps[q].size(), hipMemcpyHostToDevice));
+            lv.d_parity_sites[q].upload(ps[q]);
           }
         }
       }
       if (d == 0) { if (par.method != 4) lv.fsap.setup(g, fop, par.block_iter[0], par.method, knobs_, st_, par.odd_even != 0); lv.fip.alloc(g, *geoms[1], lv.nvec, knobs_); }
       else { if (par.method != 4) lv.csap.setup(g, &lv.cop, par.block_iter[d], par.method, st_); lv.cip.alloc(g, *geoms[d + 1], lv.n, lv.nvec, knobs_); }
-      DDAMG_HIP_CHECK(device_alloc(&lv.d_agg_face, g.V));
+      lv.d_agg_face.alloc(g.V);
       DDAMG_HIP_CHECK(hipMemcpy(lv.d_agg_face, g.agg_face.data(), g.V, hipMemcpyHostToDevice));
       if (d == 0) {
         // the forward faces of an aggregate in compact form (AggFaces, transfer.h) -- where every aggregate has the same shape
@@ -82,8 +81,7 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
             af.nface[mu] = (int)list.size() - af.loff[mu];
           }
           tab.insert(tab.end(), list.begin(), list.end());
-          DDAMG_HIP_CHECK(device_alloc(&lv.d_agg_tables, sizeof(unsigned short) * tab.size()));
-          DDAMG_HIP_CHECK(hipMemcpy(lv.d_agg_tables, tab.data(), sizeof(unsigned short) * tab.size(), hipMemcpyHostToDevice));
+          lv.d_agg_tables.upload(tab);
           af.rank = lv.d_agg_tables;
           af.list = lv.d_agg_tables + (size_t)4 * as;
         }
@@ -91,8 +89,7 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
       for (int mu = 0; mu < 4; mu++) {
         std::vector<unsigned char> m(g.V);
         for (int s = 0; s < g.V; s++) m[s] = g.agg_face[s] & (unsigned char)(1u << mu);
-        DDAMG_HIP_CHECK(device_alloc(&lv.d_dir_mask[mu], g.V));
-        DDAMG_HIP_CHECK(hipMemcpy(lv.d_dir_mask[mu], m.data(), g.V, hipMemcpyHostToDevice));
+        lv.d_dir_mask[mu].upload(m);
       }
     }
     if (d > 0 && !lv.coarsest) {
@@ -153,14 +150,13 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
   const Geometry& g0 = *geoms[0];
   std::vector<int> id(g0.V);
   for (int i = 0; i < g0.V; i++) id[i] = i;
-  DDAMG_HIP_CHECK(device_alloc(&d_identity0_, sizeof(int) * g0.V));
-  DDAMG_HIP_CHECK(hipMemcpy(d_identity0_, id.data(), sizeof(int) * g0.V, hipMemcpyHostToDevice));
-  DDAMG_HIP_CHECK(device_alloc(&d_lex0_, sizeof(int) * g0.V));
+  d_identity0_.upload(id);
+  d_lex0_.alloc(g0.V);
   DDAMG_HIP_CHECK(hipMemcpy(d_lex0_, g0.lex_of_site.data(), sizeof(int) * g0.V, hipMemcpyHostToDevice));
-  DDAMG_HIP_CHECK(device_alloc(&d_stage_, sizeof(double) * std::max(lv_[0]->nel, max_coarse)));
+  d_stage_.alloc(std::max(lv_[0]->nel, max_coarse));
   // (W_, the five full fields of the column-by-column Galerkin construction, is allocated when that path first runs: 8 GB at
   // 64^4 that the batched construction never touches)
-  DDAMG_HIP_CHECK(device_alloc(&cwork_, sizeof(T) * max_coarse * 5));
+  cwork_.alloc(max_coarse * 5);
   if (par.gather_coarsest && lv_.back()->g->distributed()) setup_gathered_coarsest();
 }
 
@@ -209,16 +205,16 @@ void Multigrid<T>::setup_gathered_coarsest() {
     }
   }
   for (int s = 0; s < V; s++) DDAMG_REQUIRE(g2d[s] >= 0, "gathered coarsest lattice: a site has no owner");
-  DDAMG_HIP_CHECK(device_alloc(&G.d_g2d, sizeof(int) * V));
-  DDAMG_HIP_CHECK(device_alloc(&G.d_d2g, sizeof(int) * gd.V));
+  G.d_g2d.alloc(V);
+  G.d_d2g.alloc(gd.V);
   DDAMG_HIP_CHECK(hipMemcpy(G.d_g2d, g2d.data(), sizeof(int) * V, hipMemcpyHostToDevice));
   DDAMG_HIP_CHECK(hipMemcpy(G.d_d2g, d2g.data(), sizeof(int) * gd.V, hipMemcpyHostToDevice));
   G.cop.alloc(G.g, n, knobs_);
   const size_t nel = (size_t)V * n * 2;
-  for (int i = 0; i < 2; i++) { DDAMG_HIP_CHECK(device_alloc(&G.buf[i], sizeof(T) * nel)); DDAMG_HIP_CHECK(device_zero(G.buf[i], sizeof(T) * nel)); }
+  for (int i = 0; i < 2; i++) { G.buf[i].alloc(nel); DDAMG_HIP_CHECK(device_zero(G.buf[i], sizeof(T) * nel)); }
   // landing zone of the all-gathers: the operator is the larger payload (5 matrices per site)
   const size_t raw_elems = std::max((size_t)V * 5 * lv.cop.msize() * 2, nel);
-  DDAMG_HIP_CHECK(device_alloc(&G.raw, sizeof(T) * raw_elems));
+  G.raw.alloc(raw_elems);
   G.rw.init(std::max(par_.coarse_iter, 8) + 4);
   G.gm.pipelined = false;     // nothing to hide: the reductions are local
   G.gm.single_allreduce = knobs_.single_allreduce_arnoldi;
@@ -247,34 +243,6 @@ void Multigrid<T>::regather_coarsest_operator() {
 template <typename T>
 Multigrid<T>::~Multigrid() {
   (void)hipStreamSynchronize(st_);
-  for (auto& p : lv_) {
-    MGLevel<T>& lv = *p;
-    for (int i = 0; i < 4; i++) if (lv.buf[i]) (void)hipFree(lv.buf[i]);
-    if (!lv.coarsest) { if (lv.depth == 0) lv.fip.release(); else lv.cip.release(); }
-    if (lv.gm.slab) lv.gm.release();
-    lv.rw.destroy();
-    if (lv.sgm.slab) { lv.sgm.release(); lv.srw.destroy(); }
-    for (int i = 0; i < 3; i++) if (lv.sbuf[i]) (void)hipFree(lv.sbuf[i]);
-    for (int q = 0; q < 2; q++) if (lv.d_parity_sites[q]) (void)hipFree(lv.d_parity_sites[q]);
-    if (lv.d_agg_face) (void)hipFree(lv.d_agg_face);
-    if (lv.d_agg_tables) (void)hipFree(lv.d_agg_tables);
-    for (int mu = 0; mu < 4; mu++) if (lv.d_dir_mask[mu]) (void)hipFree(lv.d_dir_mask[mu]);
-  }
-  if (d_identity0_) (void)hipFree(d_identity0_);
-  if (d_lex0_) (void)hipFree(d_lex0_);
-  if (d_stage_) (void)hipFree(d_stage_);
-  if (W_) (void)hipFree(W_);
-  if (gal_W_) (void)hipFree(gal_W_);
-  if (gal_C_) (void)hipFree(gal_C_);
-  if (gal_cwork_) (void)hipFree(gal_cwork_);
-  if (cwork_) (void)hipFree(cwork_);
-  if (gath_.on) {
-    for (int i = 0; i < 2; i++) if (gath_.buf[i]) (void)hipFree(gath_.buf[i]);
-    if (gath_.raw) (void)hipFree(gath_.raw);
-    if (gath_.d_g2d) (void)hipFree(gath_.d_g2d);
-    if (gath_.d_d2g) (void)hipFree(gath_.d_d2g);
-    gath_.gm.release(); gath_.rw.destroy();
-  }
 }
 
 // ---- level-generic pieces ---------------------------------------------------------------------------
@@ -754,20 +722,17 @@ void Multigrid<T>::build_coarse_operator(int l) {
         if (knobs_.galerkin_slab_aggs.set) gal_slab_aggs_ = std::max(1, std::min(knobs_.galerkin_slab_aggs.value, nagg));   // tests
         DDAMG_REQUIRE(per_agg * (size_t)gal_slab_aggs_ + coarse_b < free_b, "Galerkin construction: slab workspace does not fit the free device memory");
         gal_batch_ = 2 * N;
-        DDAMG_HIP_CHECK(device_alloc(&gal_W_, per_agg * (size_t)gal_slab_aggs_));
-        gal_W_elems_ = per_agg / sizeof(T) * (size_t)gal_slab_aggs_;
+        gal_W_.alloc(per_agg / sizeof(T) * (size_t)gal_slab_aggs_);
       } else {
-        DDAMG_HIP_CHECK(device_alloc(&gal_W_, sizeof(T) * gal_batch_ * wcol));
-        gal_W_elems_ = (size_t)gal_batch_ * wcol;
+        gal_W_.alloc((size_t)gal_batch_ * wcol);
       }
       // coarse column vectors: five per column, or -- with the restriction writing straight into the matrices -- only what the
       // bootstrap borrows (Nvec right-hand sides and Nvec solutions)
       const size_t c_cols = direct ? (size_t)2 * N : (size_t)5 * gal_batch_;
-      DDAMG_HIP_CHECK(device_alloc(&gal_C_, sizeof(T) * c_cols * cs));
-      gal_C_elems_ = c_cols * cs;
+      gal_C_.alloc(c_cols * cs);
     }
     const int batch = gal_batch_;
-    DDAMG_REQUIRE(direct || gal_C_elems_ >= (size_t)5 * gal_batch_ * cs, "Galerkin construction: the workspace of this context was sized for the direct store of the restriction");
+    DDAMG_REQUIRE(direct || gal_C_.size() >= (size_t)5 * gal_batch_ * cs, "Galerkin construction: the workspace of this context was sized for the direct store of the restriction");
     T *Wb = gal_W_, *Cb = gal_C_;
     if (gal_slab_aggs_ > 0) {
       for (int a0 = 0; a0 < nagg; a0 += gal_slab_aggs_) {
@@ -801,14 +766,14 @@ void Multigrid<T>::build_coarse_operator(int l) {
   } else if (l == 0) {
     for (int chir = 0; chir < 2; chir++)
       for (int j = 0; j < N; j++) {
-        if (!W_) DDAMG_HIP_CHECK(device_alloc(&W_, sizeof(T) * lv_[0]->nel * 5));
+        if (!W_) W_.alloc(lv_[0]->nel * 5);
         aggregate_dirac<T>(W_, interpolation_column(lv.fip, j), chir, *lv.fop, lv.d_agg_face, st_);
         galerkin_column<T>(nx.cop, lv.fip, W_, chir * N + j, cwork_, st_);
       }
   } else if constexpr (sizeof(T) == 4) {
     if (!no_batch && coarse_galerkin_batch_available(lv.n, 2 * N, sizeof(T))) {
       // all 2*Nvec columns at once on the matrix cores (coarse_batch.hip)
-      if (!gal_cwork_) DDAMG_HIP_CHECK(device_alloc(&gal_cwork_, sizeof(T) * coarse_galerkin_batch_work(lv_[1]->g->V, lv_[1]->n)));
+      if (!gal_cwork_) gal_cwork_.alloc(coarse_galerkin_batch_work(lv_[1]->g->V, lv_[1]->n));
       coarse_galerkin_batched(nx.cop, lv.cop, lv.cip, lv.d_agg_face, gal_cwork_, knobs_, st_);
       if (nx.coarsest || par_.method == 4) nx.cop.compute_self_inverse(st_);   // D_oo^-1 of the Schur complements
       if (nx.coarsest) regather_coarsest_operator();
@@ -843,9 +808,7 @@ void Multigrid<T>::build_coarse_operator(int l) {
 template <typename T>
 void Multigrid<T>::release_setup_workspace() {
   DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
-  if (gal_W_) { DDAMG_HIP_CHECK(hipFree(gal_W_)); gal_W_ = nullptr; gal_W_elems_ = 0; }
-  if (gal_C_) { DDAMG_HIP_CHECK(hipFree(gal_C_)); gal_C_ = nullptr; gal_C_elems_ = 0; }
-  if (gal_cwork_) { DDAMG_HIP_CHECK(hipFree(gal_cwork_)); gal_cwork_ = nullptr; }
+  gal_W_.reset(); gal_C_.reset(); gal_cwork_.reset();
   lockstep_.release();
   multi1_.release();
 }
@@ -902,11 +865,11 @@ bool Multigrid<T>::bootstrap_vcycles_batched() {
   if (!Interpolation<T>::restrict_batch_available(lv.fip.agg_sites, N) || !Interpolation<T>::interpolate_batch_available(lv.fip.agg_sites, N, N)) return false;
   // the borrowed workspace holds `cap` fine vectors: all Nvec in a first setup; fewer next to a context that already holds its
   // solver workspace (64^4: 17 of 24), and then the interpolation + smoothing at the end goes through it in groups
-  int cap = (int)std::min<size_t>((size_t)N, gal_W_elems_ / ws);
+  int cap = (int)std::min<size_t>((size_t)N, gal_W_.size() / ws);
   if (knobs_.bootstrap_group.set) cap = std::max(1, std::min(cap, knobs_.bootstrap_group.value));   // tests: groups at any volume
-  if (cap < 1 || gal_C_elems_ < (size_t)2 * N * cs) {
+  if (cap < 1 || gal_C_.size() < (size_t)2 * N * cs) {
     if (knobs_.setup_timing)
-      fprintf(stderr, "[ddamg setup] bootstrap one vector at a time: workspace %zu / %zu elements, needed %zu / %zu\n", gal_W_elems_, gal_C_elems_, (size_t)N * ws, (size_t)2 * N * cs);
+      fprintf(stderr, "[ddamg setup] bootstrap one vector at a time: workspace %zu / %zu elements, needed %zu / %zu\n", gal_W_.size(), gal_C_.size(), (size_t)N * ws, (size_t)2 * N * cs);
     return false;
   }
   T* F = gal_W_;                 // N fine vectors: the iterates of the V-cycles
@@ -1103,16 +1066,16 @@ void Multigrid<T>::import_interpolation_level(int l, const double* P_lex_host) {
   if (l == 0) { import_interpolation(P_lex_host); return; }
   MGLevel<T>& lv = *lv_[l];
   DDAMG_REQUIRE(l > 0 && l + 1 < num_levels(), "import_interpolation_level: the level has no coarser level below it");
-  int* d_lex = nullptr;
-  DDAMG_HIP_CHECK(device_alloc(&d_lex, sizeof(int) * lv.g->V));
-  DDAMG_HIP_CHECK(hipMemcpy(d_lex, lv.g->lex_of_site.data(), sizeof(int) * lv.g->V, hipMemcpyHostToDevice));
-  for (int k = 0; k < lv.nvec; k++) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_stage_, P_lex_host + (size_t)k * lv.nel, sizeof(double) * lv.nel, hipMemcpyHostToDevice, st_));
-    aos_from_lex<T>(lv.cip.interp_vector(k), d_stage_, d_lex, lv.g->V, lv.n, st_);
-    aos_from_lex<T>(lv.cip.test_vector(k), d_stage_, d_lex, lv.g->V, lv.n, st_);
-    DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
+  {
+    DeviceBuffer<int> d_lex;
+    d_lex.upload(lv.g->lex_of_site);
+    for (int k = 0; k < lv.nvec; k++) {
+      DDAMG_HIP_CHECK(hipMemcpyAsync(d_stage_, P_lex_host + (size_t)k * lv.nel, sizeof(double) * lv.nel, hipMemcpyHostToDevice, st_));
+      aos_from_lex<T>(lv.cip.interp_vector(k), d_stage_, d_lex, lv.g->V, lv.n, st_);
+      aos_from_lex<T>(lv.cip.test_vector(k), d_stage_, d_lex, lv.g->V, lv.n, st_);
+      DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
+    }
   }
-  DDAMG_HIP_CHECK(hipFree(d_lex));
   p_orthonormal_ = false;
   build_coarse_operator(l);
   initial_setup_from(l + 1);

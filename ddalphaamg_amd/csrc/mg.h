@@ -42,18 +42,18 @@ struct MGLevel {
   // Krylov solver of this level: K-cycle FGMRES (intermediate) or even-site Schur GMRES (coarsest)
   Gmres<T> gm;
   ReduceWork rw;
-  T* buf[4] = {nullptr, nullptr, nullptr, nullptr};
+  DeviceBuffer<T> buf[4];
   // GMRES smoother (method 4): GMRES(block_iter) restarted post_smooth_iter times on the global odd-even Schur complement
   Gmres<T> sgm;
   ReduceWork srw;
-  T* sbuf[3] = {nullptr, nullptr, nullptr};
-  int* d_parity_sites[2] = {nullptr, nullptr};   // depth > 0: even / odd sites of this level
+  DeviceBuffer<T> sbuf[3];
+  DeviceBuffer<int> d_parity_sites[2];           // depth > 0: even / odd sites of this level
   int n_parity_sites[2] = {0, 0};
   // setup helpers
-  unsigned char* d_agg_face = nullptr;
+  DeviceBuffer<unsigned char> d_agg_face;
   AggFaces agg_faces;                    // depth 0: the forward faces of an aggregate in compact form (Galerkin construction)
-  unsigned short* d_agg_tables = nullptr;
-  unsigned char* d_dir_mask[4] = {nullptr, nullptr, nullptr, nullptr};
+  DeviceBuffer<unsigned short> d_agg_tables;   // what agg_faces.rank / .list point into
+  DeviceBuffer<unsigned char> d_dir_mask[4];
   std::vector<int> ref_order;   // site visited i-th by the reference's vector loops on this level
 };
 
@@ -67,10 +67,10 @@ struct GatheredCoarsest {
   CoarseOp<T> cop;
   Gmres<T> gm;
   ReduceWork rw;         // no transport: every process computes the same sums
-  T* buf[2] = {nullptr, nullptr};
-  T* raw = nullptr;      // all-gather landing zone: [process][local site][...]
-  int* d_g2d = nullptr;  // gathered site -> process * V_local + local site
-  int* d_d2g = nullptr;  // my local site -> gathered site
+  DeviceBuffer<T> buf[2];
+  DeviceBuffer<T> raw;        // all-gather landing zone: [process][local site][...]
+  DeviceBuffer<int> d_g2d;    // gathered site -> process * V_local + local site
+  DeviceBuffer<int> d_d2g;    // my local site -> gathered site
   int V_local = 0;
 };
 
@@ -79,7 +79,7 @@ class Multigrid {
  public:
   // knobs: the context's switches (knobs.h); they outlive the hierarchy and reach every object created for it
   Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st);
-  ~Multigrid();
+  ~Multigrid();   // waits for the stream; the members free themselves
 
   // ---- setup -------------------------------------------------------------------------------
   void initial_setup();                 // method_setup
@@ -128,10 +128,9 @@ class Multigrid {
   hipStream_t st_;
   Comm* comm_ = nullptr;
   unsigned long long rng_stream_ = 0;
-  T *gal_W_ = nullptr, *gal_C_ = nullptr;   // batched Galerkin workspace
-  T* gal_cwork_ = nullptr;                  // the same for coarse levels (sized for level 1, the largest)
+  DeviceBuffer<T> gal_W_, gal_C_;           // batched Galerkin workspace (the bootstrap borrows the two between the builds)
+  DeviceBuffer<T> gal_cwork_;               // the same for coarse levels (sized for level 1, the largest)
   int gal_batch_ = 0;
-  size_t gal_W_elems_ = 0, gal_C_elems_ = 0;   // sizes of the two (the bootstrap borrows them between the builds)
   int gal_slab_aggs_ = 0;                   // > 0: all columns, the lattice in slabs of this many aggregates
  public:
   // wall-clock seconds per setup phase (stream-synchronised), filled when DDAMG_SETUP_TIMING is set
@@ -140,11 +139,10 @@ class Multigrid {
   double tick(const char* phase, double t0);
   std::vector<std::unique_ptr<MGLevel<T>>> lv_;
   bool p_orthonormal_ = true;   // false after interpolation vectors were imported as they are: then P^H P = 1 cannot be assumed
-  int* d_lex0_ = nullptr;
-  int* d_identity0_ = nullptr;
-  double* d_stage_ = nullptr;
-  T* W_ = nullptr;        // 5 level-0 vectors (Galerkin)
-  T* cwork_ = nullptr;    // coarse work space (5 vectors of the largest coarse level)
+  DeviceBuffer<int> d_lex0_, d_identity0_;
+  DeviceBuffer<double> d_stage_;
+  DeviceBuffer<T> W_;        // 5 level-0 vectors (Galerkin)
+  DeviceBuffer<T> cwork_;    // coarse work space (5 vectors of the largest coarse level)
 
   GatheredCoarsest<T> gath_;
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)

@@ -32,7 +32,6 @@ struct SapDev {
 template <typename T>
 class SapSmoother {
  public:
-  ~SapSmoother();
   // method: 1 additive, 2 red-black, 3 sixteen colours (g.method of the reference, src/vcycle_generic.c:33-39)
   // odd_even == false: MinRes on the whole block instead of its even-site Schur complement (g.odd_even == 0)
   void setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, const Knobs& knobs, hipStream_t st, bool odd_even = true);
@@ -42,7 +41,7 @@ class SapSmoother {
   void smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st);
   bool ready() const { return op_ != nullptr; }
   // work vectors (exposed for tests): residual r, latest_iter, x
-  T *r = nullptr, *latest = nullptr, *x = nullptr;
+  DeviceBuffer<T> r, latest, x;
 
  private:
   const FineOp<T>* op_ = nullptr;
@@ -50,21 +49,17 @@ class SapSmoother {
   int variant_ = 3;   // block-solver kernel (Knobs::sap_variant), fixed at setup
   enum Schedule { ADDITIVE, RED_BLACK, SIXTEEN, TWO_COLOR } schedule_ = RED_BLACK;
   std::vector<int> ncol_, ncol_interior_;          // blocks per colour; the first ncol_interior_[c] of them have no site next to another process
-  int* d_blk_nb_ = nullptr;
-  int* d_block_list_ = nullptr;
-  std::vector<int*> d_color_blocks_;               // block indices per colour
-  T* latest2_ = nullptr;                           // additive method: the other generation of block updates
+  DeviceBuffer<int> d_blk_nb_, d_block_list_;
+  std::vector<DeviceBuffer<int>> d_color_blocks_;  // block indices per colour
+  DeviceBuffer<T> latest2_;                        // additive method: the other generation of block updates
   // production shape (fp32, 4^4 blocks, multiplicative schedules): one block per workgroup, block-boundary couplings through
   // face buffers (sap_pair.h).  faces_d_: projected faces of every block's latest update; faces_x_: of the iterate x
   bool odd_even_ = true;
   bool pair_ = false;
-  float4 *faces_d_ = nullptr, *faces_x_ = nullptr;
-  unsigned char* d_frank_ = nullptr;
+  DeviceBuffer<float4> faces_d_, faces_x_;
+  DeviceBuffer<unsigned char> d_frank_;            // [BS][4] one byte per direction, written as one packed word per site
   const int* d_block_nb_ = nullptr;                // FineOp's [8][num_blocks] table
-  int* d_block_nb_own_ = nullptr;
-  std::vector<int*> d_other_blocks_;               // red-black: blocks of the other colour (their x faces feed the first full residual)
-  std::vector<int> n_other_blocks_;
-  int* d_all_blocks_ = nullptr;
+  DeviceBuffer<int> d_block_nb_own_, d_all_blocks_;
   // face_in: 0 none, 1 faces_d_, 2 faces_x_;  face_out bit 0: write faces_d_, bit 1: write faces_x_
   // production path: where a visit reads / writes the iterate and the residual (see SapPairArgs)
   struct PairIO { const T* x_in = nullptr; T* x_out = nullptr; const T* r_in = nullptr; const T* res_src = nullptr; const T* halo_src = nullptr;

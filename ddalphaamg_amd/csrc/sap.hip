@@ -657,23 +657,6 @@ __global__ __launch_bounds__((BS < 64 ? 64 : BS), (sizeof(T) == 4 ? 2 : 1)) void
 #undef DDAMG_COLLECT
 
 template <typename T>
-SapSmoother<T>::~SapSmoother() {
-  if (r) (void)hipFree(r);
-  if (latest) (void)hipFree(latest);
-  if (latest2_) (void)hipFree(latest2_);
-  if (x) (void)hipFree(x);
-  if (d_blk_nb_) (void)hipFree(d_blk_nb_);
-  if (d_block_list_) (void)hipFree(d_block_list_);
-  for (int* p : d_color_blocks_) if (p) (void)hipFree(p);
-  for (int* p : d_other_blocks_) if (p) (void)hipFree(p);
-  if (faces_d_) (void)hipFree(faces_d_);
-  if (faces_x_) (void)hipFree(faces_x_);
-  if (d_frank_) (void)hipFree(d_frank_);
-  if (d_block_nb_own_) (void)hipFree(d_block_nb_own_);
-  if (d_all_blocks_) (void)hipFree(d_all_blocks_);
-}
-
-template <typename T>
 void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_iter, int method, const Knobs& knobs, hipStream_t st, bool odd_even) {
   odd_even_ = odd_even; variant_ = knobs.sap_variant;
   op_ = op; V_ = g.V; BS_ = g.block_sites; HS_ = g.block_sites / 2; nblocks_ = g.num_blocks; block_iter_ = block_iter;
@@ -690,19 +673,19 @@ void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_ite
     for (int mu = 0; mu < 4; mu++)
       DDAMG_REQUIRE((g.nblk[mu] * g.P[mu]) % 2 == 0, "multiplicative SAP needs an even number of blocks per direction of the global lattice");
   const size_t n = (size_t)24 * V_;
-  DDAMG_HIP_CHECK(device_alloc(&r, sizeof(T) * n));
-  DDAMG_HIP_CHECK(device_alloc(&latest, sizeof(T) * n));
-  DDAMG_HIP_CHECK(device_alloc(&x, sizeof(T) * n));
+  r.alloc(n);
+  latest.alloc(n);
+  x.alloc(n);
   DDAMG_HIP_CHECK(hipMemsetAsync(r, 0, sizeof(T) * n, st));
   DDAMG_HIP_CHECK(hipMemsetAsync(latest, 0, sizeof(T) * n, st));
   DDAMG_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(T) * n, st));
   if (schedule_ == ADDITIVE) {
-    DDAMG_HIP_CHECK(device_alloc(&latest2_, sizeof(T) * n));
+    latest2_.alloc(n);
     DDAMG_HIP_CHECK(hipMemsetAsync(latest2_, 0, sizeof(T) * n, st));
   }
-  DDAMG_HIP_CHECK(device_alloc(&d_blk_nb_, sizeof(int) * 8 * BS_));
+  d_blk_nb_.alloc(8 * BS_);
   DDAMG_HIP_CHECK(hipMemcpyAsync(d_blk_nb_, g.blk_nb.data(), sizeof(int) * 8 * BS_, hipMemcpyHostToDevice, st));
-  DDAMG_HIP_CHECK(device_alloc(&d_block_list_, sizeof(int) * nblocks_));
+  d_block_list_.alloc(nblocks_);
   DDAMG_HIP_CHECK(hipMemcpyAsync(d_block_list_, g.block_list.data(), sizeof(int) * nblocks_, hipMemcpyHostToDevice, st));
   // per colour: blocks without a neighbour on another process first (their solves overlap with the halo exchange)
   std::vector<std::vector<int>> cb(ncolors), cbb(ncolors);
@@ -713,14 +696,13 @@ void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_ite
     const int c = schedule_ == ADDITIVE ? 0 : schedule_ == SIXTEEN ? g.block_color16[b] : g.block_color[b];
     (boundary ? cbb : cb)[c].push_back(b);
   }
-  ncol_.assign(ncolors, 0); ncol_interior_.assign(ncolors, 0); d_color_blocks_.assign(ncolors, nullptr);
+  ncol_.assign(ncolors, 0); ncol_interior_.assign(ncolors, 0); d_color_blocks_ = std::vector<DeviceBuffer<int>>(ncolors);
   for (int c = 0; c < ncolors; c++) {
     ncol_interior_[c] = (int)cb[c].size();
     cb[c].insert(cb[c].end(), cbb[c].begin(), cbb[c].end());
     ncol_[c] = (int)cb[c].size();
     DDAMG_REQUIRE(ncol_[c] > 0, "SAP needs blocks of every colour");
-    DDAMG_HIP_CHECK(device_alloc(&d_color_blocks_[c], sizeof(int) * ncol_[c]));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_color_blocks_[c], cb[c].data(), sizeof(int) * ncol_[c], hipMemcpyHostToDevice, st));
+    d_color_blocks_[c].upload(cb[c], st);
   }
   // production shape: paired-block kernel with face buffers (sap_pair.hip)
   pair_ = sizeof(T) == 4 && BS_ == 256 && schedule_ != ADDITIVE && variant_ == 3 && odd_even_;
@@ -745,23 +727,20 @@ void SapSmoother<T>::setup(const Geometry& g, const FineOp<T>* op, int block_ite
           DDAMG_REQUIRE((int)on.size() == 32, "a 4^4 block has 32 sites of each parity class on every face");
           for (int k = 0; k < (int)on.size(); k++) packed[on[k].second] |= (unsigned)k << (8 * mu);
         }
-    DDAMG_HIP_CHECK(device_alloc(&d_frank_, sizeof(unsigned) * BS_));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_frank_, packed.data(), sizeof(unsigned) * BS_, hipMemcpyHostToDevice, st));
+    d_frank_.upload(packed, st);
     std::vector<int> nb8((size_t)8 * nblocks_);   // [block][8]: the eight neighbours of a block in one scalar load
     for (int b = 0; b < nblocks_; b++)
       for (int d = 0; d < 8; d++) nb8[(size_t)b * 8 + d] = g.block_nb[(size_t)d * nblocks_ + b];
-    DDAMG_HIP_CHECK(device_alloc(&d_block_nb_own_, sizeof(int) * 8 * nblocks_));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_block_nb_own_, nb8.data(), sizeof(int) * 8 * nblocks_, hipMemcpyHostToDevice, st));
+    d_block_nb_own_.upload(nb8, st);
     d_block_nb_ = d_block_nb_own_;
     const size_t fe = sap_face_elems(nblocks_);
-    DDAMG_HIP_CHECK(device_alloc(&faces_d_, sizeof(float4) * fe));
-    DDAMG_HIP_CHECK(device_alloc(&faces_x_, sizeof(float4) * fe));
+    faces_d_.alloc(fe);
+    faces_x_.alloc(fe);
     DDAMG_HIP_CHECK(hipMemsetAsync(faces_d_, 0, sizeof(float4) * fe, st));
     DDAMG_HIP_CHECK(hipMemsetAsync(faces_x_, 0, sizeof(float4) * fe, st));
     std::vector<int> all(nblocks_);
     for (int b = 0; b < nblocks_; b++) all[b] = b;
-    DDAMG_HIP_CHECK(device_alloc(&d_all_blocks_, sizeof(int) * nblocks_));
-    DDAMG_HIP_CHECK(hipMemcpyAsync(d_all_blocks_, all.data(), sizeof(int) * nblocks_, hipMemcpyHostToDevice, st));
+    d_all_blocks_.upload(all, st);
     DDAMG_HIP_CHECK(hipStreamSynchronize(st));   // the host vectors above go out of scope
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));

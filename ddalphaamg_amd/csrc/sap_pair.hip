@@ -557,19 +557,15 @@ __global__ __launch_bounds__(256) void sap_face_pack_kernel(FineOpDev<float> op,
 using namespace sap_pair_detail;
 
 #ifdef DDAMG_SAP_CHAIN_DIAG
-static unsigned long long* g_sap_diag = nullptr;
-static size_t g_sap_diag_wgs = 0;
+static DeviceBuffer<unsigned long long> g_sap_diag;   // [workgroups][4][SAP_DIAG_STAMPS]
+static size_t sap_diag_workgroups() { return g_sap_diag.size() / (4 * SAP_DIAG_STAMPS); }
 unsigned long long* sap_chain_diag_buffer(size_t workgroups) {
-  if (workgroups > g_sap_diag_wgs) {
-    if (g_sap_diag) (void)hipFree(g_sap_diag);
-    DDAMG_HIP_CHECK(device_alloc(&g_sap_diag, sizeof(unsigned long long) * workgroups * 4 * SAP_DIAG_STAMPS));
-    g_sap_diag_wgs = workgroups;
-  }
+  if (workgroups > sap_diag_workgroups()) g_sap_diag.alloc(workgroups * 4 * SAP_DIAG_STAMPS);
   return g_sap_diag;
 }
 // the stamps of the last stamped launch: [workgroups][4][16]; returns the number of workgroups (0: nothing stamped yet)
 extern "C" int ddamg_hip_diag_sap_chain(unsigned long long* host, int max_workgroups) {
-  const int n = (int)std::min<size_t>(g_sap_diag_wgs, (size_t)max_workgroups);
+  const int n = (int)std::min<size_t>(sap_diag_workgroups(), (size_t)max_workgroups);
   if (n > 0 && hipMemcpy(host, g_sap_diag, sizeof(unsigned long long) * (size_t)n * 4 * SAP_DIAG_STAMPS, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
 }

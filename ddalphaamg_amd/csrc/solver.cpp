@@ -65,8 +65,8 @@ static void ensure_outer(ddamg_hip_ctx* c) {
       c->outer.prec = [c](double* phi, double*, const double* eta, int) { c->bicg64.solve(phi, eta, c->outer.tol); };
     } else {
       c->bicg32.init(g0, &c->fop32, c->stream); c->bicg32.set_comm(c->comm);
-      DDAMG_HIP_CHECK(device_alloc(&c->p32_in, sizeof(float) * n));
-      DDAMG_HIP_CHECK(device_alloc(&c->p32_out, sizeof(float) * n));
+      c->p32_in.alloc(n);
+      c->p32_out.alloc(n);
       c->outer.prec = [c](double* phi, double*, const double* eta, int) {
         const size_t V = c->levels[0]->geom.V;
         const double rel = c->outer.gamma_jp1 / c->outer.norm_r0;
@@ -81,8 +81,8 @@ static void ensure_outer(ddamg_hip_ctx* c) {
     if (c->par.mixed_precision == 0) {
       c->outer.prec = [c](double* phi, double* Dphi, const double* eta, int res) { c->mg64->vcycle(0, phi, Dphi, eta, res); };
     } else {
-      DDAMG_HIP_CHECK(device_alloc(&c->p32_in, sizeof(float) * n));
-      DDAMG_HIP_CHECK(device_alloc(&c->p32_out, sizeof(float) * n));
+      c->p32_in.alloc(n);
+      c->p32_out.alloc(n);
       // preconditioner(): trans_float -> vcycle_float -> trans_back_float (src/preconditioner.c:31-33)
       c->outer.prec = [c](double* phi, double* Dphi, const double* eta, int res) {
         const size_t V = c->levels[0]->geom.V;
@@ -201,7 +201,7 @@ static void ensure_mp(ddamg_hip_ctx* c) {
     c->mp_inner.prec = [c](float* phi, float* Dphi, const float* eta, int res) { c->mg32->vcycle(0, phi, c->par.method <= 2 ? Dphi : nullptr, eta, res); };
     c->mp_inner.prec_gives_Dphi = c->par.method <= 2;   // g.method >= 1 && g.method <= 2, src/linsolve.c:338
   }
-  for (double** p : {&c->mp_x, &c->mp_b, &c->mp_r}) DDAMG_HIP_CHECK(device_alloc(p, sizeof(double) * n));
+  for (DeviceBuffer<double>* p : {&c->mp_x, &c->mp_b, &c->mp_r}) p->alloc(n);
   if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
   c->mp_ready = true;
 }
@@ -392,10 +392,8 @@ static void check_vec(ddamg_hip_ctx* c, const ddamg_hip_vec* v, int level) {
 namespace {
 // columns next to each other in one device buffer, as the bootstrap holds them
 struct Columns {
-  float* p = nullptr; size_t cs = 0;
-  Columns(size_t cs_, int ncols) : cs(cs_) { DDAMG_HIP_CHECK(device_alloc(&p, sizeof(float) * cs * ncols)); }
-  ~Columns() { if (p) (void)hipFree(p); }
-  Columns(const Columns&) = delete; Columns& operator=(const Columns&) = delete;
+  DeviceBuffer<float> p; size_t cs = 0;
+  Columns(size_t cs_, int ncols) : cs(cs_) { p.alloc(cs * ncols); }
 };
 int many_level(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* a, const ddamg_hip_vec* const* b) {
   DDAMG_REQUIRE(c && c->mg32 && a && b, "the many-right-hand-side entry points need the fp32 hierarchy (mixed_precision >= 1)");
@@ -409,10 +407,10 @@ int many_level(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* a, const ddamg
   return lvl;
 }
 void pack(ddamg_hip_ctx* c, Columns& C, const ddamg_hip_vec* const* v, int ncols) {
-  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(C.p + (size_t)k * C.cs, v[k]->data, v[k]->bytes, hipMemcpyDeviceToDevice, c->stream));
+  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(C.p + (size_t)k * C.cs, v[k]->data.get(), v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
 }
 void unpack(ddamg_hip_ctx* c, ddamg_hip_vec* const* v, const Columns& C, int ncols) {
-  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(v[k]->data, C.p + (size_t)k * C.cs, v[k]->bytes, hipMemcpyDeviceToDevice, c->stream));
+  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(v[k]->data.get(), C.p + (size_t)k * C.cs, v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 }  // namespace
@@ -425,8 +423,8 @@ int ddamg_hip_smoother(ddamg_hip_ctx* c, ddamg_hip_vec* phi, const ddamg_hip_vec
   DDAMG_REQUIRE(phi && phi->level >= 0 && phi->level + 1 < c->par.num_levels, "smoother: the coarsest level has none");
   const int lvl = phi->level;
   check_vec(c, phi, lvl); check_vec(c, eta, lvl);
-  if (c->mg32) c->mg32->smoother(lvl, (float*)phi->data, nullptr, (const float*)eta->data, cycles, initial_guess_zero ? NO_RES : RES);
-  else c->mg64->smoother(lvl, (double*)phi->data, nullptr, (const double*)eta->data, cycles, initial_guess_zero ? NO_RES : RES);
+  if (c->mg32) c->mg32->smoother(lvl, (float*)phi->data.get(), nullptr, (const float*)eta->data.get(), cycles, initial_guess_zero ? NO_RES : RES);
+  else c->mg64->smoother(lvl, (double*)phi->data.get(), nullptr, (const double*)eta->data.get(), cycles, initial_guess_zero ? NO_RES : RES);
   DDAMG_API_END
 }
 
@@ -436,8 +434,8 @@ int ddamg_hip_restrict(ddamg_hip_ctx* c, ddamg_hip_vec* coarse, const ddamg_hip_
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   DDAMG_REQUIRE(fine && fine->level >= 0 && fine->level + 1 < c->par.num_levels, "restrict: no coarser level below this vector");
   check_vec(c, coarse, fine->level + 1); check_vec(c, fine, fine->level);
-  if (c->mg32) c->mg32->restrict_to(fine->level, (float*)coarse->data, (const float*)fine->data);
-  else c->mg64->restrict_to(fine->level, (double*)coarse->data, (const double*)fine->data);
+  if (c->mg32) c->mg32->restrict_to(fine->level, (float*)coarse->data.get(), (const float*)fine->data.get());
+  else c->mg64->restrict_to(fine->level, (double*)coarse->data.get(), (const double*)fine->data.get());
   DDAMG_API_END
 }
 
@@ -447,8 +445,8 @@ int ddamg_hip_interpolate(ddamg_hip_ctx* c, ddamg_hip_vec* fine, const ddamg_hip
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   DDAMG_REQUIRE(fine && fine->level >= 0 && fine->level + 1 < c->par.num_levels, "interpolate: no coarser level below this vector");
   check_vec(c, coarse, fine->level + 1); check_vec(c, fine, fine->level);
-  if (c->mg32) c->mg32->interpolate(fine->level, (float*)fine->data, (const float*)coarse->data, add != 0);
-  else c->mg64->interpolate(fine->level, (double*)fine->data, (const double*)coarse->data, add != 0);
+  if (c->mg32) c->mg32->interpolate(fine->level, (float*)fine->data.get(), (const float*)coarse->data.get(), add != 0);
+  else c->mg64->interpolate(fine->level, (double*)fine->data.get(), (const double*)coarse->data.get(), add != 0);
   DDAMG_API_END
 }
 
@@ -458,8 +456,8 @@ int ddamg_hip_coarse_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   DDAMG_REQUIRE(out && in && out->level >= 1 && out->level == in->level, "coarse vectors of one level expected");
   check_vec(c, out, out->level); check_vec(c, in, in->level);
-  if (c->mg32) c->mg32->apply_op(out->level, (float*)out->data, (const float*)in->data);
-  else c->mg64->apply_op(out->level, (double*)out->data, (const double*)in->data);
+  if (c->mg32) c->mg32->apply_op(out->level, (float*)out->data.get(), (const float*)in->data.get());
+  else c->mg64->apply_op(out->level, (double*)out->data.get(), (const double*)in->data.get());
   DDAMG_API_END
 }
 
@@ -471,13 +469,13 @@ int ddamg_hip_coarse_solve(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_v
   check_vec(c, x, lc); check_vec(c, b, lc);
   int it;
   if (c->mg32) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->coarse_b(), b->data, b->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->coarse_b(), b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
     it = c->mg32->coarse_solve();
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data, c->mg32->coarse_x(), x->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg32->coarse_x(), x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   } else {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->coarse_b(), b->data, b->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->coarse_b(), b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
     it = c->mg64->coarse_solve();
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data, c->mg64->coarse_x(), x->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg64->coarse_x(), x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   }
   if (iterations) *iterations = it;
   DDAMG_API_END
@@ -491,13 +489,13 @@ int ddamg_hip_coarse_solve_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* cons
   const int lc = c->par.num_levels - 1;
   for (int k = 0; k < ncols; k++) { check_vec(c, x[k], lc); check_vec(c, b[k], lc); DDAMG_REQUIRE(x[k]->precision == 32 && b[k]->precision == 32, "fp32 vectors expected"); }
   // columns next to each other in one buffer, as the bootstrap holds them
-  const size_t cs = b[0]->bytes / sizeof(float);
+  const size_t cs = b[0]->data.bytes() / sizeof(float);
   Columns B(cs, ncols), X(cs, ncols);     // freed on every path out of here
   pack(c, B, b, ncols);
   const bool ok = c->mg32->coarse_solve_many(X.p, cs, B.p, cs, ncols, iterations);
   if (ok)
     for (int k = 0; k < ncols; k++)
-      if (iterations[k] >= 0) DDAMG_HIP_CHECK(hipMemcpyAsync(x[k]->data, X.p + (size_t)k * cs, x[k]->bytes, hipMemcpyDeviceToDevice, c->stream));
+      if (iterations[k] >= 0) DDAMG_HIP_CHECK(hipMemcpyAsync(x[k]->data.get(), X.p + (size_t)k * cs, x[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   c->mg32->release_many_workspace();      // the lockstep batches are setup workspace: not kept next to the production solves
   DDAMG_REQUIRE(ok, "coarse_solve_many: shape not covered (fp32, single process, odd-even, at most 64 dof per site)");
@@ -511,8 +509,8 @@ int ddamg_hip_vcycle(ddamg_hip_ctx* c, ddamg_hip_vec* phi, const ddamg_hip_vec* 
   DDAMG_REQUIRE(phi && phi->level >= 0 && phi->level + 1 < c->par.num_levels, "vcycle: the coarsest level has none");
   const int lvl = phi->level;
   check_vec(c, phi, lvl); check_vec(c, eta, lvl);
-  if (c->mg32) c->mg32->vcycle(lvl, (float*)phi->data, nullptr, (const float*)eta->data, NO_RES);
-  else c->mg64->vcycle(lvl, (double*)phi->data, nullptr, (const double*)eta->data, NO_RES);
+  if (c->mg32) c->mg32->vcycle(lvl, (float*)phi->data.get(), nullptr, (const float*)eta->data.get(), NO_RES);
+  else c->mg64->vcycle(lvl, (double*)phi->data.get(), nullptr, (const double*)eta->data.get(), NO_RES);
   DDAMG_API_END
 }
 
@@ -525,13 +523,13 @@ int ddamg_hip_kcycle(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b,
   check_vec(c, x, lvl); check_vec(c, b, lvl);
   int it;
   if (c->mg32) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->level(lvl).gm.b, b->data, b->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->level(lvl).gm.b, b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
     it = c->mg32->kcycle_solve(lvl);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data, c->mg32->level(lvl).gm.x, x->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg32->level(lvl).gm.x, x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   } else {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->level(lvl).gm.b, b->data, b->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->level(lvl).gm.b, b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
     it = c->mg64->kcycle_solve(lvl);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data, c->mg64->level(lvl).gm.x, x->bytes, hipMemcpyDeviceToDevice, c->stream));
+    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg64->level(lvl).gm.x, x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (iterations) *iterations = it;
@@ -543,7 +541,7 @@ int ddamg_hip_coarse_apply_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* cons
   DDAMG_API_BEGIN
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, out, in);
-  Columns I(in[0]->bytes / sizeof(float), ncols), O(in[0]->bytes / sizeof(float), ncols);
+  Columns I(in[0]->data.bytes() / sizeof(float), ncols), O(in[0]->data.bytes() / sizeof(float), ncols);
   pack(c, I, in, ncols);
   const bool ok = lvl == c->par.num_levels - 1 ? c->mg32->coarsest_apply_many(O.p, O.cs, I.p, I.cs, ncols) : (lvl == 1 && c->mg32->level1_apply_many(O.p, O.cs, I.p, I.cs, ncols));
   if (ok) unpack(c, out, O, ncols);
@@ -556,7 +554,7 @@ int ddamg_hip_smoother_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* p
   DDAMG_API_BEGIN
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, phi, eta);
-  Columns E(eta[0]->bytes / sizeof(float), ncols), P(eta[0]->bytes / sizeof(float), ncols);
+  Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
   pack(c, E, eta, ncols); pack(c, P, phi, ncols);
   const bool ok = lvl == 1 && c->mg32->level1_smooth_many(P.p, P.cs, E.p, E.cs, ncols, cycles, initial_guess_zero ? NO_RES : RES);
   if (ok) unpack(c, phi, P, ncols);
@@ -570,7 +568,7 @@ int ddamg_hip_vcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* phi
   DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, phi, eta);
-  Columns E(eta[0]->bytes / sizeof(float), ncols), P(eta[0]->bytes / sizeof(float), ncols);
+  Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
   pack(c, E, eta, ncols);
   const bool ok = lvl == 1 && c->mg32->level1_vcycle_many(P.p, P.cs, E.p, E.cs, ncols);
   if (ok) unpack(c, phi, P, ncols);
@@ -584,7 +582,7 @@ int ddamg_hip_kcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* x, 
   DDAMG_REQUIRE(c && c->setup_done && iterations, "setup has not been run");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, x, b);
-  Columns B(b[0]->bytes / sizeof(float), ncols), X(b[0]->bytes / sizeof(float), ncols);
+  Columns B(b[0]->data.bytes() / sizeof(float), ncols), X(b[0]->data.bytes() / sizeof(float), ncols);
   pack(c, B, b, ncols);
   const bool ok = lvl == 1 && c->mg32->level1_kcycle_many(X.p, X.cs, B.p, B.cs, ncols, iterations);
   if (ok) unpack(c, x, X, ncols);
@@ -665,8 +663,8 @@ int ddamg_hip_solve_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec*
   DDAMG_REQUIRE(x->level == 0 && b->level == 0 && x->precision == 64 && b->precision == 64, "solve_vec needs fine-level fp64 vectors");
   const size_t n = (size_t)24 * c->levels[0]->geom.V;
   solve_core(c, tol,
-             [&](double* dst) { vec_copy<double>(dst, (const double*)b->data, whole(n), c->stream); },
-             [&](const double* src) { vec_copy<double>((double*)x->data, src, whole(n), c->stream); },
+             [&](double* dst) { vec_copy<double>(dst, (const double*)b->data.get(), whole(n), c->stream); },
+             [&](const double* src) { vec_copy<double>((double*)x->data.get(), src, whole(n), c->stream); },
              iterations, coarse_iterations, relres);
   DDAMG_API_END
 }
@@ -685,16 +683,16 @@ int ddamg_hip_vec_copy(ddamg_hip_ctx* c, ddamg_hip_vec* dst, const ddamg_hip_vec
   DDAMG_API_BEGIN
   same_shape(dst, src);
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (dst->precision == 32) vec_copy<float>((float*)dst->data, (const float*)src->data, whole(vec_len(dst)), c->stream);
-  else vec_copy<double>((double*)dst->data, (const double*)src->data, whole(vec_len(dst)), c->stream);
+  if (dst->precision == 32) vec_copy<float>((float*)dst->data.get(), (const float*)src->data.get(), whole(vec_len(dst)), c->stream);
+  else vec_copy<double>((double*)dst->data.get(), (const double*)src->data.get(), whole(vec_len(dst)), c->stream);
   DDAMG_API_END
 }
 int ddamg_hip_vec_axpy(ddamg_hip_ctx* c, ddamg_hip_vec* z, const ddamg_hip_vec* x, const ddamg_hip_vec* y, double alpha_re, double alpha_im) {
   DDAMG_API_BEGIN
   same_shape(z, x); same_shape(z, y);
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (z->precision == 32) vec_axpy<float>((float*)z->data, (const float*)x->data, (const float*)y->data, alpha_re, alpha_im, whole(vec_len(z)), c->stream);
-  else vec_axpy<double>((double*)z->data, (const double*)x->data, (const double*)y->data, alpha_re, alpha_im, whole(vec_len(z)), c->stream);
+  if (z->precision == 32) vec_axpy<float>((float*)z->data.get(), (const float*)x->data.get(), (const float*)y->data.get(), alpha_re, alpha_im, whole(vec_len(z)), c->stream);
+  else vec_axpy<double>((double*)z->data.get(), (const double*)x->data.get(), (const double*)y->data.get(), alpha_re, alpha_im, whole(vec_len(z)), c->stream);
   DDAMG_API_END
 }
 int ddamg_hip_vec_dot(ddamg_hip_ctx* c, const ddamg_hip_vec* x, const ddamg_hip_vec* y, double* re, double* im, double* norm_x) {
@@ -702,8 +700,8 @@ int ddamg_hip_vec_dot(ddamg_hip_ctx* c, const ddamg_hip_vec* x, const ddamg_hip_
   same_shape(x, y);
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   ReduceWork& rw = blas_rw(c);
-  if (x->precision == 32) vec_dot_and_norm2<float>((const float*)x->data, (const float*)y->data, whole(vec_len(x)), rw, rw.d_result, c->stream);
-  else vec_dot_and_norm2<double>((const double*)x->data, (const double*)y->data, whole(vec_len(x)), rw, rw.d_result, c->stream);
+  if (x->precision == 32) vec_dot_and_norm2<float>((const float*)x->data.get(), (const float*)y->data.get(), whole(vec_len(x)), rw, rw.d_result, c->stream);
+  else vec_dot_and_norm2<double>((const double*)x->data.get(), (const double*)y->data.get(), whole(vec_len(x)), rw, rw.d_result, c->stream);
   DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (re) *re = rw.h_result[0];

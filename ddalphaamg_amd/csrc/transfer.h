@@ -42,12 +42,11 @@ template <typename T>
 struct Interpolation {
   int V = 0, nvec = 0, num_aggs = 0, agg_sites = 0;
   size_t pstride = 0;      // elements between consecutive vectors
-  T* tv = nullptr;         // test vectors   [nvec][24*V]
-  T* P = nullptr;          // orthonormalised interpolation vectors, aggregate by aggregate: [aggregate][nvec][24 * plane_sites()]
-  int* agg_csite = nullptr; // [num_aggs] coarse-level site index of every aggregate
+  DeviceBuffer<T> tv;      // test vectors   [nvec][24*V]
+  DeviceBuffer<T> P;       // orthonormalised interpolation vectors, aggregate by aggregate: [aggregate][nvec][24 * plane_sites()]
+  DeviceBuffer<int> agg_csite; // [num_aggs] coarse-level site index of every aggregate
   const Knobs* knobs = nullptr;   // the context's switches (alloc): gs_workgroup
   void alloc(const Geometry& g, const Geometry& gc, int nvec_, const Knobs& knobs_);
-  void release();
   T* test_vector(int j) const { return tv + pstride * j; }
   // column j of P from / into a vector in lattice order (import, export, the Galerkin construction's fall-back paths)
   void set_column(int j, const T* vec, hipStream_t st);

@@ -30,20 +30,13 @@ void Interpolation<T>::alloc(const Geometry& g, const Geometry& gc, int nvec_, c
   DDAMG_REQUIRE(gc.V == g.num_aggs, "coarse lattice does not match the aggregate decomposition");
   // aggregate a (lexicographic in aggregate coordinates) is coarse lattice point with the same
   // coordinates; its index in the coarse level's own site ordering:
-  DDAMG_HIP_CHECK(device_alloc(&agg_csite, sizeof(int) * num_aggs));
+  agg_csite.alloc(num_aggs);
   DDAMG_HIP_CHECK(hipMemcpy(agg_csite, gc.site_of_lex.data(), sizeof(int) * num_aggs, hipMemcpyHostToDevice));
   pstride = (size_t)24 * V;
-  DDAMG_HIP_CHECK(device_alloc(&tv, sizeof(T) * pstride * nvec));
-  DDAMG_HIP_CHECK(device_alloc(&P, sizeof(T) * p_elems()));
+  tv.alloc(pstride * nvec);
+  P.alloc(p_elems());
   DDAMG_HIP_CHECK(device_zero(tv, sizeof(T) * pstride * nvec));
   DDAMG_HIP_CHECK(device_zero(P, sizeof(T) * p_elems()));
-}
-template <typename T>
-void Interpolation<T>::release() {
-  if (tv) (void)hipFree(tv);
-  if (P) (void)hipFree(P);
-  if (agg_csite) (void)hipFree(agg_csite);
-  tv = P = nullptr; agg_csite = nullptr;
 }
 
 // ---- restriction: phi_c[a][h*N + j] = sum_{x in a, d in chirality h} conj(P_j(x,d)) phi(x,d) ------

@@ -18,6 +18,8 @@
 #ifndef DDAMG_HIP_H
 #define DDAMG_HIP_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -250,6 +252,11 @@ int ddamg_hip_comm_init_host(ddamg_hip_ctx* ctx, ddamg_hip_exchange_fn fn, ddamg
  * reset != 0 clears the counters and returns "{}".  For reading a multi-GPU run against the message table of
  * docs/design/06a_rehearsal_and_messages.md. */
 const char* ddamg_hip_comm_stats(ddamg_hip_ctx* ctx, int reset);
+/* Bytes of device memory and of pinned host memory that the library's own buffers hold at this moment, summed over all contexts
+ * of the process (either pointer may be NULL).  What RCCL and the HIP runtime allocate for themselves is not counted.  A
+ * diagnostic for leak checks: hipMemGetInfo is device-wide, so on a GPU shared with other processes its differences prove
+ * nothing.  Needs no context; always returns 0. */
+int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes);
 /* host-only helper (no GPU needed): the halo plan of one process.  For face d (0..3: +mu face sending to
  * +mu, 4..7: -mu face) returns the neighbour rank and, if lex_sites != NULL, the local lexicographic index
  * of the face sites in message (slot) order; *count = 0 when the direction is not split. */

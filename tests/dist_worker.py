@@ -331,6 +331,43 @@ def run_sample_np2(rank, world, P):
     return dev * 1e-6
 
 
+def run_ownership(rank, world, P):
+    """one lifetime of a two-level context on the process grid through the host transport, the coarsest level gathered: every
+    byte of device and pinned host memory that the library's buffers took is back after close (ddamg_hip_memory_in_use)"""
+    import ddalphaamg_amd as dd
+    here = os.path.dirname(os.path.abspath(__file__))
+    g = np.load(os.path.join(here, "golden", "ref_8x8_dirac.npz"))
+    G = [8, 8, 8, 8]
+    L = [G[mu] // P[mu] for mu in range(4)]
+    C = ddist.coords_of(rank, P)
+    start = api.memory_in_use()
+    p = api.default_params(); p.num_levels = 2
+    for mu in range(4):
+        p.local_lattice[0][mu] = L[mu]; p.block_lattice[0][mu] = 2; p.local_lattice[1][mu] = L[mu] // 2
+        p.process_grid[mu] = P[mu]; p.process_coords[mu] = C[mu]
+    p.num_vect[0] = 8; p.setup_iter[0] = 1
+    p.restart, p.max_restart, p.tol = 30, 20, 1e-8
+    p.coarse_iter, p.coarse_restart, p.coarse_tol = 30, 10, 5e-2
+    p.mixed_precision, p.method, p.odd_even = 1, 2, 1
+    p.m0, p.csw = -0.5, 1.0
+    p.gather_coarsest = 1
+    ctx = dd.Context(p)
+    ddist.attach_host(ctx)
+    ctx.set_gauge(ddist.local_part(g["gauge"], G, P, C), anti_pbc=True)
+    ctx.setup(1)
+    b = np.zeros((int(np.prod(L)), 12, 2)); b[..., 0] = 1.0
+    _, it, _, rr = ctx.solve(b, 1e-8)
+    for lvl in range(2):
+        ctx.vector(lvl, 32).free()
+    held = api.memory_in_use()
+    dist.barrier()
+    ctx.close()
+    end = api.memory_in_use()
+    print(f"rank {rank}: {it} iterations, relres {rr:.2e}; held {held}, after close {end}, at start {start}", flush=True)
+    assert held[0] > start[0] and held[1] > start[1] and end == start, (start, held, end)
+    return 0.0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="plan")
@@ -356,6 +393,8 @@ def main():
         err = run_sample_np2(rank, world, P)
     elif a.mode == "amg3":
         err = run_amg(rank, world, P, a.prec, levels=3, G=[int(x) for x in a.lattice.split(",")], method=a.method, gather=a.gather)
+    elif a.mode == "ownership":
+        err = run_ownership(rank, world, P)
     elif a.mode == "gmres":
         err = run_gmres(rank, world, P, a.prec)
     else:

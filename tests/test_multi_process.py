@@ -82,6 +82,13 @@ def test_coarsest_level_gathered_on_every_process(nproc, grid, mode, lattice):
 
 
 @pytest.mark.gpu
+def test_every_rank_gets_its_memory_back():
+    """two ranks through the host transport with the coarsest level gathered: the halo arenas, the pinned staging of the
+    transport and the gathered level are back after close on every rank (dist_worker.run_ownership)"""
+    launch(2, "--mode", "ownership", "--grid", "2,1,1,1", timeout=300)
+
+
+@pytest.mark.gpu
 def test_decomposed_two_level_amg_with_pipelined_arnoldi(monkeypatch):
     """the coarsest-level recurrence whose global sum travels behind the operator application (DDAMG_PIPELINED_ARNOLDI)"""
     monkeypatch.setenv("DDAMG_PIPELINED_ARNOLDI", "1")
