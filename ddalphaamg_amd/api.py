@@ -122,6 +122,9 @@ def load_library():
         "ddamg_hip_interpolate": [vp, vp, vp, ctypes.c_int],
         "ddamg_hip_coarse_apply": [vp, vp, vp],
         "ddamg_hip_coarse_solve": [vp, vp, vp, ctypes.POINTER(ctypes.c_int)],
+        "ddamg_hip_set_coarse_storage": [vp, ctypes.c_int],
+        "ddamg_hip_coarse_hop": [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_coarse_self_mul": [vp, vp, vp, ctypes.c_int, ctypes.c_int],
         "ddamg_hip_coarse_solve_many": [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_vcycle": [vp, vp, vp],
         "ddamg_hip_solve": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
@@ -452,6 +455,19 @@ class Context:
         it = ctypes.c_int(0)
         _check(self._lib.ddamg_hip_coarse_solve(self._h, x._h, b._h, ctypes.byref(it)))
         return it.value
+
+    def set_coarse_storage(self, bits):
+        """storage of the coarsest couplings for the solve: 32 (default) or 16 (fp16 pairs + one fp32 scale per matrix, fp32
+        accumulation); raises DDAMGError where the context cannot carry 16 (see include/ddamg_hip.h)"""
+        _check(self._lib.ddamg_hip_set_coarse_storage(self._h, int(bits)))
+
+    def coarse_hop(self, out, inp, parity, sign=1.0, accumulate=False):
+        """a half hopping term of the coarsest level: out (+)= sign * hopping terms of inp on the even (0) / odd (1) sites"""
+        _check(self._lib.ddamg_hip_coarse_hop(self._h, out._h, inp._h, int(parity), float(sign), int(bool(accumulate))))
+
+    def coarse_self_mul(self, out, inp, parity, inverse=False):
+        """out = M0 inp (or M0^-1 inp) on the even (0) / odd (1) sites of the coarsest level"""
+        _check(self._lib.ddamg_hip_coarse_self_mul(self._h, out._h, inp._h, int(parity), int(bool(inverse))))
 
     def coarse_solve_many(self, xs, bs):
         """the coarsest-level solve for up to 32 right-hand sides in lockstep (matrix-core coarse operator); returns the list of

@@ -34,6 +34,15 @@ double* ddamg_hip_ctx::stage(size_t bytes) {
   return d_stage;
 }
 
+// why this context cannot keep its coarsest couplings in 16 bits (nullptr: it can)
+static const char* coarse_half_refusal(const ddamg_hip_ctx* c) {
+  if (c->par.num_levels < 2 || c->par.method < 1 || c->par.method > 4) return "16-bit coarse storage needs a multigrid hierarchy (two levels or more, method 1 to 4)";
+  if (c->par.mixed_precision == 0) return "16-bit coarse storage needs the fp32 V-cycle (mixed_precision 1 or 2)";
+  if (c->par.odd_even == 0) return "16-bit coarse storage is implemented for the odd-even coarsest solve (odd_even = 1)";
+  if (c->levels.back()->geom.distributed() && !c->par.gather_coarsest) return "16-bit coarse storage needs the coarsest level on one process (single process, or gather_coarsest)";
+  return nullptr;
+}
+
 extern "C" {
 
 const char* ddamg_hip_last_error(void) { return g_last_error.c_str(); }
@@ -122,6 +131,7 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
     DDAMG_HIP_CHECK(hipMemcpy(lv->d_lex_of_site, lv->geom.lex_of_site.data(), sizeof(int) * lv->geom.V, hipMemcpyHostToDevice));
     c->levels.push_back(std::move(lv));
   }
+  if (c->knobs.coarse_half && coarse_half_refusal(c.get()) == nullptr) c->coarse_storage_bits = 16;
   srand(1000u * (unsigned)c->levels[0]->geom.rank);  // reference: srand( 1000*g.my_rank ) unless "randomize test vectors" (src/init.c:870-873)
   *out = c.release();
   DDAMG_API_END
@@ -137,6 +147,17 @@ int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes) {
   if (device_bytes) *device_bytes = DeviceMemory::in_use.load();
   if (pinned_bytes) *pinned_bytes = PinnedMemory::in_use.load();
   return 0;
+}
+
+int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* c, int bits) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_REQUIRE(bits == 16 || bits == 32, "coarse storage: bits must be 16 or 32");
+  if (bits == 16) if (const char* why = coarse_half_refusal(c)) throw std::runtime_error(why);
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  if (c->mg32) c->mg32->set_coarse_storage(bits);
+  c->coarse_storage_bits = bits;
+  DDAMG_API_END
 }
 
 static void drop_clover_base(ddamg_hip_ctx* c) {

@@ -68,6 +68,9 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   std::unique_ptr<ddamg::Multigrid<float>> mg32;
   std::unique_ptr<ddamg::Multigrid<double>> mg64;
   bool setup_done = false;
+  // bits per real of the coarsest couplings the solve reads, 32 or 16 (ddamg_hip_set_coarse_storage; initial value from
+  // knobs.coarse_half); handed to mg32 when the hierarchy is created
+  int coarse_storage_bits = 32;
   // outer FGMRES (fp64) and its workspace
   ddamg::Gmres<double> outer;
   ddamg::ReduceWork rw_outer;

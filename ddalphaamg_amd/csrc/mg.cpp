@@ -248,7 +248,31 @@ Multigrid<T>::~Multigrid() {
 // ---- level-generic pieces ---------------------------------------------------------------------------
 template <typename T> void Multigrid<T>::apply_op(int l, T* out, const T* in) {
   if (l == 0) lv_[0]->fop->apply(out, in, st_);
+  else if (lv_[l]->coarsest && half_storage(lv_[l]->cop)) {   // self coupling, then the hopping terms on top of it
+    DDAMG_REQUIRE(out != in, "coarse apply cannot run in place");
+    const CoarseOp<T>& cop = lv_[l]->cop;
+    coarsest_self_mul(cop, out, in, 0, cop.V(), false);
+    coarsest_hop(cop, out, in, 0, cop.V(), -1.0, true);
+  }
   else lv_[l]->cop.apply(out, in, st_);
+}
+
+// ---- storage of the coarsest couplings (coarse_half.h) ------------------------------------------------
+template <typename T>
+void Multigrid<T>::set_coarse_storage(int bits) {
+  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "coarse storage: 32 bits, or 16 with the fp32 V-cycle");
+  coarse_bits_ = bits;
+  if (bits == 32 && half_.allocated()) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); half_.release(); }
+}
+template <typename T>
+void Multigrid<T>::coarsest_hop(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, double sign, bool accumulate) {
+  if constexpr (sizeof(T) == 4) { if (half_storage(cop)) { half_.hop(cop, out, in, s0, s1, sign, accumulate, st_); return; } }
+  cop.hop(out, in, s0, s1, sign, accumulate, st_);
+}
+template <typename T>
+void Multigrid<T>::coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse) {
+  if constexpr (sizeof(T) == 4) { if (half_storage(cop)) { half_.self_mul(cop, out, in, s0, s1, inverse, st_); return; } }
+  cop.self_mul(out, in, s0, s1, inverse, st_);
 }
 template <typename T> void Multigrid<T>::smoother(int l, T* phi, T* Dphi, const T* eta, int cycles, int res) {
   if (par_.method == 4) {
@@ -350,15 +374,30 @@ void Multigrid<T>::gmres_smoother(int l, T* phi, const T* eta, int cycles, int r
   }
 }
 
+template <typename T>
+void Multigrid<T>::coarsest_hop_parity(T* out, const T* in, int parity, double sign, bool accumulate) {
+  DDAMG_REQUIRE(par_.odd_even && (parity == 0 || parity == 1), "coarsest hopping term by parity: odd_even = 1, parity 0 or 1");
+  const CoarseOp<T>& cop = lv_.back()->cop;
+  const int Ve = cop.V() / 2;
+  coarsest_hop(cop, out, in, parity ? Ve : 0, parity ? cop.V() : Ve, sign, accumulate);
+}
+template <typename T>
+void Multigrid<T>::coarsest_self_mul_parity(T* out, const T* in, int parity, bool inverse) {
+  DDAMG_REQUIRE(par_.odd_even && (parity == 0 || parity == 1), "coarsest self coupling by parity: odd_even = 1, parity 0 or 1");
+  const CoarseOp<T>& cop = lv_.back()->cop;
+  const int Ve = cop.V() / 2;
+  coarsest_self_mul(cop, out, in, parity ? Ve : 0, parity ? cop.V() : Ve, inverse);
+}
+
 // ---- coarsest level: odd-even Schur complement solve ----------------------------------------------
 // S = D_ee - D_eo D_oo^-1 D_oe  on the even sites (coarse_apply_schur_complement_PRECISION)
 template <typename T>
 void Multigrid<T>::schur_on(const CoarseOp<T>& cop, int V, T* t0, T* t1, T* out, const T* in) {
   const int Ve = V / 2;
-  cop.self_mul(out, in, 0, Ve, false, st_);        // out_e = D_ee in_e
-  cop.hop(t0, in, Ve, V, -1.0, false, st_);        // tmp0_o = -H_oe in_e   (= D_oe in_e)
-  cop.self_mul(t1, t0, Ve, V, true, st_);          // tmp1_o = D_oo^-1 tmp0_o
-  cop.hop(out, t1, 0, Ve, +1.0, true, st_);        // out_e += H_eo tmp1_o  (= -D_eo tmp1_o)
+  coarsest_self_mul(cop, out, in, 0, Ve, false);        // out_e = D_ee in_e
+  coarsest_hop(cop, t0, in, Ve, V, -1.0, false);        // tmp0_o = -H_oe in_e   (= D_oe in_e)
+  coarsest_self_mul(cop, t1, t0, Ve, V, true);          // tmp1_o = D_oo^-1 tmp0_o
+  coarsest_hop(cop, out, t1, 0, Ve, +1.0, true);        // out_e += H_eo tmp1_o  (= -D_eo tmp1_o)
 }
 template <typename T>
 void Multigrid<T>::schur(T* out, const T* in) {
@@ -385,20 +424,20 @@ int Multigrid<T>::coarse_solve() {
     comm_allgather(comm_, b, G.raw, sizeof(T) * row * (size_t)G.V_local, st_);
     T *gx = G.gm.x, *gb = G.gm.b;
     gather_rows<T>(gb, G.raw, G.d_g2d, Vg, row, st_);
-    G.cop.self_mul(gx, gb, Vge, Vg, true, st_);
-    G.cop.hop(gb, gx, 0, Vge, +1.0, true, st_);
+    coarsest_self_mul(G.cop, gx, gb, Vge, Vg, true);
+    coarsest_hop(G.cop, gb, gx, 0, Vge, +1.0, true);
     const int it = G.gm.solve();
-    G.cop.hop(gb, gx, Vge, Vg, +1.0, true, st_);
-    G.cop.self_mul(gx, gb, Vge, Vg, true, st_);
+    coarsest_hop(G.cop, gb, gx, Vge, Vg, +1.0, true);
+    coarsest_self_mul(G.cop, gx, gb, Vge, Vg, true);
     gather_rows<T>(x, gx, G.d_d2g, G.V_local, row, st_);
     coarse_iter_count += it;
     return it;
   }
-  lv.cop.self_mul(x, b, Ve, V, true, st_);          // x_o = D_oo^-1 b_o
-  lv.cop.hop(b, x, 0, Ve, +1.0, true, st_);         // b_e <- b_e - D_eo x_o
+  coarsest_self_mul(lv.cop, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
+  coarsest_hop(lv.cop, b, x, 0, Ve, +1.0, true);    // b_e <- b_e - D_eo x_o
   int it = lv.gm.solve();                           // S x_e = b_e  to coarse_tol
-  lv.cop.hop(b, x, Ve, V, +1.0, true, st_);         // b_o <- b_o - D_oe x_e
-  lv.cop.self_mul(x, b, Ve, V, true, st_);          // x_o = D_oo^-1 b_o
+  coarsest_hop(lv.cop, b, x, Ve, V, +1.0, true);    // b_o <- b_o - D_oe x_e
+  coarsest_self_mul(lv.cop, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
   coarse_iter_count += it;
   return it;
 }
@@ -830,6 +869,7 @@ void Multigrid<T>::initial_setup() { setup_times.clear(); initial_setup_from(0);
 template <typename T>
 void Multigrid<T>::initial_setup_from(int l0) {
   // method_setup -> next_level_setup -> interpolation_PRECISION_define -> coarse_grid_correction_PRECISION_setup
+  const SetupStorage fp32_couplings(coarse_bits_);
   const int L = num_levels();
   if (l0 == 0) p_orthonormal_ = true;
   for (int l = l0; l + 1 < L; l++) {
@@ -1008,6 +1048,7 @@ void Multigrid<T>::bootstrap(int l, int iters) {
 template <typename T>
 void Multigrid<T>::iterative_setup(int iters) {
   if (iters <= 0) return;
+  const SetupStorage fp32_couplings(coarse_bits_);
   set_kcycle_tol(par_.coarse_tol);   // src/setup_generic.c:447-449
   bootstrap(0, iters);
   set_kcycle_tol(par_.kcycle_tol);

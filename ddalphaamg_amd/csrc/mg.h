@@ -16,6 +16,7 @@
 #include "coarse_mg.h"
 #include "coarse_lockstep.h"
 #include "coarse_multi.h"
+#include "coarse_half.h"
 #include "krylov.h"
 #include "../../include/ddamg_hip.h"
 #include <memory>
@@ -115,6 +116,15 @@ class Multigrid {
   bool level1_vcycle_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols);
   bool level1_kcycle_many(T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters);
   int kcycle_solve(int l);                                       // the K-cycle FGMRES of level l on level(l).gm.b -> gm.x, one vector
+  // ---- couplings of the coarsest level in 16-bit storage (coarse_half.h; fp32 V-cycle, odd-even, coarsest level on one process) ----
+  // bits 32 or 16: what the one-right-hand-side coarsest Schur complement and apply_op on the coarsest level read.  32 frees the
+  // 16-bit copy.  The setup phases run with 32 whatever the setting (SetupStorage), so the hierarchy never depends on it.
+  void set_coarse_storage(int bits);
+  int coarse_storage() const { return coarse_bits_; }
+  // the two products the coarsest Schur complement is made of, on the sites of one parity (0: even, 1: odd) of the parity-ordered
+  // coarsest level, in the storage that is set: CoarseOp::hop / self_mul over that half of the sites (ddamg_hip_coarse_hop, ..._self_mul)
+  void coarsest_hop_parity(T* out, const T* in, int parity, double sign, bool accumulate);
+  void coarsest_self_mul_parity(T* out, const T* in, int parity, bool inverse);
 
   int num_levels() const { return (int)lv_.size(); }
   MGLevel<T>& level(int l) { return *lv_[l]; }
@@ -145,6 +155,18 @@ class Multigrid {
   DeviceBuffer<T> cwork_;    // coarse work space (5 vectors of the largest coarse level)
 
   GatheredCoarsest<T> gath_;
+  int coarse_bits_ = 32;
+  CoarseHalf half_;                 // the 16-bit copy of the coarsest couplings: allocated by its first use, never with coarse_bits_ == 32
+  bool half_storage(const CoarseOp<T>& cop) const { return sizeof(T) == 4 && coarse_bits_ == 16 && !cop.distributed(); }
+  // CoarseOp::hop / self_mul of the coarsest level in the storage that is set
+  void coarsest_hop(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, double sign, bool accumulate);
+  void coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse);
+  // 32-bit storage for the lifetime of the object (a setup phase), the setting restored afterwards
+  struct SetupStorage {
+    int& bits; const int saved;
+    explicit SetupStorage(int& b) : bits(b), saved(b) { bits = 32; }
+    ~SetupStorage() { bits = saved; }
+  };
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)
   CoarseMulti multi1_;              // three levels: the intermediate level for all test vectors at once (coarse_multi.h)
   void ensure_lockstep();

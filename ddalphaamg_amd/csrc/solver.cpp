@@ -36,7 +36,7 @@ static void ensure_mg(ddamg_hip_ctx* c) {
   if (c->par.mixed_precision == 0) {
     if (!c->mg64) { c->mg64.reset(new Multigrid<double>(c->par, c->knobs, geoms, &c->fop64, c->stream)); c->mg64->set_comm(c->comm); }
   } else {
-    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, c->knobs, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); }
+    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, c->knobs, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); c->mg32->set_coarse_storage(c->coarse_storage_bits); }
   }
 }
 
@@ -458,6 +458,30 @@ int ddamg_hip_coarse_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip
   check_vec(c, out, out->level); check_vec(c, in, in->level);
   if (c->mg32) c->mg32->apply_op(out->level, (float*)out->data.get(), (const float*)in->data.get());
   else c->mg64->apply_op(out->level, (double*)out->data.get(), (const double*)in->data.get());
+  DDAMG_API_END
+}
+
+int ddamg_hip_coarse_hop(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, double sign, int accumulate) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const int lc = c->par.num_levels - 1;
+  check_vec(c, out, lc); check_vec(c, in, lc);
+  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place hopping term is not supported");
+  if (c->mg32) c->mg32->coarsest_hop_parity((float*)out->data.get(), (const float*)in->data.get(), parity, sign, accumulate != 0);
+  else c->mg64->coarsest_hop_parity((double*)out->data.get(), (const double*)in->data.get(), parity, sign, accumulate != 0);
+  DDAMG_API_END
+}
+
+int ddamg_hip_coarse_self_mul(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, int inverse) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const int lc = c->par.num_levels - 1;
+  check_vec(c, out, lc); check_vec(c, in, lc);
+  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place self coupling is not supported");
+  if (c->mg32) c->mg32->coarsest_self_mul_parity((float*)out->data.get(), (const float*)in->data.get(), parity, inverse != 0);
+  else c->mg64->coarsest_self_mul_parity((double*)out->data.get(), (const double*)in->data.get(), parity, inverse != 0);
   DDAMG_API_END
 }
 

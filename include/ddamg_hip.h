@@ -172,8 +172,28 @@ int ddamg_hip_restrict(ddamg_hip_ctx* ctx, ddamg_hip_vec* coarse, const ddamg_hi
 int ddamg_hip_interpolate(ddamg_hip_ctx* ctx, ddamg_hip_vec* fine, const ddamg_hip_vec* coarse, int add);
 /* replaces apply_coarse_operator_PRECISION (src/coarse_operator_generic.c:383-394) */
 int ddamg_hip_coarse_apply(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in);
+/* The two products the coarsest odd-even Schur complement is made of (coarse_hopping_term / coarse_n_hopping_term and
+ * coarse_diag_ee / coarse_diag_oo_inv, src/coarse_oddeven_generic.c:123-198, 447-729), on the sites of one parity of the coarsest
+ * level (0: even, 1: odd; odd_even == 1), in the coarse storage that is set:
+ *   hop:      out(x) = [accumulate ? out(x) : 0] + sign * (sum of the eight hopping terms of `in`)(x)    -- a "half hopping term"
+ *   self_mul: out(x) = M0(x) in(x), or M0(x)^-1 in(x) with inverse != 0
+ * The sites of the other parity in `out` are left as they are.  For measurements and kernel tests (tools/coarse_half_bench.py). */
+int ddamg_hip_coarse_hop(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, double sign, int accumulate);
+int ddamg_hip_coarse_self_mul(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, int inverse);
 /* replaces coarse_solve_odd_even_PRECISION (src/coarse_oddeven_generic.c:1139-1159) */
 int ddamg_hip_coarse_solve(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* b, int* iterations);
+/* Storage of the coarsest level's couplings for the solve: bits = 32 (default) or 16.  With 16 the one-right-hand-side coarsest
+ * odd-even solve (ddamg_hip_coarse_solve, and with it every V-cycle, K-cycle and ddamg_hip_solve) and ddamg_hip_coarse_apply on
+ * coarsest-level vectors read a copy of the couplings and of the inverted self couplings that holds one fp16 pair (re, im) per
+ * element and one fp32 scale per matrix; vectors and accumulation stay fp32.  The copy is made by its first use, follows every
+ * change of the operator by itself (ddamg_hip_shift_mass, ddamg_hip_scale_clover, ddamg_hip_setup_update,
+ * ddamg_hip_set_coarse_operator*), and is freed by setting 32 again.  ddamg_hip_setup, ddamg_hip_setup_at_mass and
+ * ddamg_hip_setup_update always run on the 32-bit couplings: the hierarchy does not depend on the setting.  Callable at any time
+ * after ddamg_hip_create; the initial value is 32, or 16 under DDAMG_COARSE_HALF=1 where the context can carry it.  Returns
+ * non-zero, with the storage unchanged, if bits is neither 16 nor 32, and for 16 on a context without an fp32 multigrid hierarchy
+ * (mixed_precision == 0, fewer than two levels, method 5), with odd_even == 0, or whose coarsest level is decomposed over
+ * processes and not gathered (gather_coarsest).  No counterpart in the reference. */
+int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* ctx, int bits);
 /* the same for ncols <= 32 right-hand sides at once: ncols independent GMRES recurrences advanced in lockstep, the coarse
  * operator applied to all columns on the matrix cores (v_mfma_f32_16x16x4_f32), as the bootstrap setup runs the coarsest-level
  * solves of its Nvec test vectors (the reference solves them one by one, src/setup_generic.c:441-503).  fp32 V-cycle, single
