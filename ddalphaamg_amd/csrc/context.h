@@ -71,6 +71,8 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   // bits per real of the coarsest couplings the solve reads, 32 or 16 (ddamg_hip_set_coarse_storage; initial value from
   // knobs.coarse_half); handed to mg32 when the hierarchy is created
   int coarse_storage_bits = 32;
+  // the same for the fine level's interpolation operator (ddamg_hip_set_transfer_storage; knobs.transfer_half)
+  int transfer_storage_bits = 32;
   // outer FGMRES (fp64) and its workspace
   ddamg::Gmres<double> outer;
   ddamg::ReduceWork rw_outer;

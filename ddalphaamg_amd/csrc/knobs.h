@@ -51,6 +51,9 @@ struct Knobs {
   int coarse_apply_once_min_sites = 2048;   // DDAMG_COARSE_APPLY_ONCE_MIN_SITES: lattices from this size on read every link once (CoarseOp<T>::apply)
   bool coarse_half = false;                 // DDAMG_COARSE_HALF=1: a context starts with the coarsest couplings in 16-bit storage (ddamg_hip_set_coarse_storage)
 
+  // ---- transfers of the fine level ----
+  bool transfer_half = false;               // DDAMG_TRANSFER_HALF=1: a context starts with the fine level's interpolation operator in 16-bit storage (ddamg_hip_set_transfer_storage)
+
   // ---- Krylov solvers ----
   bool pipelined_arnoldi = false;          // DDAMG_PIPELINED_ARNOLDI: the reference's -DPIPELINED_ARNOLDI build, at run time (coarsest level)
   bool single_allreduce_arnoldi = false;   // DDAMG_SINGLE_ALLREDUCE_ARNOLDI: the reference's -DSINGLE_ALLREDUCE_ARNOLDI build, at run time (every GMRES)
@@ -85,6 +88,7 @@ struct Knobs {
     k.coarse_sap_unfused = present("DDAMG_COARSE_SAP_UNFUSED");
     if (const OptionalInt v = integer("DDAMG_COARSE_APPLY_ONCE_MIN_SITES"); v.set) k.coarse_apply_once_min_sites = v.value;
     if (const OptionalInt v = integer("DDAMG_COARSE_HALF"); v.set) k.coarse_half = v.value != 0;
+    if (const OptionalInt v = integer("DDAMG_TRANSFER_HALF"); v.set) k.transfer_half = v.value != 0;
     k.pipelined_arnoldi = present("DDAMG_PIPELINED_ARNOLDI");
     k.single_allreduce_arnoldi = present("DDAMG_SINGLE_ALLREDUCE_ARNOLDI");
     k.comm_cus = integer("DDAMG_COMM_CUS");

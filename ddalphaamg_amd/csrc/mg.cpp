@@ -283,11 +283,20 @@ template <typename T> void Multigrid<T>::smoother(int l, T* phi, T* Dphi, const 
   if (l == 0) lv_[0]->fsap.smooth(phi, Dphi, eta, cycles, res, st_);
   else lv_[l]->csap.smooth(phi, Dphi, eta, cycles, res, st_);
 }
+// ---- storage of the fine level's interpolation operator (transfer_half.h) -----------------------------
+template <typename T>
+void Multigrid<T>::set_transfer_storage(int bits) {
+  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "transfer storage: 32 bits, or 16 with the fp32 V-cycle");
+  transfer_bits_ = bits;
+  if (bits == 32 && thalf_.allocated()) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); thalf_.release(); }
+}
 template <typename T> void Multigrid<T>::restrict_to(int l, T* phi_c, const T* phi) {
+  if constexpr (sizeof(T) == 4) { if (l == 0 && transfer_bits_ == 16) { thalf_.restrict_to(lv_[0]->fip, phi_c, phi, st_); return; } }
   if (l == 0) lv_[0]->fip.restrict_to(phi_c, phi, st_);
   else lv_[l]->cip.restrict_to(phi_c, phi, st_);
 }
 template <typename T> void Multigrid<T>::interpolate(int l, T* phi, const T* phi_c, bool add) {
+  if constexpr (sizeof(T) == 4) { if (l == 0 && transfer_bits_ == 16) { thalf_.interpolate(lv_[0]->fip, phi, phi_c, add, st_); return; } }
   if (l == 0) lv_[0]->fip.interpolate(phi, phi_c, add, st_);
   else lv_[l]->cip.interpolate(phi, phi_c, add, st_);
 }
@@ -869,7 +878,7 @@ void Multigrid<T>::initial_setup() { setup_times.clear(); initial_setup_from(0);
 template <typename T>
 void Multigrid<T>::initial_setup_from(int l0) {
   // method_setup -> next_level_setup -> interpolation_PRECISION_define -> coarse_grid_correction_PRECISION_setup
-  const SetupStorage fp32_couplings(coarse_bits_);
+  const SetupStorage fp32_storage(*this);
   const int L = num_levels();
   if (l0 == 0) p_orthonormal_ = true;
   for (int l = l0; l + 1 < L; l++) {
@@ -1048,7 +1057,7 @@ void Multigrid<T>::bootstrap(int l, int iters) {
 template <typename T>
 void Multigrid<T>::iterative_setup(int iters) {
   if (iters <= 0) return;
-  const SetupStorage fp32_couplings(coarse_bits_);
+  const SetupStorage fp32_storage(*this);
   set_kcycle_tol(par_.coarse_tol);   // src/setup_generic.c:447-449
   bootstrap(0, iters);
   set_kcycle_tol(par_.kcycle_tol);

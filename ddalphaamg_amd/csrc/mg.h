@@ -17,6 +17,7 @@
 #include "coarse_lockstep.h"
 #include "coarse_multi.h"
 #include "coarse_half.h"
+#include "transfer_half.h"
 #include "krylov.h"
 #include "../../include/ddamg_hip.h"
 #include <memory>
@@ -125,6 +126,12 @@ class Multigrid {
   // coarsest level, in the storage that is set: CoarseOp::hop / self_mul over that half of the sites (ddamg_hip_coarse_hop, ..._self_mul)
   void coarsest_hop_parity(T* out, const T* in, int parity, double sign, bool accumulate);
   void coarsest_self_mul_parity(T* out, const T* in, int parity, bool inverse);
+  // ---- the fine level's interpolation operator in 16-bit storage (transfer_half.h; fp32 V-cycle) ----
+  // bits 32 or 16: what restrict_to(0, ...) and interpolate(0, ...) read.  32 frees the 16-bit copy.  The many-vector transfers
+  // (restrict_batch*, interpolate_batch, the Galerkin construction) and the intermediate levels read the fp32 P whatever the
+  // setting, and so does every setup phase (SetupStorage).
+  void set_transfer_storage(int bits);
+  int transfer_storage() const { return transfer_bits_; }
 
   int num_levels() const { return (int)lv_.size(); }
   MGLevel<T>& level(int l) { return *lv_[l]; }
@@ -161,11 +168,15 @@ class Multigrid {
   // CoarseOp::hop / self_mul of the coarsest level in the storage that is set
   void coarsest_hop(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, double sign, bool accumulate);
   void coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse);
-  // 32-bit storage for the lifetime of the object (a setup phase), the setting restored afterwards
+  int transfer_bits_ = 32;
+  TransferHalf thalf_;              // the 16-bit copy of the fine level's P: allocated by its first use, never with transfer_bits_ == 32
+  // 32-bit storage of both for the lifetime of the object (a setup phase), the settings restored afterwards
   struct SetupStorage {
-    int& bits; const int saved;
-    explicit SetupStorage(int& b) : bits(b), saved(b) { bits = 32; }
-    ~SetupStorage() { bits = saved; }
+    int& coarse; int& transfer; const int saved_coarse, saved_transfer;
+    explicit SetupStorage(Multigrid& mg) : coarse(mg.coarse_bits_), transfer(mg.transfer_bits_), saved_coarse(mg.coarse_bits_), saved_transfer(mg.transfer_bits_) {
+      coarse = 32; transfer = 32;
+    }
+    ~SetupStorage() { coarse = saved_coarse; transfer = saved_transfer; }
   };
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)
   CoarseMulti multi1_;              // three levels: the intermediate level for all test vectors at once (coarse_multi.h)

@@ -46,6 +46,10 @@ struct Interpolation {
   DeviceBuffer<T> P;       // orthonormalised interpolation vectors, aggregate by aggregate: [aggregate][nvec][24 * plane_sites()]
   DeviceBuffer<int> agg_csite; // [num_aggs] coarse-level site index of every aggregate
   const Knobs* knobs = nullptr;   // the context's switches (alloc): gs_workgroup
+  // moves whenever P is written (orthonormalize, set_column): what a copy of P in another format compares its own stamp with
+  // (transfer_half.h)
+  unsigned version() const { return version_; }
+  unsigned version_ = 0;
   void alloc(const Geometry& g, const Geometry& gc, int nvec_, const Knobs& knobs_);
   T* test_vector(int j) const { return tv + pstride * j; }
   // column j of P from / into a vector in lattice order (import, export, the Galerkin construction's fall-back paths)

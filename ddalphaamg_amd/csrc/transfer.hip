@@ -563,6 +563,7 @@ __global__ __launch_bounds__(256) void p_columns_kernel(T* __restrict__ P, T* __
 }
 template <typename T>
 void Interpolation<T>::set_column(int j, const T* vec, hipStream_t st) {
+  version_++;
   hipLaunchKernelGGL((p_columns_kernel<T, true>), dim3(num_aggs, 1), dim3(256), 0, st, P, const_cast<T*>(vec), (size_t)0, j, nvec, V, agg_sites, plane_sites());
   DDAMG_HIP_CHECK(hipGetLastError());
 }
@@ -780,6 +781,7 @@ template <typename T>
 void Interpolation<T>::orthonormalize(hipStream_t st) {
   // (P <- tv is part of the kernel: a column is read from the test vectors in lattice order and written, orthonormalised, into
   // its aggregate-major place; the earlier columns it is projected on are read from there)
+  version_++;
   const int nt = wg_threads(agg_sites);
   const int spt = (agg_sites + nt - 1) / nt;
   // columns per pass: 2 (measured at 32^4, Nvec 24: 6.8 ms with one column, 4.3 ms with two, 4.5 ms with four -- 190 registers,

@@ -194,6 +194,18 @@ int ddamg_hip_coarse_solve(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip
  * (mixed_precision == 0, fewer than two levels, method 5), with odd_even == 0, or whose coarsest level is decomposed over
  * processes and not gathered (gather_coarsest).  No counterpart in the reference. */
 int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* ctx, int bits);
+/* Storage of the fine level's interpolation operator P for the solve: bits = 32 (default) or 16.  With 16 ddamg_hip_restrict and
+ * ddamg_hip_interpolate on fine-level vectors (and with them every V-cycle, K-cycle, ddamg_hip_preconditioner, ddamg_hip_solve
+ * and ddamg_hip_solve_vec) read a copy of P that holds one fp16 number per real and one fp32 scale per aggregate, vector and
+ * chirality; vectors and accumulation stay fp32.  The transfers of the intermediate levels stay fp32.  The copy costs half the
+ * bytes of P again, is made by its first use, follows every change of P by itself (ddamg_hip_setup, ddamg_hip_setup_update,
+ * ddamg_hip_set_test_vectors, ddamg_hip_set_interpolation), and is freed by setting 32 again.  ddamg_hip_setup,
+ * ddamg_hip_setup_at_mass and ddamg_hip_setup_update always run on the 32-bit P: the hierarchy does not depend on the setting.
+ * Callable at any time after ddamg_hip_create; the initial value is 32, or 16 under DDAMG_TRANSFER_HALF=1 where the context can
+ * carry it.  Returns non-zero, with the storage unchanged, if bits is neither 16 nor 32, and for 16 on a context without an fp32
+ * multigrid hierarchy (mixed_precision == 0, fewer than two levels, a method outside 1-4).  Process grids are not refused:
+ * aggregates never cross a process boundary and the two kernels are local.  No counterpart in the reference. */
+int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* ctx, int bits);
 /* the same for ncols <= 32 right-hand sides at once: ncols independent GMRES recurrences advanced in lockstep, the coarse
  * operator applied to all columns on the matrix cores (v_mfma_f32_16x16x4_f32), as the bootstrap setup runs the coarsest-level
  * solves of its Nvec test vectors (the reference solves them one by one, src/setup_generic.c:441-503).  fp32 V-cycle, single
