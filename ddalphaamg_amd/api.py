@@ -124,6 +124,7 @@ def load_library():
         "ddamg_hip_coarse_solve": [vp, vp, vp, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_set_coarse_storage": [vp, ctypes.c_int],
         "ddamg_hip_set_transfer_storage": [vp, ctypes.c_int],
+        "ddamg_hip_set_intermediate_storage": [vp, ctypes.c_int],
         "ddamg_hip_coarse_hop": [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_coarse_self_mul": [vp, vp, vp, ctypes.c_int, ctypes.c_int],
         "ddamg_hip_coarse_solve_many": [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int)],
@@ -467,6 +468,11 @@ class Context:
         aggregate, vector and chirality, fp32 accumulation); raises DDAMGError where the context cannot carry 16 (see
         include/ddamg_hip.h)"""
         _check(self._lib.ddamg_hip_set_transfer_storage(self._h, int(bits)))
+
+    def set_intermediate_storage(self, bits):
+        """storage of the couplings of every intermediate level for the solve: 32 (default) or 16 (fp16 pairs + one fp32 scale per
+        matrix, fp32 accumulation); raises DDAMGError where the context cannot carry 16 (see include/ddamg_hip.h)"""
+        _check(self._lib.ddamg_hip_set_intermediate_storage(self._h, int(bits)))
 
     def coarse_hop(self, out, inp, parity, sign=1.0, accumulate=False):
         """a half hopping term of the coarsest level: out (+)= sign * hopping terms of inp on the even (0) / odd (1) sites"""

@@ -1,6 +1,7 @@
 // capi.cpp -- implementation of the thin C-ABI (include/ddamg_hip.h).
 #include "context.h"
 #include "gauge.h"
+#include "intermediate_refusal.h"
 #include <cstring>
 #include <string>
 
@@ -48,6 +49,13 @@ static const char* transfer_half_refusal(const ddamg_hip_ctx* c) {
   if (c->par.num_levels < 2 || c->par.method < 1 || c->par.method > 4) return "16-bit transfer storage needs a multigrid hierarchy (two levels or more, method 1 to 4)";
   if (c->par.mixed_precision == 0) return "16-bit transfer storage needs the fp32 V-cycle (mixed_precision 1 or 2)";
   return nullptr;
+}
+
+// why this context cannot keep the couplings of its intermediate levels in 16 bits (nullptr: it can)
+static const char* intermediate_half_refusal(const ddamg_hip_ctx* c) {
+  bool decomposed = false;
+  for (int l = 1; l + 1 < c->par.num_levels; l++) decomposed = decomposed || c->levels[l]->geom.distributed();
+  return ddamg::intermediate_half_refusal(c->par.num_levels, c->par.method, c->par.mixed_precision, decomposed);
 }
 
 extern "C" {
@@ -140,6 +148,7 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
   }
   if (c->knobs.coarse_half && coarse_half_refusal(c.get()) == nullptr) c->coarse_storage_bits = 16;
   if (c->knobs.transfer_half && transfer_half_refusal(c.get()) == nullptr) c->transfer_storage_bits = 16;
+  if (c->knobs.intermediate_half && intermediate_half_refusal(c.get()) == nullptr) c->intermediate_storage_bits = 16;
   srand(1000u * (unsigned)c->levels[0]->geom.rank);  // reference: srand( 1000*g.my_rank ) unless "randomize test vectors" (src/init.c:870-873)
   *out = c.release();
   DDAMG_API_END
@@ -176,6 +185,17 @@ int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* c, int bits) {
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   if (c->mg32) c->mg32->set_transfer_storage(bits);
   c->transfer_storage_bits = bits;
+  DDAMG_API_END
+}
+
+int ddamg_hip_set_intermediate_storage(ddamg_hip_ctx* c, int bits) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_REQUIRE(bits == 16 || bits == 32, "intermediate storage: bits must be 16 or 32");
+  if (bits == 16) if (const char* why = intermediate_half_refusal(c)) throw std::runtime_error(why);
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  if (c->mg32) c->mg32->set_intermediate_storage(bits);
+  c->intermediate_storage_bits = bits;
   DDAMG_API_END
 }
 

@@ -31,6 +31,11 @@ struct CoarseHalfDev {
   size_t msize;          // __half2 per matrix = nt * nt * 64
 };
 
+// the copy's build kernel (coarse_half.hip), shared with the intermediate levels (coarse_half_level.h): matrices m0 .. m0 + count - 1
+// of every site (0-4 the couplings, 5 the inverted self coupling) from `op` into Mh / Minvh in the layout above, their scales to
+// scale[site * 6 + m].  Minvh is read only for m = 5.
+void coarse_half_build(__half2* Mh, __half2* Minvh, float* scale, const CoarseOpDev<float>& op, int m0, int count, hipStream_t st);
+
 class CoarseHalf {
  public:
   // the two products of the coarsest Schur complement, with the signature and semantics of CoarseOp::hop / self_mul; `op` is

@@ -384,8 +384,19 @@ void CoarseSap<T>::setup(const Geometry& g, const CoarseOp<T>* op, int block_ite
 }
 
 template <typename T>
-void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st) {
+void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st, CoarseHalfLevel* half) {
   DDAMG_REQUIRE(op_ != nullptr, "coarse SAP smoother not set up");
+  DDAMG_REQUIRE(half == nullptr || sizeof(T) == 4, "coarse SAP smoother: 16-bit couplings need fp32 vectors");
+  // the two products of the operator in the storage the caller chose
+  const auto apply_masked = [&](T* out, const T* in, const int* site_list, int nsites, const unsigned char* dir_mask, bool mask_invert, double sign_self,
+                                double sign_hop, bool accumulate) {
+    if constexpr (sizeof(T) == 4) { if (half) { half->apply_masked(*op_, out, in, site_list, nsites, dir_mask, mask_invert, sign_self, sign_hop, accumulate, st); return; } }
+    op_->apply_masked(out, in, site_list, nsites, dir_mask, mask_invert, sign_self, sign_hop, accumulate, st);
+  };
+  const auto block_minres = [&](const int* blocks, int nblocks, double eps) {
+    if constexpr (sizeof(T) == 4) { if (half) return half->block_minres(*op_, x, r, latest, blocks, nblocks, plan_, block_iter_, eps, st); }
+    return op_->block_minres(x, r, latest, blocks, nblocks, plan_, block_iter_, eps, st);
+  };
   DDAMG_REQUIRE(phi != eta, "smoother: phi and eta must differ");
   const size_t nel = (size_t)V_ * n_ * 2;
   const View all = whole(nel);
@@ -416,19 +427,19 @@ void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hi
       } else if (full) {
         // r_b = eta_b - (D x)_b   (coarse_block_operator + coarse_block_boundary_op); the additive method takes the
         // start vector (kept in latest), the blocks being solved side by side
-        op_->apply_masked(tmp, schedule_ == ADDITIVE ? latest : x, d_sites_[li], nblk_[li] * BS_, nullptr, false, 1.0, -1.0, false, st);
+        apply_masked(tmp, schedule_ == ADDITIVE ? latest : x, d_sites_[li], nblk_[li] * BS_, nullptr, false, 1.0, -1.0, false);
         hipLaunchKernelGGL((block_ew_kernel<T, BOP_ETA_MINUS>), dim3(nblk_[li]), dim3(256), 0, st, r, eta, tmp, d_blocks_[li], blen);
       } else {
         // r_b -= D_{b,ext} latest  (n_coarse_block_boundary_op)
-        if (nblk_[lj] > 0) op_->apply_masked(r, latest, d_sites_[lj], nblk_[lj] * BS_, d_blk_face_, false, 0.0, +1.0, true, st);
+        if (nblk_[lj] > 0) apply_masked(r, latest, d_sites_[lj], nblk_[lj] * BS_, d_blk_face_, false, 0.0, +1.0, true);
       }
       // local_minres on every block of this colour (with one colour all reads of the previous generation of updates are
       // done by now, so the same buffer takes the new one)
-      if (!op_->block_minres(x, r, latest, d_blocks_[li], nblk_[li], plan_, block_iter_, eps, st)) {
+      if (!block_minres(d_blocks_[li], nblk_[li], eps)) {
         // step-by-step form (blocks that do not fit the fused kernel)
         hipLaunchKernelGGL((block_ew_kernel<T, BOP_ZERO>), dim3(nblk_[li]), dim3(256), 0, st, latest, (const T*)nullptr, (const T*)nullptr, d_blocks_[li], blen);
         for (int it = 0; it < block_iter_; it++) {
-          op_->apply_masked(tmp, r, d_sites_[li], nblk_[li] * BS_, d_blk_face_, true, 1.0, -1.0, false, st);   // Dr = D_block r
+          apply_masked(tmp, r, d_sites_[li], nblk_[li] * BS_, d_blk_face_, true, 1.0, -1.0, false);   // Dr = D_block r
           hipLaunchKernelGGL(block_minres_kernel<T>, dim3(nblk_[li]), dim3(256), 0, st, latest, r, tmp, d_blocks_[li], blen / 2, eps);
         }
         hipLaunchKernelGGL((block_ew_kernel<T, BOP_ADD>), dim3(nblk_[li]), dim3(256), 0, st, x, latest, (const T*)nullptr, d_blocks_[li], blen);
@@ -439,7 +450,7 @@ void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hi
   vec_copy<T>(phi, x, all, st);
   if (Dphi != nullptr) {
     DDAMG_REQUIRE(schedule_ != SIXTEEN, "the sixteen-colour smoother does not return D*phi");
-    op_->apply_masked(r, latest, d_sites_[0], nblk_[0] * BS_, d_blk_face_, false, 0.0, +1.0, true, st);
+    apply_masked(r, latest, d_sites_[0], nblk_[0] * BS_, d_blk_face_, false, 0.0, +1.0, true);
     vec_minus<T>(Dphi, eta, r, all, st);
   }
 }

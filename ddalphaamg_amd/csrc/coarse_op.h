@@ -75,6 +75,10 @@ class CoarseOp {
   unsigned inverse_version() const { return inverse_version_; }   // moves with every compute_self_inverse()
   size_t msize() const { return msize_; }
   int nt() const { return nt_; }
+  const Knobs& knobs() const { return *knobs_; }
+  // [4][V][n] complex: the backward products between the two passes of apply(); allocated by its first use, shared with the
+  // 16-bit form of that apply (coarse_half_level.h)
+  T* backward_workspace() const { if (!bwd_) bwd_.alloc(4 * (size_t)V_ * n_ * 2); return bwd_; }
 
   // out = D_c in on all sites
   void apply(T* out, const T* in, hipStream_t st) const;

@@ -73,6 +73,8 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   int coarse_storage_bits = 32;
   // the same for the fine level's interpolation operator (ddamg_hip_set_transfer_storage; knobs.transfer_half)
   int transfer_storage_bits = 32;
+  // the same for the couplings of every intermediate level (ddamg_hip_set_intermediate_storage; knobs.intermediate_half)
+  int intermediate_storage_bits = 32;
   // outer FGMRES (fp64) and its workspace
   ddamg::Gmres<double> outer;
   ddamg::ReduceWork rw_outer;

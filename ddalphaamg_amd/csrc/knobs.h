@@ -50,6 +50,7 @@ struct Knobs {
   bool coarse_sap_unfused = false;          // DDAMG_COARSE_SAP_UNFUSED: the coarse Schwarz block solver step by step instead of fused
   int coarse_apply_once_min_sites = 2048;   // DDAMG_COARSE_APPLY_ONCE_MIN_SITES: lattices from this size on read every link once (CoarseOp<T>::apply)
   bool coarse_half = false;                 // DDAMG_COARSE_HALF=1: a context starts with the coarsest couplings in 16-bit storage (ddamg_hip_set_coarse_storage)
+  bool intermediate_half = false;           // DDAMG_INTERMEDIATE_HALF=1: a context starts with the intermediate levels' couplings in 16-bit storage (ddamg_hip_set_intermediate_storage)
 
   // ---- transfers of the fine level ----
   bool transfer_half = false;               // DDAMG_TRANSFER_HALF=1: a context starts with the fine level's interpolation operator in 16-bit storage (ddamg_hip_set_transfer_storage)
@@ -88,6 +89,7 @@ struct Knobs {
     k.coarse_sap_unfused = present("DDAMG_COARSE_SAP_UNFUSED");
     if (const OptionalInt v = integer("DDAMG_COARSE_APPLY_ONCE_MIN_SITES"); v.set) k.coarse_apply_once_min_sites = v.value;
     if (const OptionalInt v = integer("DDAMG_COARSE_HALF"); v.set) k.coarse_half = v.value != 0;
+    if (const OptionalInt v = integer("DDAMG_INTERMEDIATE_HALF"); v.set) k.intermediate_half = v.value != 0;
     if (const OptionalInt v = integer("DDAMG_TRANSFER_HALF"); v.set) k.transfer_half = v.value != 0;
     k.pipelined_arnoldi = present("DDAMG_PIPELINED_ARNOLDI");
     k.single_allreduce_arnoldi = present("DDAMG_SINGLE_ALLREDUCE_ARNOLDI");

@@ -28,6 +28,8 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
     if (d > 0) max_coarse = std::max(max_coarse, lv->nel);
     lv_.push_back(std::move(lv));
   }
+  ihalf_.resize(L);
+  for (int d = 1; d + 1 < L; d++) ihalf_[d].reset(new CoarseHalfLevel);
   for (int d = 0; d < L; d++) {
     MGLevel<T>& lv = *lv_[d];
     const Geometry& g = *lv.g;
@@ -254,6 +256,9 @@ template <typename T> void Multigrid<T>::apply_op(int l, T* out, const T* in) {
     coarsest_self_mul(cop, out, in, 0, cop.V(), false);
     coarsest_hop(cop, out, in, 0, cop.V(), -1.0, true);
   }
+  else if (CoarseHalfLevel* h = intermediate_half(l)) {
+    if constexpr (sizeof(T) == 4) h->apply(lv_[l]->cop, out, in, st_);
+  }
   else lv_[l]->cop.apply(out, in, st_);
 }
 
@@ -281,7 +286,18 @@ template <typename T> void Multigrid<T>::smoother(int l, T* phi, T* Dphi, const 
     return;
   }
   if (l == 0) lv_[0]->fsap.smooth(phi, Dphi, eta, cycles, res, st_);
-  else lv_[l]->csap.smooth(phi, Dphi, eta, cycles, res, st_);
+  else lv_[l]->csap.smooth(phi, Dphi, eta, cycles, res, st_, intermediate_half(l));
+}
+// ---- storage of the intermediate levels' couplings (coarse_half_level.h) --------------------------------
+template <typename T>
+void Multigrid<T>::set_intermediate_storage(int bits) {
+  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "intermediate storage: 32 bits, or 16 with the fp32 V-cycle");
+  intermediate_bits_ = bits;
+  if (bits == 32) {
+    bool any = false;
+    for (auto& h : ihalf_) any = any || (h && h->allocated());
+    if (any) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); for (auto& h : ihalf_) if (h) h->release(); }
+  }
 }
 // ---- storage of the fine level's interpolation operator (transfer_half.h) -----------------------------
 template <typename T>

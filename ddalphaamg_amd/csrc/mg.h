@@ -17,6 +17,7 @@
 #include "coarse_lockstep.h"
 #include "coarse_multi.h"
 #include "coarse_half.h"
+#include "coarse_half_level.h"
 #include "transfer_half.h"
 #include "krylov.h"
 #include "../../include/ddamg_hip.h"
@@ -132,6 +133,13 @@ class Multigrid {
   // setting, and so does every setup phase (SetupStorage).
   void set_transfer_storage(int bits);
   int transfer_storage() const { return transfer_bits_; }
+  // ---- the couplings of every intermediate level in 16-bit storage (coarse_half_level.h; fp32 V-cycle, methods 1-3, level on one process) ----
+  // bits 32 or 16: what apply_op(l, ...) and smoother(l, ...) read on the levels with depth > 0 that are not the coarsest (the
+  // K-cycle's operator, the Schwarz smoother's residual updates and its block solver).  One copy per such level, made by its
+  // first use; 32 frees them.  The many-vector paths (coarse_multi.h, *_many), the Galerkin construction and every setup phase
+  // (SetupStorage) read the fp32 couplings whatever the setting.
+  void set_intermediate_storage(int bits);
+  int intermediate_storage() const { return intermediate_bits_; }
 
   int num_levels() const { return (int)lv_.size(); }
   MGLevel<T>& level(int l) { return *lv_[l]; }
@@ -170,13 +178,21 @@ class Multigrid {
   void coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse);
   int transfer_bits_ = 32;
   TransferHalf thalf_;              // the 16-bit copy of the fine level's P: allocated by its first use, never with transfer_bits_ == 32
-  // 32-bit storage of both for the lifetime of the object (a setup phase), the settings restored afterwards
+  int intermediate_bits_ = 32;
+  std::vector<std::unique_ptr<CoarseHalfLevel>> ihalf_;   // per level: the 16-bit copy of an intermediate level's couplings (null elsewhere), allocated by its first use
+  // the copy that level l's products read in the storage that is set, or nullptr: the fp32 couplings
+  CoarseHalfLevel* intermediate_half(int l) const {
+    if (sizeof(T) != 4 || intermediate_bits_ != 16 || par_.method > 3 || !ihalf_[l] || lv_[l]->cop.distributed()) return nullptr;
+    return ihalf_[l].get();
+  }
+  // 32-bit storage of all three for the lifetime of the object (a setup phase), the settings restored afterwards
   struct SetupStorage {
-    int& coarse; int& transfer; const int saved_coarse, saved_transfer;
-    explicit SetupStorage(Multigrid& mg) : coarse(mg.coarse_bits_), transfer(mg.transfer_bits_), saved_coarse(mg.coarse_bits_), saved_transfer(mg.transfer_bits_) {
-      coarse = 32; transfer = 32;
+    int& coarse; int& transfer; int& intermediate; const int saved_coarse, saved_transfer, saved_intermediate;
+    explicit SetupStorage(Multigrid& mg) : coarse(mg.coarse_bits_), transfer(mg.transfer_bits_), intermediate(mg.intermediate_bits_),
+                                           saved_coarse(mg.coarse_bits_), saved_transfer(mg.transfer_bits_), saved_intermediate(mg.intermediate_bits_) {
+      coarse = 32; transfer = 32; intermediate = 32;
     }
-    ~SetupStorage() { coarse = saved_coarse; transfer = saved_transfer; }
+    ~SetupStorage() { coarse = saved_coarse; transfer = saved_transfer; intermediate = saved_intermediate; }
   };
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)
   CoarseMulti multi1_;              // three levels: the intermediate level for all test vectors at once (coarse_multi.h)

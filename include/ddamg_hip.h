@@ -206,6 +206,21 @@ int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* ctx, int bits);
  * multigrid hierarchy (mixed_precision == 0, fewer than two levels, a method outside 1-4).  Process grids are not refused:
  * aggregates never cross a process boundary and the two kernels are local.  No counterpart in the reference. */
 int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* ctx, int bits);
+/* Storage of the couplings of every intermediate level (depth > 0, not the coarsest) for the solve: bits = 32 (default) or 16.
+ * With 16 the operator of those levels (ddamg_hip_coarse_apply on their vectors, the K-cycle's FGMRES), the residual updates of
+ * their Schwarz smoother and its block solver (ddamg_hip_smoother on their vectors, and with them every V-cycle, K-cycle,
+ * ddamg_hip_preconditioner, ddamg_hip_solve and ddamg_hip_solve_vec) read a copy of the couplings that holds one fp16 pair
+ * (re, im) per element and one fp32 scale per matrix; vectors and accumulation stay fp32.  The many-vector paths of the
+ * intermediate level and its transfers stay fp32.  There is one copy per intermediate level; each costs half the bytes of the
+ * level's couplings again (about 3 GB at 64^4 with 16^4 x 48), is made by its first use, follows every change of the operator by
+ * itself (ddamg_hip_shift_mass, ddamg_hip_scale_clover, ddamg_hip_setup_update, ddamg_hip_set_coarse_operator_level), and is
+ * freed by setting 32 again.  ddamg_hip_setup, ddamg_hip_setup_at_mass and ddamg_hip_setup_update always run on the 32-bit
+ * couplings: the hierarchy does not depend on the setting.  Callable at any time after ddamg_hip_create; the initial value is
+ * 32, or 16 under DDAMG_INTERMEDIATE_HALF=1 where the context can carry it.  Returns non-zero, with the storage unchanged, if
+ * bits is neither 16 nor 32, and for 16 on a context with fewer than three levels, with a method outside 1-3 (the GMRES smoother
+ * of method 4 is not covered), with mixed_precision == 0, or with an intermediate level that is decomposed over processes.  No
+ * counterpart in the reference. */
+int ddamg_hip_set_intermediate_storage(ddamg_hip_ctx* ctx, int bits);
 /* the same for ncols <= 32 right-hand sides at once: ncols independent GMRES recurrences advanced in lockstep, the coarse
  * operator applied to all columns on the matrix cores (v_mfma_f32_16x16x4_f32), as the bootstrap setup runs the coarsest-level
  * solves of its Nvec test vectors (the reference solves them one by one, src/setup_generic.c:441-503).  fp32 V-cycle, single
