@@ -1,7 +1,7 @@
 // capi.cpp -- implementation of the thin C-ABI (include/ddamg_hip.h).
 #include "context.h"
 #include "gauge.h"
-#include "intermediate_refusal.h"
+#include "storage_refusal.h"
 #include <cstring>
 #include <string>
 
@@ -35,27 +35,26 @@ double* ddamg_hip_ctx::stage(size_t bytes) {
   return d_stage;
 }
 
-// why this context cannot keep its coarsest couplings in 16 bits (nullptr: it can)
-static const char* coarse_half_refusal(const ddamg_hip_ctx* c) {
-  if (c->par.num_levels < 2 || c->par.method < 1 || c->par.method > 4) return "16-bit coarse storage needs a multigrid hierarchy (two levels or more, method 1 to 4)";
-  if (c->par.mixed_precision == 0) return "16-bit coarse storage needs the fp32 V-cycle (mixed_precision 1 or 2)";
-  if (c->par.odd_even == 0) return "16-bit coarse storage is implemented for the odd-even coarsest solve (odd_even = 1)";
-  if (c->levels.back()->geom.distributed() && !c->par.gather_coarsest) return "16-bit coarse storage needs the coarsest level on one process (single process, or gather_coarsest)";
-  return nullptr;
-}
-
-// why this context cannot keep the fine level's interpolation operator in 16 bits (nullptr: it can)
-static const char* transfer_half_refusal(const ddamg_hip_ctx* c) {
-  if (c->par.num_levels < 2 || c->par.method < 1 || c->par.method > 4) return "16-bit transfer storage needs a multigrid hierarchy (two levels or more, method 1 to 4)";
-  if (c->par.mixed_precision == 0) return "16-bit transfer storage needs the fp32 V-cycle (mixed_precision 1 or 2)";
-  return nullptr;
-}
-
-// why this context cannot keep the couplings of its intermediate levels in 16 bits (nullptr: it can)
-static const char* intermediate_half_refusal(const ddamg_hip_ctx* c) {
+// why this context cannot keep what `kind` names in 16 bits (nullptr: it can): storage_refusal.h on the context's parameters
+static const char* storage_refusal(const ddamg_hip_ctx* c, StorageKind kind) {
+  const ddamg_hip_params& p = c->par;
+  if (kind == Coarse) return coarse_half_refusal(p.num_levels, p.method, p.mixed_precision, p.odd_even, c->levels.back()->geom.distributed(), p.gather_coarsest != 0);
+  if (kind == Transfer) return transfer_half_refusal(p.num_levels, p.method, p.mixed_precision);
   bool decomposed = false;
-  for (int l = 1; l + 1 < c->par.num_levels; l++) decomposed = decomposed || c->levels[l]->geom.distributed();
-  return ddamg::intermediate_half_refusal(c->par.num_levels, c->par.method, c->par.mixed_precision, decomposed);
+  for (int l = 1; l + 1 < p.num_levels; l++) decomposed = decomposed || c->levels[l]->geom.distributed();
+  return intermediate_half_refusal(p.num_levels, p.method, p.mixed_precision, decomposed);
+}
+
+// ddamg_hip_set_coarse_storage / _transfer_ / _intermediate_: name is the word their messages begin with
+static int set_storage(ddamg_hip_ctx* c, StorageKind kind, int bits, const char* name) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_REQUIRE(bits == 16 || bits == 32, (std::string(name) + " storage: bits must be 16 or 32").c_str());
+  if (bits == 16) if (const char* why = storage_refusal(c, kind)) throw std::runtime_error(why);
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  if (c->mg32) c->mg32->set_storage(kind, bits);
+  c->storage.bits[kind] = bits;
+  DDAMG_API_END
 }
 
 extern "C" {
@@ -146,9 +145,8 @@ int ddamg_hip_create(const ddamg_hip_params* p, ddamg_hip_ctx** out) {
     DDAMG_HIP_CHECK(hipMemcpy(lv->d_lex_of_site, lv->geom.lex_of_site.data(), sizeof(int) * lv->geom.V, hipMemcpyHostToDevice));
     c->levels.push_back(std::move(lv));
   }
-  if (c->knobs.coarse_half && coarse_half_refusal(c.get()) == nullptr) c->coarse_storage_bits = 16;
-  if (c->knobs.transfer_half && transfer_half_refusal(c.get()) == nullptr) c->transfer_storage_bits = 16;
-  if (c->knobs.intermediate_half && intermediate_half_refusal(c.get()) == nullptr) c->intermediate_storage_bits = 16;
+  const bool half[3] = {c->knobs.coarse_half, c->knobs.transfer_half, c->knobs.intermediate_half};   // by StorageKind
+  for (int k = 0; k < 3; k++) if (half[k] && storage_refusal(c.get(), (StorageKind)k) == nullptr) c->storage.bits[k] = 16;
   srand(1000u * (unsigned)c->levels[0]->geom.rank);  // reference: srand( 1000*g.my_rank ) unless "randomize test vectors" (src/init.c:870-873)
   *out = c.release();
   DDAMG_API_END
@@ -166,38 +164,9 @@ int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes) {
   return 0;
 }
 
-int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* c, int bits) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_REQUIRE(bits == 16 || bits == 32, "coarse storage: bits must be 16 or 32");
-  if (bits == 16) if (const char* why = coarse_half_refusal(c)) throw std::runtime_error(why);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (c->mg32) c->mg32->set_coarse_storage(bits);
-  c->coarse_storage_bits = bits;
-  DDAMG_API_END
-}
-
-int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* c, int bits) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_REQUIRE(bits == 16 || bits == 32, "transfer storage: bits must be 16 or 32");
-  if (bits == 16) if (const char* why = transfer_half_refusal(c)) throw std::runtime_error(why);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (c->mg32) c->mg32->set_transfer_storage(bits);
-  c->transfer_storage_bits = bits;
-  DDAMG_API_END
-}
-
-int ddamg_hip_set_intermediate_storage(ddamg_hip_ctx* c, int bits) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_REQUIRE(bits == 16 || bits == 32, "intermediate storage: bits must be 16 or 32");
-  if (bits == 16) if (const char* why = intermediate_half_refusal(c)) throw std::runtime_error(why);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (c->mg32) c->mg32->set_intermediate_storage(bits);
-  c->intermediate_storage_bits = bits;
-  DDAMG_API_END
-}
+int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Coarse, bits, "coarse"); }
+int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Transfer, bits, "transfer"); }
+int ddamg_hip_set_intermediate_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Intermediate, bits, "intermediate"); }
 
 static void drop_clover_base(ddamg_hip_ctx* c) {
   if (c->clover_base) { (void)hipStreamSynchronize(c->stream); c->clover_base.reset(); }

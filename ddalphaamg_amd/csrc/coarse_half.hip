@@ -82,27 +82,31 @@ __global__ __launch_bounds__(256) void coarse_half_build_kernel(__half2* __restr
   if (threadIdx.x == 0) scale[(size_t)x * 6 + m] = s;
 }
 
-void coarse_half_build(__half2* Mh, __half2* Minvh, float* scale, const CoarseOpDev<float>& op, int m0, int count, hipStream_t st) {
+// matrices m0 .. m0 + count - 1 of every site (0-4 the couplings, 5 the inverted self coupling) from `op` into Mh / Minvh in the
+// layout of coarse_half.h, their scales to scale[site * 6 + m].  Minvh is read only for m = 5.
+static void coarse_half_build(__half2* Mh, __half2* Minvh, float* scale, const CoarseOpDev<float>& op, int m0, int count, hipStream_t st) {
   hipLaunchKernelGGL(coarse_half_build_kernel, dim3(op.V, count), dim3(256), 0, st, Mh, Minvh, scale, op, m0);
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 
-CoarseHalfDev CoarseHalf::refresh(const CoarseOp<float>& op, hipStream_t st) {
-  DDAMG_REQUIRE(!op.distributed(), "16-bit coarse storage: the coarsest level must live on one process");
-  DDAMG_REQUIRE(op.nt() >= 1 && op.nt() <= 8, "16-bit coarse storage: at most 64 dof per site");
+// with_inverse: the caller reads Minv as well; it is allocated and built by the first such call
+CoarseHalfDev CoarseHalf::refresh(const CoarseOp<float>& op, hipStream_t st, bool with_inverse) {
+  DDAMG_REQUIRE(!op.distributed(), "16-bit coupling storage: the level must live on one process");
+  DDAMG_REQUIRE(op.nt() >= 1 && op.nt() <= 8, "16-bit coupling storage: at most 64 dof per site");
   const size_t V = (size_t)op.V();
-  if (src_ != &op || !M_) {
+  if (!M_) {
     M_.alloc(V * 5 * op.msize());
-    Minv_.alloc(V * op.msize());
     scale_.alloc(V * 6);
-    src_ = &op; valid_ = false;
+    valid_ = false;
   }
+  const bool new_inverse = with_inverse && !Minv_;
+  if (new_inverse) Minv_.alloc(V * op.msize());
   const CoarseOpDev<float> d = op.dev();
   if (!valid_ || version_ != op.version()) {
     coarse_half_build(M_, Minv_, scale_, d, 0, 5, st);
     version_ = op.version();
   }
-  if (!valid_ || inverse_version_ != op.inverse_version()) {
+  if (with_inverse && (new_inverse || inverse_version_ != op.inverse_version())) {
     coarse_half_build(M_, Minv_, scale_, d, 5, 1, st);
     inverse_version_ = op.inverse_version();
   }
@@ -112,7 +116,7 @@ CoarseHalfDev CoarseHalf::refresh(const CoarseOp<float>& op, hipStream_t st) {
 
 void CoarseHalf::release() {
   M_.reset(); Minv_.reset(); scale_.reset();
-  src_ = nullptr; valid_ = false;
+  valid_ = false;
 }
 
 static void launch_half(const CoarseHalfDev& h, int nt, float* out, const float* in, int s0, int s1, int mode, double sign, bool acc, int swz, hipStream_t st) {
@@ -135,13 +139,13 @@ static void launch_half(const CoarseHalfDev& h, int nt, float* out, const float*
 
 void CoarseHalf::hop(const CoarseOp<float>& op, float* out, const float* in, int s0, int s1, double sign, bool accumulate, hipStream_t st) {
   DDAMG_REQUIRE(out != in, "coarse hopping term cannot run in place");
-  const CoarseHalfDev h = refresh(op, st);
+  const CoarseHalfDev h = refresh(op, st, true);
   launch_half(h, op.nt(), out, in, s0, s1, HALF_HOP, sign, accumulate, (hop_count_++ & 1u) ? 2 : 0, st);
 }
 
 void CoarseHalf::self_mul(const CoarseOp<float>& op, float* out, const float* in, int s0, int s1, bool inverse, hipStream_t st) {
   DDAMG_REQUIRE(out != in, "coarse self coupling cannot run in place");
-  const CoarseHalfDev h = refresh(op, st);
+  const CoarseHalfDev h = refresh(op, st, true);
   launch_half(h, op.nt(), out, in, s0, s1, inverse ? HALF_SELFINV : HALF_SELF, 1.0, false, 0, st);
 }
 

@@ -1,8 +1,8 @@
-// coarse_half_level.hip -- see coarse_half_level.h.  The kernels are the three intermediate-level products of coarse_op.hip
+// coarse_half_level.hip -- see coarse_half.h.  The kernels are the three intermediate-level products of coarse_op.hip
 // (coarse_apply_once_kernel + its finish pass, coarse_site_kernel in its full and hopping-term forms, coarse_block_minres_kernel)
 // on the 16-bit copy: the same workgroup shapes, the same LDS plans, every matrix streamed in 16-byte loads per lane, converted
 // in registers and accumulated in fp32.
-#include "coarse_half_level.h"
+#include "coarse_half.h"
 #include "coarse_half_device.h"
 
 namespace ddamg {
@@ -320,30 +320,7 @@ __global__ __launch_bounds__(HALF_MINRES_THREADS) void coarse_half_block_minres_
   }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
-CoarseHalfDev CoarseHalfLevel::refresh(const CoarseOp<float>& op, hipStream_t st) {
-  DDAMG_REQUIRE(!op.distributed(), "16-bit intermediate storage: the level must live on one process");
-  DDAMG_REQUIRE(op.nt() >= 1 && op.nt() <= 8, "16-bit intermediate storage: at most 64 dof per site");
-  const size_t V = (size_t)op.V();
-  if (src_ != &op || !M_) {
-    M_.alloc(V * 5 * op.msize());
-    scale_.alloc(V * 6);
-    src_ = &op; valid_ = false;
-  }
-  const CoarseOpDev<float> d = op.dev();
-  if (!valid_ || version_ != op.version()) {
-    coarse_half_build(M_, nullptr, scale_, d, 0, 5, st);
-    version_ = op.version();
-  }
-  valid_ = true;
-  return CoarseHalfDev{M_, nullptr, scale_, d.nb, op.V(), op.n(), op.msize()};
-}
-
-void CoarseHalfLevel::release() {
-  M_.reset(); scale_.reset();
-  src_ = nullptr; valid_ = false;
-}
-
+// ---- host side: CoarseHalf's three products of an intermediate level (refresh and release: coarse_half.hip) ------------------
 static void launch_half_site(const CoarseHalfDev& h, int nt, float* out, const float* in, int nsites, bool full, double ss, double sh, bool acc,
                              const int* site_list, const unsigned char* dir_mask, bool mask_invert, hipStream_t st) {
   if (nsites <= 0) return;
@@ -362,9 +339,9 @@ static void launch_half_site(const CoarseHalfDev& h, int nt, float* out, const f
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 
-void CoarseHalfLevel::apply(const CoarseOp<float>& op, float* out, const float* in, hipStream_t st) {
+void CoarseHalf::apply(const CoarseOp<float>& op, float* out, const float* in, hipStream_t st) {
   DDAMG_REQUIRE(out != in, "coarse apply cannot run in place");
-  const CoarseHalfDev h = refresh(op, st);
+  const CoarseHalfDev h = refresh(op, st, false);
   if (op.V() < op.knobs().coarse_apply_once_min_sites) {   // the threshold of CoarseOp::apply
     launch_half_site(h, op.nt(), out, in, op.V(), true, 1.0, -1.0, false, nullptr, nullptr, false, st);
     return;
@@ -381,21 +358,21 @@ void CoarseHalfLevel::apply(const CoarseOp<float>& op, float* out, const float* 
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 
-void CoarseHalfLevel::apply_masked(const CoarseOp<float>& op, float* out, const float* in, const int* site_list, int nsites, const unsigned char* dir_mask,
+void CoarseHalf::apply_masked(const CoarseOp<float>& op, float* out, const float* in, const int* site_list, int nsites, const unsigned char* dir_mask,
                                    bool mask_invert, double sign_self, double sign_hop, bool accumulate, hipStream_t st) {
   DDAMG_REQUIRE(out != in, "coarse apply cannot run in place");
-  const CoarseHalfDev h = refresh(op, st);
+  const CoarseHalfDev h = refresh(op, st, false);
   launch_half_site(h, op.nt(), out, in, nsites, sign_self != 0.0, sign_self, sign_hop, accumulate, site_list, dir_mask, mask_invert, st);
 }
 
-bool CoarseHalfLevel::block_minres(const CoarseOp<float>& op, float* x, float* r, float* latest, const int* blocks, int nblocks,
+bool CoarseHalf::block_minres(const CoarseOp<float>& op, float* x, float* r, float* latest, const int* blocks, int nblocks,
                                    const CoarseOp<float>::BlockPlan& plan, int iters, double eps, hipStream_t st) {
   // the shape limits of CoarseOp::block_minres
   const int np = 8 * op.nt(), BS = plan.block_sites;
   const size_t lds = 48 * sizeof(double) + sizeof(float) * 2 * np * ((size_t)2 * BS + (size_t)2 * plan.nitems);
   if (op.knobs().coarse_sap_unfused || plan.nitems == 0 || (size_t)BS * op.n() > (size_t)HALF_MINRES_THREADS * HALF_MINRES_MAXE || lds > 150 * 1024) return false;
   if (nblocks <= 0) return true;
-  const CoarseHalfDev h = refresh(op, st);
+  const CoarseHalfDev h = refresh(op, st, false);
 #define DDAMG_CASE(NTV) case NTV: \
     DDAMG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&coarse_half_block_minres_kernel<NTV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     hipLaunchKernelGGL((coarse_half_block_minres_kernel<NTV>), dim3(nblocks), dim3(HALF_MINRES_THREADS), lds, st, x, r, latest, h, blocks, plan.d_items, plan.nitems, \

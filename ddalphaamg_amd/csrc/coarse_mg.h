@@ -9,7 +9,7 @@
 #include "common.h"
 #include "geometry.h"
 #include "coarse_op.h"
-#include "coarse_half_level.h"
+#include "coarse_half.h"
 #include <vector>
 
 namespace ddamg {
@@ -34,8 +34,8 @@ class CoarseSap {
  public:
   void setup(const Geometry& g, const CoarseOp<T>* op, int block_iter, int method, hipStream_t st);
   // half: the 16-bit copy of the level's couplings that the residual updates and the block solver read instead of the fp32
-  // couplings (coarse_half_level.h; fp32 only), or nullptr
-  void smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st, CoarseHalfLevel* half = nullptr);
+  // couplings (coarse_half.h; fp32 only), or nullptr
+  void smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st, CoarseHalf* half = nullptr);
   DeviceBuffer<T> r, latest, x, tmp;
 
  private:

@@ -384,7 +384,7 @@ void CoarseSap<T>::setup(const Geometry& g, const CoarseOp<T>* op, int block_ite
 }
 
 template <typename T>
-void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st, CoarseHalfLevel* half) {
+void CoarseSap<T>::smooth(T* phi, T* Dphi, const T* eta, int cycles, int res, hipStream_t st, CoarseHalf* half) {
   DDAMG_REQUIRE(op_ != nullptr, "coarse SAP smoother not set up");
   DDAMG_REQUIRE(half == nullptr || sizeof(T) == 4, "coarse SAP smoother: 16-bit couplings need fp32 vectors");
   // the two products of the operator in the storage the caller chose

@@ -77,7 +77,7 @@ class CoarseOp {
   int nt() const { return nt_; }
   const Knobs& knobs() const { return *knobs_; }
   // [4][V][n] complex: the backward products between the two passes of apply(); allocated by its first use, shared with the
-  // 16-bit form of that apply (coarse_half_level.h)
+  // 16-bit form of that apply (coarse_half.h)
   T* backward_workspace() const { if (!bwd_) bwd_.alloc(4 * (size_t)V_ * n_ * 2); return bwd_; }
 
   // out = D_c in on all sites

@@ -68,13 +68,9 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   std::unique_ptr<ddamg::Multigrid<float>> mg32;
   std::unique_ptr<ddamg::Multigrid<double>> mg64;
   bool setup_done = false;
-  // bits per real of the coarsest couplings the solve reads, 32 or 16 (ddamg_hip_set_coarse_storage; initial value from
-  // knobs.coarse_half); handed to mg32 when the hierarchy is created
-  int coarse_storage_bits = 32;
-  // the same for the fine level's interpolation operator (ddamg_hip_set_transfer_storage; knobs.transfer_half)
-  int transfer_storage_bits = 32;
-  // the same for the couplings of every intermediate level (ddamg_hip_set_intermediate_storage; knobs.intermediate_half)
-  int intermediate_storage_bits = 32;
+  // bits per real, 32 or 16, of what the solve may read from a 16-bit copy (half_storage.h; ddamg_hip_set_*_storage, initial
+  // values from knobs.*_half); handed to mg32 when the hierarchy is created
+  ddamg::StorageBits storage;
   // outer FGMRES (fp64) and its workspace
   ddamg::Gmres<double> outer;
   ddamg::ReduceWork rw_outer;

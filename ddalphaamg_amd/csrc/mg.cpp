@@ -28,8 +28,6 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
     if (d > 0) max_coarse = std::max(max_coarse, lv->nel);
     lv_.push_back(std::move(lv));
   }
-  ihalf_.resize(L);
-  for (int d = 1; d + 1 < L; d++) ihalf_[d].reset(new CoarseHalfLevel);
   for (int d = 0; d < L; d++) {
     MGLevel<T>& lv = *lv_[d];
     const Geometry& g = *lv.g;
@@ -228,7 +226,7 @@ void Multigrid<T>::setup_gathered_coarsest() {
   for (int s = 0; s < V; s++) if (G.g.parity[s] == 0) n_even++;
   DDAMG_REQUIRE(n_even * 2 == V, "coarsest lattice needs as many even as odd sites");
   G.gm.view = View{1, 0, 0, (size_t)n_even * n * 2};
-  G.gm.op = [this](T* out, const T* in) { this->schur_on(gath_.cop, gath_.g.V, gath_.buf[0], gath_.buf[1], out, in); };
+  G.gm.op = [this](T* out, const T* in) { this->schur_on(true, gath_.g.V, gath_.buf[0], gath_.buf[1], out, in); };
   G.on = true;
 }
 
@@ -250,33 +248,44 @@ Multigrid<T>::~Multigrid() {
 // ---- level-generic pieces ---------------------------------------------------------------------------
 template <typename T> void Multigrid<T>::apply_op(int l, T* out, const T* in) {
   if (l == 0) lv_[0]->fop->apply(out, in, st_);
-  else if (lv_[l]->coarsest && half_storage(lv_[l]->cop)) {   // self coupling, then the hopping terms on top of it
-    DDAMG_REQUIRE(out != in, "coarse apply cannot run in place");
-    const CoarseOp<T>& cop = lv_[l]->cop;
-    coarsest_self_mul(cop, out, in, 0, cop.V(), false);
-    coarsest_hop(cop, out, in, 0, cop.V(), -1.0, true);
-  }
-  else if (CoarseHalfLevel* h = intermediate_half(l)) {
-    if constexpr (sizeof(T) == 4) h->apply(lv_[l]->cop, out, in, st_);
+  else if (CoarseHalf* h = half_of(l)) {
+    if (lv_[l]->coarsest) {   // self coupling, then the hopping terms on top of it
+      DDAMG_REQUIRE(out != in, "coarse apply cannot run in place");
+      const int V = lv_[l]->cop.V();
+      coarsest_self_mul(false, out, in, 0, V, false);
+      coarsest_hop(false, out, in, 0, V, -1.0, true);
+    } else if constexpr (sizeof(T) == 4) h->apply(lv_[l]->cop, out, in, st_);
   }
   else lv_[l]->cop.apply(out, in, st_);
 }
 
-// ---- storage of the coarsest couplings (coarse_half.h) ------------------------------------------------
+// ---- 16-bit storage for the solve (half_storage.h) -------------------------------------------------------
 template <typename T>
-void Multigrid<T>::set_coarse_storage(int bits) {
-  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "coarse storage: 32 bits, or 16 with the fp32 V-cycle");
-  coarse_bits_ = bits;
-  if (bits == 32 && half_.allocated()) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); half_.release(); }
+void Multigrid<T>::set_storage(StorageKind kind, int bits) {
+  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "storage: 32 bits, or 16 with the fp32 V-cycle");
+  storage_.bits[kind] = bits;
+  if (bits != 32) return;
+  // free this kind's copies; one wait for the stream if any of them is in use
+  bool waited = false;
+  const auto release = [&](auto& copy) {
+    if (!copy.allocated()) return;
+    if (!waited) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); waited = true; }
+    copy.release();
+  };
+  if (kind == Transfer) release(thalf_);
+  if (kind == Coarse) { release(lv_.back()->half); release(gath_.half); }
+  if (kind == Intermediate) for (int l = 1; l + 1 < num_levels(); l++) release(lv_[l]->half);
 }
 template <typename T>
-void Multigrid<T>::coarsest_hop(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, double sign, bool accumulate) {
-  if constexpr (sizeof(T) == 4) { if (half_storage(cop)) { half_.hop(cop, out, in, s0, s1, sign, accumulate, st_); return; } }
+void Multigrid<T>::coarsest_hop(bool gathered, T* out, const T* in, int s0, int s1, double sign, bool accumulate) {
+  const CoarseOp<T>& cop = gathered ? gath_.cop : lv_.back()->cop;
+  if constexpr (sizeof(T) == 4) { if (CoarseHalf* h = half_of(num_levels() - 1, gathered)) { h->hop(cop, out, in, s0, s1, sign, accumulate, st_); return; } }
   cop.hop(out, in, s0, s1, sign, accumulate, st_);
 }
 template <typename T>
-void Multigrid<T>::coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse) {
-  if constexpr (sizeof(T) == 4) { if (half_storage(cop)) { half_.self_mul(cop, out, in, s0, s1, inverse, st_); return; } }
+void Multigrid<T>::coarsest_self_mul(bool gathered, T* out, const T* in, int s0, int s1, bool inverse) {
+  const CoarseOp<T>& cop = gathered ? gath_.cop : lv_.back()->cop;
+  if constexpr (sizeof(T) == 4) { if (CoarseHalf* h = half_of(num_levels() - 1, gathered)) { h->self_mul(cop, out, in, s0, s1, inverse, st_); return; } }
   cop.self_mul(out, in, s0, s1, inverse, st_);
 }
 template <typename T> void Multigrid<T>::smoother(int l, T* phi, T* Dphi, const T* eta, int cycles, int res) {
@@ -286,33 +295,15 @@ template <typename T> void Multigrid<T>::smoother(int l, T* phi, T* Dphi, const 
     return;
   }
   if (l == 0) lv_[0]->fsap.smooth(phi, Dphi, eta, cycles, res, st_);
-  else lv_[l]->csap.smooth(phi, Dphi, eta, cycles, res, st_, intermediate_half(l));
-}
-// ---- storage of the intermediate levels' couplings (coarse_half_level.h) --------------------------------
-template <typename T>
-void Multigrid<T>::set_intermediate_storage(int bits) {
-  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "intermediate storage: 32 bits, or 16 with the fp32 V-cycle");
-  intermediate_bits_ = bits;
-  if (bits == 32) {
-    bool any = false;
-    for (auto& h : ihalf_) any = any || (h && h->allocated());
-    if (any) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); for (auto& h : ihalf_) if (h) h->release(); }
-  }
-}
-// ---- storage of the fine level's interpolation operator (transfer_half.h) -----------------------------
-template <typename T>
-void Multigrid<T>::set_transfer_storage(int bits) {
-  DDAMG_REQUIRE(bits == 32 || (bits == 16 && sizeof(T) == 4), "transfer storage: 32 bits, or 16 with the fp32 V-cycle");
-  transfer_bits_ = bits;
-  if (bits == 32 && thalf_.allocated()) { DDAMG_HIP_CHECK(hipStreamSynchronize(st_)); thalf_.release(); }
+  else lv_[l]->csap.smooth(phi, Dphi, eta, cycles, res, st_, half_of(l));
 }
 template <typename T> void Multigrid<T>::restrict_to(int l, T* phi_c, const T* phi) {
-  if constexpr (sizeof(T) == 4) { if (l == 0 && transfer_bits_ == 16) { thalf_.restrict_to(lv_[0]->fip, phi_c, phi, st_); return; } }
+  if constexpr (sizeof(T) == 4) { if (l == 0 && storage_.bits[Transfer] == 16) { thalf_.restrict_to(lv_[0]->fip, phi_c, phi, st_); return; } }
   if (l == 0) lv_[0]->fip.restrict_to(phi_c, phi, st_);
   else lv_[l]->cip.restrict_to(phi_c, phi, st_);
 }
 template <typename T> void Multigrid<T>::interpolate(int l, T* phi, const T* phi_c, bool add) {
-  if constexpr (sizeof(T) == 4) { if (l == 0 && transfer_bits_ == 16) { thalf_.interpolate(lv_[0]->fip, phi, phi_c, add, st_); return; } }
+  if constexpr (sizeof(T) == 4) { if (l == 0 && storage_.bits[Transfer] == 16) { thalf_.interpolate(lv_[0]->fip, phi, phi_c, add, st_); return; } }
   if (l == 0) lv_[0]->fip.interpolate(phi, phi_c, add, st_);
   else lv_[l]->cip.interpolate(phi, phi_c, add, st_);
 }
@@ -402,32 +393,30 @@ void Multigrid<T>::gmres_smoother(int l, T* phi, const T* eta, int cycles, int r
 template <typename T>
 void Multigrid<T>::coarsest_hop_parity(T* out, const T* in, int parity, double sign, bool accumulate) {
   DDAMG_REQUIRE(par_.odd_even && (parity == 0 || parity == 1), "coarsest hopping term by parity: odd_even = 1, parity 0 or 1");
-  const CoarseOp<T>& cop = lv_.back()->cop;
-  const int Ve = cop.V() / 2;
-  coarsest_hop(cop, out, in, parity ? Ve : 0, parity ? cop.V() : Ve, sign, accumulate);
+  const int V = lv_.back()->cop.V(), Ve = V / 2;
+  coarsest_hop(false, out, in, parity ? Ve : 0, parity ? V : Ve, sign, accumulate);
 }
 template <typename T>
 void Multigrid<T>::coarsest_self_mul_parity(T* out, const T* in, int parity, bool inverse) {
   DDAMG_REQUIRE(par_.odd_even && (parity == 0 || parity == 1), "coarsest self coupling by parity: odd_even = 1, parity 0 or 1");
-  const CoarseOp<T>& cop = lv_.back()->cop;
-  const int Ve = cop.V() / 2;
-  coarsest_self_mul(cop, out, in, parity ? Ve : 0, parity ? cop.V() : Ve, inverse);
+  const int V = lv_.back()->cop.V(), Ve = V / 2;
+  coarsest_self_mul(false, out, in, parity ? Ve : 0, parity ? V : Ve, inverse);
 }
 
 // ---- coarsest level: odd-even Schur complement solve ----------------------------------------------
 // S = D_ee - D_eo D_oo^-1 D_oe  on the even sites (coarse_apply_schur_complement_PRECISION)
 template <typename T>
-void Multigrid<T>::schur_on(const CoarseOp<T>& cop, int V, T* t0, T* t1, T* out, const T* in) {
+void Multigrid<T>::schur_on(bool gathered, int V, T* t0, T* t1, T* out, const T* in) {
   const int Ve = V / 2;
-  coarsest_self_mul(cop, out, in, 0, Ve, false);        // out_e = D_ee in_e
-  coarsest_hop(cop, t0, in, Ve, V, -1.0, false);        // tmp0_o = -H_oe in_e   (= D_oe in_e)
-  coarsest_self_mul(cop, t1, t0, Ve, V, true);          // tmp1_o = D_oo^-1 tmp0_o
-  coarsest_hop(cop, out, t1, 0, Ve, +1.0, true);        // out_e += H_eo tmp1_o  (= -D_eo tmp1_o)
+  coarsest_self_mul(gathered, out, in, 0, Ve, false);        // out_e = D_ee in_e
+  coarsest_hop(gathered, t0, in, Ve, V, -1.0, false);        // tmp0_o = -H_oe in_e   (= D_oe in_e)
+  coarsest_self_mul(gathered, t1, t0, Ve, V, true);          // tmp1_o = D_oo^-1 tmp0_o
+  coarsest_hop(gathered, out, t1, 0, Ve, +1.0, true);        // out_e += H_eo tmp1_o  (= -D_eo tmp1_o)
 }
 template <typename T>
 void Multigrid<T>::schur(T* out, const T* in) {
   MGLevel<T>& lv = *lv_.back();
-  schur_on(lv.cop, lv.g->V, lv.buf[0], lv.buf[1], out, in);
+  schur_on(false, lv.g->V, lv.buf[0], lv.buf[1], out, in);
 }
 
 template <typename T>
@@ -449,20 +438,20 @@ int Multigrid<T>::coarse_solve() {
     comm_allgather(comm_, b, G.raw, sizeof(T) * row * (size_t)G.V_local, st_);
     T *gx = G.gm.x, *gb = G.gm.b;
     gather_rows<T>(gb, G.raw, G.d_g2d, Vg, row, st_);
-    coarsest_self_mul(G.cop, gx, gb, Vge, Vg, true);
-    coarsest_hop(G.cop, gb, gx, 0, Vge, +1.0, true);
+    coarsest_self_mul(true, gx, gb, Vge, Vg, true);
+    coarsest_hop(true, gb, gx, 0, Vge, +1.0, true);
     const int it = G.gm.solve();
-    coarsest_hop(G.cop, gb, gx, Vge, Vg, +1.0, true);
-    coarsest_self_mul(G.cop, gx, gb, Vge, Vg, true);
+    coarsest_hop(true, gb, gx, Vge, Vg, +1.0, true);
+    coarsest_self_mul(true, gx, gb, Vge, Vg, true);
     gather_rows<T>(x, gx, G.d_d2g, G.V_local, row, st_);
     coarse_iter_count += it;
     return it;
   }
-  coarsest_self_mul(lv.cop, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
-  coarsest_hop(lv.cop, b, x, 0, Ve, +1.0, true);    // b_e <- b_e - D_eo x_o
+  coarsest_self_mul(false, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
+  coarsest_hop(false, b, x, 0, Ve, +1.0, true);    // b_e <- b_e - D_eo x_o
   int it = lv.gm.solve();                           // S x_e = b_e  to coarse_tol
-  coarsest_hop(lv.cop, b, x, Ve, V, +1.0, true);    // b_o <- b_o - D_oe x_e
-  coarsest_self_mul(lv.cop, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
+  coarsest_hop(false, b, x, Ve, V, +1.0, true);    // b_o <- b_o - D_oe x_e
+  coarsest_self_mul(false, x, b, Ve, V, true);     // x_o = D_oo^-1 b_o
   coarse_iter_count += it;
   return it;
 }

@@ -17,8 +17,8 @@
 #include "coarse_lockstep.h"
 #include "coarse_multi.h"
 #include "coarse_half.h"
-#include "coarse_half_level.h"
 #include "transfer_half.h"
+#include "half_storage.h"
 #include "krylov.h"
 #include "../../include/ddamg_hip.h"
 #include <memory>
@@ -39,6 +39,7 @@ struct MGLevel {
   // operators
   const FineOp<T>* fop = nullptr;   // depth 0
   CoarseOp<T> cop;                  // depth > 0
+  CoarseHalf half;                  // depth > 0, fp32: the 16-bit copy of cop's couplings, allocated by its first use (Multigrid::half_of)
   // smoother + transfer to the next level (not on the coarsest level)
   SapSmoother<T> fsap; Interpolation<T> fip;     // depth 0
   CoarseSap<T> csap; CoarseTransfer<T> cip;      // depth > 0
@@ -68,6 +69,7 @@ struct GatheredCoarsest {
   bool on = false;
   Geometry g;            // the GLOBAL coarsest lattice, not decomposed
   CoarseOp<T> cop;
+  CoarseHalf half;       // as MGLevel::half
   Gmres<T> gm;
   ReduceWork rw;         // no transport: every process computes the same sums
   DeviceBuffer<T> buf[2];
@@ -118,28 +120,17 @@ class Multigrid {
   bool level1_vcycle_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols);
   bool level1_kcycle_many(T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters);
   int kcycle_solve(int l);                                       // the K-cycle FGMRES of level l on level(l).gm.b -> gm.x, one vector
-  // ---- couplings of the coarsest level in 16-bit storage (coarse_half.h; fp32 V-cycle, odd-even, coarsest level on one process) ----
-  // bits 32 or 16: what the one-right-hand-side coarsest Schur complement and apply_op on the coarsest level read.  32 frees the
-  // 16-bit copy.  The setup phases run with 32 whatever the setting (SetupStorage), so the hierarchy never depends on it.
-  void set_coarse_storage(int bits);
-  int coarse_storage() const { return coarse_bits_; }
+  // ---- 16-bit storage for the solve (half_storage.h; fp32 V-cycle): bits 32 or 16 per kind ----
+  // 16: the kind's products read a 16-bit copy that their first use makes.  Coarse: the one-right-hand-side coarsest Schur complement
+  // and apply_op on the coarsest level (odd-even); Transfer: restrict_to(0, ...) and interpolate(0, ...); Intermediate: apply_op(l, ...)
+  // and smoother(l, ...) on the levels between, one copy per level (methods 1-3).  32 frees the kind's copies.  The many-vector
+  // paths, the Galerkin construction and every setup phase (SetupStorage) read the fp32 numbers whatever the setting.
+  void set_storage(StorageKind kind, int bits);
+  void set_storage(const StorageBits& b) { for (int k = 0; k < 3; k++) set_storage((StorageKind)k, b.bits[k]); }
   // the two products the coarsest Schur complement is made of, on the sites of one parity (0: even, 1: odd) of the parity-ordered
   // coarsest level, in the storage that is set: CoarseOp::hop / self_mul over that half of the sites (ddamg_hip_coarse_hop, ..._self_mul)
   void coarsest_hop_parity(T* out, const T* in, int parity, double sign, bool accumulate);
   void coarsest_self_mul_parity(T* out, const T* in, int parity, bool inverse);
-  // ---- the fine level's interpolation operator in 16-bit storage (transfer_half.h; fp32 V-cycle) ----
-  // bits 32 or 16: what restrict_to(0, ...) and interpolate(0, ...) read.  32 frees the 16-bit copy.  The many-vector transfers
-  // (restrict_batch*, interpolate_batch, the Galerkin construction) and the intermediate levels read the fp32 P whatever the
-  // setting, and so does every setup phase (SetupStorage).
-  void set_transfer_storage(int bits);
-  int transfer_storage() const { return transfer_bits_; }
-  // ---- the couplings of every intermediate level in 16-bit storage (coarse_half_level.h; fp32 V-cycle, methods 1-3, level on one process) ----
-  // bits 32 or 16: what apply_op(l, ...) and smoother(l, ...) read on the levels with depth > 0 that are not the coarsest (the
-  // K-cycle's operator, the Schwarz smoother's residual updates and its block solver).  One copy per such level, made by its
-  // first use; 32 frees them.  The many-vector paths (coarse_multi.h, *_many), the Galerkin construction and every setup phase
-  // (SetupStorage) read the fp32 couplings whatever the setting.
-  void set_intermediate_storage(int bits);
-  int intermediate_storage() const { return intermediate_bits_; }
 
   int num_levels() const { return (int)lv_.size(); }
   MGLevel<T>& level(int l) { return *lv_[l]; }
@@ -170,29 +161,27 @@ class Multigrid {
   DeviceBuffer<T> cwork_;    // coarse work space (5 vectors of the largest coarse level)
 
   GatheredCoarsest<T> gath_;
-  int coarse_bits_ = 32;
-  CoarseHalf half_;                 // the 16-bit copy of the coarsest couplings: allocated by its first use, never with coarse_bits_ == 32
-  bool half_storage(const CoarseOp<T>& cop) const { return sizeof(T) == 4 && coarse_bits_ == 16 && !cop.distributed(); }
-  // CoarseOp::hop / self_mul of the coarsest level in the storage that is set
-  void coarsest_hop(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, double sign, bool accumulate);
-  void coarsest_self_mul(const CoarseOp<T>& cop, T* out, const T* in, int s0, int s1, bool inverse);
-  int transfer_bits_ = 32;
-  TransferHalf thalf_;              // the 16-bit copy of the fine level's P: allocated by its first use, never with transfer_bits_ == 32
-  int intermediate_bits_ = 32;
-  std::vector<std::unique_ptr<CoarseHalfLevel>> ihalf_;   // per level: the 16-bit copy of an intermediate level's couplings (null elsewhere), allocated by its first use
-  // the copy that level l's products read in the storage that is set, or nullptr: the fp32 couplings
-  CoarseHalfLevel* intermediate_half(int l) const {
-    if (sizeof(T) != 4 || intermediate_bits_ != 16 || par_.method > 3 || !ihalf_[l] || lv_[l]->cop.distributed()) return nullptr;
-    return ihalf_[l].get();
+  StorageBits storage_;             // a 16-bit copy is allocated by its first use, never while its kind is set to 32
+  TransferHalf thalf_;              // the 16-bit copy of the fine level's P
+  // the copy that level l's products read in the storage that is set (gathered: those of the gathered coarsest operator), or
+  // nullptr: the fp32 couplings
+  CoarseHalf* half_of(int l, bool gathered = false) {
+    MGLevel<T>& lv = *lv_[l];
+    if (sizeof(T) != 4 || l == 0) return nullptr;
+    if (lv.coarsest) {
+      if (storage_.bits[Coarse] != 16) return nullptr;
+      if (gathered) return gath_.cop.distributed() ? nullptr : &gath_.half;
+    } else if (storage_.bits[Intermediate] != 16 || par_.method > 3) return nullptr;
+    return lv.cop.distributed() ? nullptr : &lv.half;
   }
-  // 32-bit storage of all three for the lifetime of the object (a setup phase), the settings restored afterwards
+  // CoarseOp::hop / self_mul of the coarsest level (gathered: of the gathered coarsest operator) in the storage that is set
+  void coarsest_hop(bool gathered, T* out, const T* in, int s0, int s1, double sign, bool accumulate);
+  void coarsest_self_mul(bool gathered, T* out, const T* in, int s0, int s1, bool inverse);
+  // 32-bit storage of all kinds for the lifetime of the object (a setup phase), the settings restored afterwards
   struct SetupStorage {
-    int& coarse; int& transfer; int& intermediate; const int saved_coarse, saved_transfer, saved_intermediate;
-    explicit SetupStorage(Multigrid& mg) : coarse(mg.coarse_bits_), transfer(mg.transfer_bits_), intermediate(mg.intermediate_bits_),
-                                           saved_coarse(mg.coarse_bits_), saved_transfer(mg.transfer_bits_), saved_intermediate(mg.intermediate_bits_) {
-      coarse = 32; transfer = 32; intermediate = 32;
-    }
-    ~SetupStorage() { coarse = saved_coarse; transfer = saved_transfer; intermediate = saved_intermediate; }
+    StorageBits& bits; const StorageBits saved;
+    explicit SetupStorage(Multigrid& mg) : bits(mg.storage_), saved(mg.storage_) { bits = StorageBits(); }
+    ~SetupStorage() { bits = saved; }
   };
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)
   CoarseMulti multi1_;              // three levels: the intermediate level for all test vectors at once (coarse_multi.h)
@@ -201,7 +190,7 @@ class Multigrid {
   int multi1_kcycle(float2* X, const float2* B, int ncols, int* iters);
   void setup_gathered_coarsest();
   void schur(T* out, const T* in);
-  void schur_on(const CoarseOp<T>& cop, int V, T* t0, T* t1, T* out, const T* in);
+  void schur_on(bool gathered, int V, T* t0, T* t1, T* out, const T* in);
   std::vector<int> ref_order0_;   // fine-level vector-loop order of the reference when odd_even == 0
   void smoother_schur(int l, T* out, const T* in);            // (apply_schur_complement / coarse_apply_schur_complement on level l)
   void gmres_smoother(int l, T* phi, const T* eta, int cycles, int res);

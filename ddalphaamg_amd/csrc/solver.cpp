@@ -36,7 +36,7 @@ static void ensure_mg(ddamg_hip_ctx* c) {
   if (c->par.mixed_precision == 0) {
     if (!c->mg64) { c->mg64.reset(new Multigrid<double>(c->par, c->knobs, geoms, &c->fop64, c->stream)); c->mg64->set_comm(c->comm); }
   } else {
-    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, c->knobs, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); c->mg32->set_coarse_storage(c->coarse_storage_bits); c->mg32->set_transfer_storage(c->transfer_storage_bits); c->mg32->set_intermediate_storage(c->intermediate_storage_bits); }
+    if (!c->mg32) { c->mg32.reset(new Multigrid<float>(c->par, c->knobs, geoms, &c->fop32, c->stream)); c->mg32->set_comm(c->comm); c->mg32->set_storage(c->storage); }
   }
 }
 

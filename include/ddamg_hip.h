@@ -177,7 +177,7 @@ int ddamg_hip_coarse_apply(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_h
  * level (0: even, 1: odd; odd_even == 1), in the coarse storage that is set:
  *   hop:      out(x) = [accumulate ? out(x) : 0] + sign * (sum of the eight hopping terms of `in`)(x)    -- a "half hopping term"
  *   self_mul: out(x) = M0(x) in(x), or M0(x)^-1 in(x) with inverse != 0
- * The sites of the other parity in `out` are left as they are.  For measurements and kernel tests (tools/coarse_half_bench.py). */
+ * The sites of the other parity in `out` are left as they are.  For measurements and kernel tests (tools/half_storage_bench.py). */
 int ddamg_hip_coarse_hop(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, double sign, int accumulate);
 int ddamg_hip_coarse_self_mul(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, int inverse);
 /* replaces coarse_solve_odd_even_PRECISION (src/coarse_oddeven_generic.c:1139-1159) */

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the intermediate levels' couplings in 16-bit storage (ddamg_hip_set_intermediate_storage,
-coarse_half_level.h): the three kernels on an operator that the format holds exactly (where the two storages differ by the
+coarse_half_level.hip): the three kernels on an operator that the format holds exactly (where the two storages differ by the
 order of their sums only), on the real operator against the format bound of tests/test_gpu_coarse_half.py, fused against
 unfused block solver, K-cycle and solve in both storages, the setup staying on the fp32 couplings, the copy following the
 operator, memory accounting and the refusals.
