@@ -1,4 +1,4 @@
-// blas_driver.hip -- host program that runs ONE operation of blas.h / krylov.h on inputs a test wrote, and writes what came out.
+// blas_driver.hip -- host program that runs ONE operation of blas.h / krylov.h / coarse_lockstep.h (the batch BLAS) on inputs a test wrote, and writes what came out.
 //
 //   blas_driver <dir>
 //
@@ -9,6 +9,7 @@
 // ends it with status 2 and the exception text on stderr.
 #include "blas.h"
 #include "krylov.h"
+#include "coarse_lockstep.h"
 #include <cstring>
 #include <fstream>
 #include <map>
@@ -381,6 +382,88 @@ static void run_gmres(const Case& c, hipStream_t st) {
   c.write("Vb", Vb.data(), Vb.size());
 }
 
+// ---- BLAS-1 on batches [row][32 columns], every column with its own coefficient (coarse_lockstep.h); fp32 only -----------------
+// Arrays are files of float (two per complex number) or double; strides and counts are in the units of the library's interface:
+// sstride / dstride in floats, vstride, rows and elems in complex numbers.
+template <typename U> static void fill_ff(U* d, size_t n) { DDAMG_HIP_CHECK(hipMemset(d, 0xFF, sizeof(U) * (n ? n : 1))); DDAMG_HIP_CHECK(hipDeviceSynchronize()); }
+static const float2* c2(const Dev<float>& a) { return reinterpret_cast<const float2*>((const float*)a.p); }
+static float2* c2(Dev<float>& a) { return reinterpret_cast<float2*>((float*)a.p); }
+
+static void run_batch_gather(const Case& c, hipStream_t st) {
+  const size_t rows = (size_t)c.i("rows"), sstride = (size_t)c.i("sstride");
+  const int ncols = (int)c.i("ncols");
+  Dev<float> Wb, src;
+  Wb.load(c, "Wb"); src.load(c, "src");
+  need(ncols >= 0 && ncols <= LOCKSTEP_COLS && rows >= 1, "0 <= ncols <= 32, rows >= 1");
+  need(ncols == 0 || (size_t)(ncols - 1) * sstride + 2 * rows <= src.n, "columns exceed src");
+  need(2 * rows * LOCKSTEP_COLS <= Wb.n, "batch exceeds Wb");
+  batch_gather(c2(Wb), src.p, sstride, ncols, rows, st);
+  sync(st);
+  Wb.store(c, "Wb");
+}
+
+static void run_batch_scatter(const Case& c, hipStream_t st) {
+  const size_t rows = (size_t)c.i("rows"), dstride = (size_t)c.i("dstride");
+  const int ncols = (int)c.i("ncols");
+  Dev<float> Wb, dst;
+  Wb.load(c, "Wb"); dst.load(c, "dst");
+  need(ncols >= 0 && ncols <= LOCKSTEP_COLS && rows >= 1, "0 <= ncols <= 32, rows >= 1");
+  need(ncols == 0 || (size_t)(ncols - 1) * dstride + 2 * rows <= dst.n, "columns exceed dst");
+  need(2 * rows * LOCKSTEP_COLS <= Wb.n, "batch exceeds Wb");
+  batch_scatter(dst.p, dstride, c2(Wb), ncols, rows, st);
+  sync(st);
+  dst.store(c, "dst");
+}
+
+// runs twice; res holds both results, each (m + extra) * 32 complex numbers of which the call may write the first m * 32
+static void run_batch_dots(const Case& c, hipStream_t st) {
+  const size_t rows = (size_t)c.i("rows"), vstride = (size_t)c.i("vstride");
+  const int m = (int)c.i("m"), extra = (int)c.i("extra", 1);
+  Dev<float> basis, w;
+  basis.load(c, "basis"); w.load(c, "w");
+  need(m >= 1 && extra >= 0 && rows >= 1, "m >= 1, extra >= 0, rows >= 1");
+  need(2 * ((size_t)(m - 1) * vstride + rows * LOCKSTEP_COLS) <= basis.n, "vectors exceed basis");
+  need(2 * rows * LOCKSTEP_COLS <= w.n, "batch exceeds w");
+  const size_t nres = (size_t)2 * (m + extra) * LOCKSTEP_COLS, nws = batch_dots_workspace();
+  DeviceBuffer<double> d_out, d_partial;
+  d_out.alloc(nres); d_partial.alloc(nws);
+  std::vector<double> res(2 * nres);
+  for (int rep = 0; rep < 2; rep++) {
+    fill_ff<double>(d_out, nres);
+    fill_ff<double>(d_partial, nws);
+    batch_dots(c2(basis), vstride, m, c2(w), rows, d_partial, d_out, st);
+    sync(st);
+    DDAMG_HIP_CHECK(hipMemcpy(res.data() + (size_t)rep * nres, d_out, sizeof(double) * nres, hipMemcpyDeviceToHost));
+  }
+  c.write("res", res.data(), res.size());
+}
+
+static void run_batch_axpy(const Case& c, hipStream_t st) {
+  const size_t elems = (size_t)c.i("elems"), vstride = (size_t)c.i("vstride");
+  const int m = (int)c.i("m");
+  Dev<float> w, basis;
+  Dev<double> coef;
+  w.load(c, "w"); basis.load(c, "basis"); coef.load(c, "coef");
+  need(m >= 1 && elems >= 1, "m >= 1, elems >= 1");
+  need(2 * elems <= w.n && 2 * ((size_t)(m - 1) * vstride + elems) <= basis.n && coef.n >= (size_t)2 * m * LOCKSTEP_COLS, "arrays too short");
+  batch_axpy(c2(w), c2(basis), vstride, m, coef.p, c.d("sign"), elems, st);
+  sync(st);
+  w.store(c, "w");
+}
+
+static void run_batch_scale_inv(const Case& c, hipStream_t st) {
+  const size_t elems = (size_t)c.i("elems");
+  Dev<float> w, out;
+  Dev<double> n2;
+  w.load(c, "w"); n2.load(c, "n2");
+  need(elems >= 1 && 2 * elems <= w.n && n2.n >= (size_t)2 * LOCKSTEP_COLS, "arrays too short");
+  out.from(std::vector<float>(w.n, 0.f));
+  fill_ff<float>(out.p, out.n);
+  batch_scale_inv(c2(out), c2(w), n2.p, elems, st);
+  sync(st);
+  out.store(c, "out");
+}
+
 template <typename T>
 static void run_typed(const Case& c, const std::string& op, hipStream_t st) {
   if (op == "ew") run_ew<T>(c, st);
@@ -403,6 +486,11 @@ int main(int argc, char** argv) {
     else if (op == "convert") run_convert(c, st);
     else if (op == "axpy_f32basis") run_axpy_f32basis(c, st);
     else if (op == "pinned") run_pinned(c, st);
+    else if (op == "batch_gather") run_batch_gather(c, st);
+    else if (op == "batch_scatter") run_batch_scatter(c, st);
+    else if (op == "batch_dots") run_batch_dots(c, st);
+    else if (op == "batch_axpy") run_batch_axpy(c, st);
+    else if (op == "batch_scale_inv") run_batch_scale_inv(c, st);
     else if (c.str("type") == "float") run_typed<float>(c, op, st);
     else if (c.str("type") == "double") run_typed<double>(c, op, st);
     else need(false, "type must be float or double");

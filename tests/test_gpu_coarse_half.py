@@ -10,6 +10,7 @@ and the eight couplings of the site (matrix m, scale s_m):
 import numpy as np
 import pytest
 from conftest import load_golden, splitmix_uniform
+from coarse_reference import CoarseMatrices
 from ddalphaamg_amd import api
 import ddalphaamg_amd as dd
 
@@ -85,68 +86,6 @@ def hier_c(gold8):
 @pytest.fixture(params=["a", "b", "c"])
 def hier(request):
     return request.getfixturevalue("hier_" + request.param)
-
-
-# ---- the coarsest operator in numpy, matrix by matrix ----------------------------------------------------------------------
-class CoarseMatrices:
-    """the nine couplings of every site of level 1 from ddamg_hip_get_coarse_operator (lexicographic sites, the reference's
-    storage): mats[m][x] with m = 0 the self coupling, 1 + mu the forward link U_mu(x), 5 + mu the backward coupling
-    G5 U_mu(x - mu)^H G5; src[m][x] the site whose vector entries matrix m of site x multiplies; sign[m] its sign in D_c"""
-
-    def __init__(self, ctx):
-        D, cl = ctx.get_coarse_operator()
-        n = ctx.ndof(1); N = n // 2
-        Lc = [int(v) for v in ctx.params.local_lattice[1]]
-        V = int(np.prod(Lc))
-        Dc = (D[..., 0] + 1j * D[..., 1]).reshape(V, 4, 4, N, N)       # [site][mu][block A, C, B, D][column][row]
-        clc = cl[..., 0] + 1j * cl[..., 1]
-        tri = N * (N + 1) // 2
-        iu = np.triu_indices(N)
-        order = np.lexsort((iu[0], iu[1]))                             # packed column by column: (0,0) (0,1) (1,1) (0,2) ...
-        ti, tj = iu[0][order], iu[1][order]
-        M0 = np.zeros((V, n, n), dtype=complex)
-        for b in range(2):
-            blk = np.zeros((V, N, N), dtype=complex)
-            blk[:, tj, ti] = np.conj(clc[:, b * tri:(b + 1) * tri])
-            blk[:, ti, tj] = clc[:, b * tri:(b + 1) * tri]
-            M0[:, b * N:(b + 1) * N, b * N:(b + 1) * N] = blk
-        B = clc[:, 2 * tri:2 * tri + N * N].reshape(V, N, N).transpose(0, 2, 1)
-        M0[:, :N, N:] = B
-        M0[:, N:, :N] = -B.conj().transpose(0, 2, 1)
-        U = np.zeros((V, 4, n, n), dtype=complex)
-        for q, (bi, bj) in enumerate([(0, 0), (1, 0), (0, 1), (1, 1)]):
-            U[:, :, bi * N:(bi + 1) * N, bj * N:(bj + 1) * N] = Dc[:, :, q].transpose(0, 1, 3, 2)
-        g5 = np.concatenate([np.ones(N), -np.ones(N)])
-        coords = np.stack(np.unravel_index(np.arange(V), Lc), axis=1)
-        self.mats, self.src, self.sign = [M0], [np.arange(V)], [1.0]
-        fwd = []
-        for mu in range(4):
-            c = coords.copy(); c[:, mu] = (c[:, mu] + 1) % Lc[mu]
-            fwd.append(np.ravel_multi_index(c.T, Lc))
-            self.mats.append(U[:, mu]); self.src.append(fwd[mu]); self.sign.append(-1.0)
-        for mu in range(4):
-            c = coords.copy(); c[:, mu] = (c[:, mu] - 1) % Lc[mu]
-            bwd = np.ravel_multi_index(c.T, Lc)
-            self.mats.append(g5[None, :, None] * U[bwd, mu].conj().transpose(0, 2, 1) * g5[None, None, :])
-            self.src.append(bwd); self.sign.append(-1.0)
-        self.V, self.n = V, n
-
-    def apply(self, x):
-        """D_c x in fp64; x: [V][n][2]"""
-        xc = x[..., 0] + 1j * x[..., 1]
-        y = sum(s * np.einsum("xij,xj->xi", M, xc[src]) for M, src, s in zip(self.mats, self.src, self.sign))
-        return np.stack([y.real, y.imag], axis=-1)
-
-    def bound(self, x, first=0):
-        """B of the module docstring, [V][n] (the same for the real and the imaginary part of a component); first = 1: the sums
-        over the eight hopping terms only"""
-        ax = np.abs(x[..., 0]) + np.abs(x[..., 1])
-        B = np.zeros((self.V, self.n))
-        for M, src in zip(self.mats[first:], self.src[first:]):
-            s = np.maximum(np.abs(M.real).max(axis=(1, 2)), np.abs(M.imag).max(axis=(1, 2)))
-            B += 2.0 ** -10 * np.einsum("xij,xj->xi", np.abs(M.real) + np.abs(M.imag), ax[src])
-            B += 2.0 ** -23 * (s * ax[src].sum(axis=1))[:, None]
-        return B
 
 
 def applies(ctx, xs, bits):

@@ -666,7 +666,8 @@ def test_coarse_operator_single_read_form(gold4, monkeypatch):
     ctx.close()
 
 
-def test_coarsest_solves_of_many_right_hand_sides_in_lockstep(gold_b4, gold8):
+@pytest.mark.parametrize("ncols", [7, 17, 32])
+def test_coarsest_solves_of_many_right_hand_sides_in_lockstep(gold_b4, gold8, ncols):
     """coarse_lockstep.h: the coarsest-level odd-even Schur GMRES for many right-hand sides at once -- independent recurrences
     advanced together, the coarse operator on the matrix cores -- against the one-at-a-time solver column by column: the same
     iteration count (one more or less where the stopping test falls on the rounding of the operator kernel), the same solution
@@ -675,7 +676,6 @@ def test_coarsest_solves_of_many_right_hand_sides_in_lockstep(gold_b4, gold8):
     ctx.setup(2)
     lc = 1
     n = ctx.ndof(lc); Vc = ctx.volume(lc)
-    ncols = 7
     bs, xs, xr, itr = [], [], [], []
     for c in range(ncols):
         bh = splitmix_uniform(Vc * n * 2, 100 + c).reshape(Vc, n, 2)

@@ -202,11 +202,12 @@ def test_schwarz_smoother_of_the_intermediate_level(unfused, monkeypatch):
         ctx.close()
 
 
-def test_schwarz_smoother_of_many_right_hand_sides(ref3):
-    """cm_block_minres_kernel: column 0 against the reference's dumps, every column against the one-vector smoother"""
+@pytest.mark.parametrize("ncols", [5, 17, 32])
+def test_schwarz_smoother_of_many_right_hand_sides(ref3, ncols):
+    """cm_block_minres_kernel: column 0 against the reference's dumps, every column against the one-vector smoother; with 17 and 32
+    columns the second half of the columns (the workgroups of col0 = 16) carries data"""
     g, ctx = ref3
     ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"], level=1)
-    ncols = 5
     hs = columns(ctx, 1, g["l1_smoother_eta"], ncols, 600)
     etas = [ctx.vector(1, 32).upload(h) for h in hs]; phis = [ctx.vector(1, 32) for _ in hs]
     one = ctx.vector(1, 32)
@@ -231,13 +232,14 @@ def test_schwarz_smoother_of_many_right_hand_sides(ref3):
         v.free()
 
 
-def test_vcycle_of_the_intermediate_level(ref3):
+@pytest.mark.parametrize("ncols", [6, 17, 32])
+def test_vcycle_of_the_intermediate_level(ref3, ncols):
     """vcycle_float on level 1 (restriction, coarsest odd-even solve, interpolation, smoother) against the reference's dump, one
-    vector at a time and for many right-hand sides in lockstep"""
+    vector at a time and for many right-hand sides in lockstep; with 17 and 32 columns cm_restrict_kernel, cm_interpolate_kernel
+    and the lockstep solve carry data in the second half of the columns"""
     g, ctx = ref3
     ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"], level=1)
     ctx.set_coarse_operator(g["l2_coarse_D"], g["l2_coarse_clover"], level=2)
-    ncols = 6
     hs = columns(ctx, 1, g["l1_vcycle_eta"], ncols, 800)
     etas = [ctx.vector(1, 32).upload(h) for h in hs]; phis = [ctx.vector(1, 32) for _ in hs]
     one = ctx.vector(1, 32)
@@ -255,14 +257,14 @@ def test_vcycle_of_the_intermediate_level(ref3):
         v.free()
 
 
-def test_kcycles_of_many_right_hand_sides_in_lockstep(ref3):
+@pytest.mark.parametrize("ncols", [6, 17, 32])
+def test_kcycles_of_many_right_hand_sides_in_lockstep(ref3, ncols):
     """CoarseMulti::kcycle: FGMRES(5) x 2 with the level's V-cycle as preconditioner, every column its own recurrence, against the
     one-at-a-time K-cycle (Gmres<T>::solve): iteration counts (one more or less where a stopping test falls on the rounding) and the
     defining property -- the residual of every column below the K-cycle tolerance or the iteration budget spent"""
     g, ctx = ref3
     ctx.set_coarse_operator(g["coarse_D"], g["coarse_clover"], level=1)
     ctx.set_coarse_operator(g["l2_coarse_D"], g["l2_coarse_clover"], level=2)
-    ncols = 6
     hs = columns(ctx, 1, g["l1_vcycle_eta"], ncols, 900)
     bs = [ctx.vector(1, 32).upload(h) for h in hs]; xs = [ctx.vector(1, 32) for _ in hs]
     one = ctx.vector(1, 32); Dx = ctx.vector(1, 32)
