@@ -89,6 +89,13 @@ def load_library():
         "ddamg_hip_destroy": [vp],
         "ddamg_hip_set_gauge": [vp, dp, ctypes.c_int, dp],
         "ddamg_hip_set_gauge2": [vp, dp, dp, ctypes.c_int, dp],
+        "ddamg_hip_set_gauge_device": [vp, dp, ctypes.c_int, dp],
+        "ddamg_hip_set_gauge2_device": [vp, dp, dp, ctypes.c_int, dp],
+        "ddamg_hip_clover_kernel_time": [vp, dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), dp],
+        "ddamg_hip_vec_upload_device": [vp, vp, dp],
+        "ddamg_hip_vec_download_device": [vp, vp, dp],
+        "ddamg_hip_solve_device": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_preconditioner_device": [vp, dp, dp],
         "ddamg_hip_set_operator": [vp, dp, dp],
         "ddamg_hip_shift_mass": [vp, ctypes.c_double],
         "ddamg_hip_setup_at_mass": [vp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_int)],
@@ -259,6 +266,29 @@ def _dp(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def _dev(a, reals, what):
+    """the address of an array of `reals` float64 numbers in device memory: an integer address (the caller vouches for size and
+    type; the library checks that it is device memory) or any object with data_ptr().  A torch tensor is checked for dtype,
+    contiguity, element count and is_cuda, and its device's current stream is waited for, because the library works on a stream
+    of its own."""
+    if isinstance(a, int):
+        return ctypes.cast(ctypes.c_void_p(a), ctypes.POINTER(ctypes.c_double))
+    if not hasattr(a, "data_ptr"):
+        raise DDAMGError(f"{what}: expected an integer device address or an object with data_ptr(), got {type(a).__name__}")
+    if hasattr(a, "is_cuda"):   # a torch tensor
+        import torch
+        if not a.is_cuda:
+            raise DDAMGError(f"{what}: the tensor is in host memory (host arrays go through the call without _device)")
+        if a.dtype != torch.float64:
+            raise DDAMGError(f"{what}: the tensor must be float64, got {a.dtype}")
+        if not a.is_contiguous():
+            raise DDAMGError(f"{what}: the tensor must be contiguous")
+        if a.numel() != reals:
+            raise DDAMGError(f"{what}: expected {reals} reals, got {a.numel()}")
+        torch.cuda.current_stream(a.device).synchronize()
+    return ctypes.cast(ctypes.c_void_p(int(a.data_ptr())), ctypes.POINTER(ctypes.c_double))
+
+
 def default_params():
     p = Params()
     load_library().ddamg_hip_default_params(ctypes.byref(p))
@@ -284,6 +314,16 @@ class Vector:
         out = np.empty((self.V, self.ndof, 2), dtype=np.float64)
         _check(self.ctx._lib.ddamg_hip_vec_download(self.ctx._h, self._h, _dp(out)))
         return out
+
+    def upload_device(self, dev_lex):
+        """upload from a lexicographic float64 array in device memory (integer address or an object with data_ptr())"""
+        _check(self.ctx._lib.ddamg_hip_vec_upload_device(self.ctx._h, self._h, _dev(dev_lex, self.V * self.ndof * 2, "upload_device")))
+        return self
+
+    def download_device(self, dev_lex):
+        """download into a lexicographic float64 array in device memory; returns dev_lex"""
+        _check(self.ctx._lib.ddamg_hip_vec_download_device(self.ctx._h, self._h, _dev(dev_lex, self.V * self.ndof * 2, "download_device")))
+        return dev_lex
 
     def free(self):
         if self._h:
@@ -322,6 +362,30 @@ class Context:
         plaq = ctypes.c_double(0)
         _check(self._lib.ddamg_hip_set_gauge2(self._h, _dp(a), _dp(b), int(bool(anti_pbc)), ctypes.byref(plaq)))
         return plaq.value
+
+    def set_gauge_device(self, gauge_dev_lex, anti_pbc=True):
+        """set_gauge from links in device memory ([V][4][9] complex float64, lexicographic): an integer address or an object
+        with data_ptr(), a torch tensor for instance; the array is not written"""
+        plaq = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_set_gauge_device(self._h, _dev(gauge_dev_lex, self.volume(0) * 72, "set_gauge_device"), int(bool(anti_pbc)),
+                                                    ctypes.byref(plaq)))
+        return plaq.value
+
+    def set_gauge2_device(self, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc=False):
+        """set_gauge2 from two fields in device memory"""
+        plaq = ctypes.c_double(0)
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_set_gauge2_device(self._h, _dev(hopp_gauge_dev_lex, n, "set_gauge2_device"),
+                                                     _dev(clover_gauge_dev_lex, n, "set_gauge2_device"), int(bool(anti_pbc)), ctypes.byref(plaq)))
+        return plaq.value
+
+    def clover_kernel_time(self, gauge_dev_lex, which, reps=10):
+        """(milliseconds per launch, plaquette) of the field-strength kernel (which = 0), the host path's clover kernel (1) or
+        the field-strength, assembly and plaquette-sum kernels together (2) on links in device memory; a measurement"""
+        ms = ctypes.c_float(0); plaq = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_clover_kernel_time(self._h, _dev(gauge_dev_lex, self.volume(0) * 72, "clover_kernel_time"), int(which), int(reps),
+                                                      ctypes.byref(ms), ctypes.byref(plaq)))
+        return ms.value, plaq.value
 
     def set_operator(self, D_lex, clover_lex):
         D = np.ascontiguousarray(D_lex, dtype=np.float64)
@@ -518,6 +582,21 @@ class Context:
         out = np.empty((self.volume(0), 12, 2))
         _check(self._lib.ddamg_hip_preconditioner(self._h, _dp(out), _dp(a)))
         return out
+
+    def solve_device(self, x_dev_lex, b_dev_lex, tol=0.0):
+        """solve with the right-hand side and the solution in device memory ([V][12] complex float64, lexicographic; integer
+        addresses or objects with data_ptr()); returns (iterations, coarse_iterations, true relative residual)"""
+        n = self.volume(0) * 24
+        it = ctypes.c_int(0); ci = ctypes.c_int(0); rr = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_solve_device(self._h, _dev(x_dev_lex, n, "solve_device"), _dev(b_dev_lex, n, "solve_device"), float(tol),
+                                                ctypes.byref(it), ctypes.byref(ci), ctypes.byref(rr)))
+        return it.value, ci.value, rr.value
+
+    def preconditioner_device(self, out_dev_lex, in_dev_lex):
+        """one V-cycle from / into arrays in device memory; returns out_dev_lex"""
+        n = self.volume(0) * 24
+        _check(self._lib.ddamg_hip_preconditioner_device(self._h, _dev(out_dev_lex, n, "preconditioner_device"), _dev(in_dev_lex, n, "preconditioner_device")))
+        return out_dev_lex
 
     def residual_history(self):
         n = ctypes.c_int(0)

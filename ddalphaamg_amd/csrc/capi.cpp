@@ -57,6 +57,27 @@ static int set_storage(ddamg_hip_ctx* c, StorageKind kind, int bits, const char*
   DDAMG_API_END
 }
 
+void ddamg_require_device_array(const ddamg_hip_ctx* c, const void* p, size_t bytes, const char* what) {
+  const std::string name(what);
+  DDAMG_REQUIRE(p != nullptr, (name + ": null pointer where an array in device memory is expected").c_str());
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError();   // a pointer the runtime does not know: host memory
+  DDAMG_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeDevice,
+                (name + ": not a pointer into device memory (host arrays go through the entry point without _device)").c_str());
+  DDAMG_REQUIRE(at.device == c->device, (name + ": the array lies in the memory of another device than the context's").c_str());
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  const hipError_t r = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<void*>(p));
+  if (r != hipSuccess) (void)hipGetLastError();
+  DDAMG_REQUIRE(r == hipSuccess && (const char*)p + bytes <= (const char*)base + size, (name + ": the device allocation is smaller than the array").c_str());
+}
+
+void ddamg_require_disjoint(const void* out, const void* in, size_t bytes, const char* what) {
+  const char* a = (const char*)out; const char* b = (const char*)in;
+  DDAMG_REQUIRE(a + bytes <= b || b + bytes <= a, (std::string(what) + ": the output and the input array overlap").c_str());
+}
+
 extern "C" {
 
 const char* ddamg_hip_last_error(void) { return g_last_error.c_str(); }
@@ -173,14 +194,63 @@ static void drop_clover_base(ddamg_hip_ctx* c) {
   c->scale_even = c->scale_odd = 1.0;
 }
 
+// what follows the upload of a new fine operator, from host arrays or from device arrays
+static void operator_replaced(ddamg_hip_ctx* c) {
+  c->have_operator = true;
+  if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
+  if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
+}
+
 static void upload_operator(ddamg_hip_ctx* c) {
   drop_clover_base(c);      // a new operator is unscaled
   const Geometry& g = c->levels[0]->geom;
   c->fop64.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
   c->fop32.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
-  c->have_operator = true;
-  if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
-  if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
+  c->mirror_valid = true;
+  operator_replaced(c);
+}
+
+// D_host / clover_host from the fp64 operator on the device when ddamg_hip_set_gauge*_device left them stale (of a scaled operator:
+// the unscaled field, which is what they hold after ddamg_hip_set_gauge as well)
+static void ensure_host_mirror(ddamg_hip_ctx* c) {
+  if (c->mirror_valid) return;
+  const size_t V = c->levels[0]->geom.V;
+  DeviceBuffer<double> dD, dC;
+  dD.alloc(72 * V);
+  dC.alloc(84 * V);
+  c->fop64.export_lex(dD, dC, c->clover_base ? c->clover_base.get() : nullptr, c->stream);
+  c->D_host.resize(72 * V);
+  c->clover_host.resize(84 * V);
+  DDAMG_HIP_CHECK(hipMemcpyAsync(c->D_host.data(), dD, sizeof(double) * 72 * V, hipMemcpyDeviceToHost, c->stream));
+  DDAMG_HIP_CHECK(hipMemcpyAsync(c->clover_host.data(), dC, sizeof(double) * 84 * V, hipMemcpyDeviceToHost, c->stream));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->mirror_valid = true;
+}
+
+// links in device memory -> both fine operators, nothing through the host (ddamg_hip_set_gauge_device / _set_gauge2_device)
+static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": links in device memory are taken on a single process only, because the clover term on a "
+                                   "process grid needs the neighbours' links: use ddamg_hip_set_gauge there").c_str());
+  const size_t V = g.V;
+  ddamg_require_device_array(c, hopp_dev, sizeof(double) * 72 * V, name);
+  if (clover_dev != hopp_dev) ddamg_require_device_array(c, clover_dev, sizeof(double) * 72 * V, name);
+  DeviceBuffer<double> dD, dC;   // the staging arrays of FineOp::upload, filled on the device
+  dD.alloc(72 * V);
+  dC.alloc(84 * V);
+  const double pl = gauge_to_operator_resident(g.L, hopp_dev, clover_dev, anti_pbc, c->par.m0, c->par.csw, dD, dC, c->stream);
+  if (plaquette) *plaquette = pl;
+  drop_clover_base(c);      // a new operator is unscaled
+  c->fop64.upload_staged(g, dD, dC, c->knobs, c->stream);
+  c->fop32.upload_staged(g, dD, dC, c->knobs, c->stream);
+  dD.reset(); dC.reset();
+  c->fop64.init_halo(g); c->fop32.init_halo(g);
+  c->mirror_valid = false;
+  std::vector<double>().swap(c->D_host);
+  std::vector<double>().swap(c->clover_host);
+  operator_replaced(c);
 }
 
 // gauge field -> operator fields in the reference's storage (dirac_setup, src/dirac.c:60-168), no upload
@@ -224,6 +294,31 @@ int ddamg_hip_set_gauge2(ddamg_hip_ctx* c, const double* hopp_gauge_lex, const d
   DDAMG_API_END
 }
 
+int ddamg_hip_set_gauge_device(ddamg_hip_ctx* c, const double* gauge_dev_lex, int anti_pbc, double* plaquette) {
+  DDAMG_API_BEGIN
+  set_gauge_resident(c, gauge_dev_lex, gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge_device");
+  DDAMG_API_END
+}
+
+int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* c, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette) {
+  // D from the first field, clover term and plaquette from the second, one layout pass
+  DDAMG_API_BEGIN
+  set_gauge_resident(c, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge2_device");
+  DDAMG_API_END
+}
+
+int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* c, const double* gauge_dev_lex, int which, int reps, float* milliseconds, double* plaquette) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && milliseconds, "null argument");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed(), "ddamg_hip_clover_kernel_time: single process only");
+  ddamg_require_device_array(c, gauge_dev_lex, sizeof(double) * 72 * g.V, "ddamg_hip_clover_kernel_time");
+  const double pl = clover_kernels_timed(g.L, gauge_dev_lex, c->par.m0, c->par.csw, which, reps, c->ev0, c->ev1, c->stream, milliseconds);
+  if (plaquette) *plaquette = pl;
+  DDAMG_API_END
+}
+
 // shift_update (src/dirac.c:646-668): m0 -> new_m0 on the operator that is set, on the device: the clover diagonals of both
 // precisions, the 6x6 inverses of the odd-even kernels, and the self couplings of every coarse level (+ their inverses).
 // No upload, no Galerkin construction; the host copy handed out by dd_alpha_amg_get_clover_pointer follows.
@@ -242,8 +337,9 @@ int ddamg_hip_shift_mass(ddamg_hip_ctx* c, double new_m0) {
       if (c->mg32) c->mg32->mass_shifted(diff);
       if (c->mg64) c->mg64->mass_shifted(diff);
     }
-    for (size_t s = 0; s < V; s++)
-      for (int k = 0; k < 12; k++) c->clover_host[(s * 42 + k) * 2] += diff;
+    if (c->mirror_valid)   // a stale host copy stays stale: what rebuilds it reads the device fields shifted above
+      for (size_t s = 0; s < V; s++)
+        for (int k = 0; k < 12; k++) c->clover_host[(s * 42 + k) * 2] += diff;
     c->par.m0 = new_m0;
     DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   }
@@ -345,6 +441,8 @@ int ddamg_hip_halo_plan(const int local_lattice[4], const int process_grid[4], c
 int ddamg_hip_get_operator(ddamg_hip_ctx* c, double* D_lex, double* clover_lex) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c && c->have_operator, "no operator set");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  ensure_host_mirror(c);
   if (D_lex) memcpy(D_lex, c->D_host.data(), sizeof(double) * c->D_host.size());
   if (clover_lex) memcpy(clover_lex, c->clover_host.data(), sizeof(double) * c->clover_host.size());
   DDAMG_API_END
@@ -410,6 +508,40 @@ int ddamg_hip_vec_download(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* hos
     else vec_to_lex<double>(st, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
   }
   DDAMG_HIP_CHECK(hipMemcpyAsync(host_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_vec_upload_device(ddamg_hip_ctx* c, ddamg_hip_vec* v, const double* dev_lex) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && v, "null argument");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  ddamg_require_device_array(c, dev_lex, (size_t)v->V * v->ndof * 2 * sizeof(double), "ddamg_hip_vec_upload_device");
+  const int* tab = c->levels[v->level]->d_lex_of_site;
+  if (v->aos) {
+    if (v->precision == 32) aos_from_lex<float>((float*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
+    else aos_from_lex<double>((double*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
+  } else {
+    if (v->precision == 32) vec_from_lex<float>((float*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
+    else vec_from_lex<double>((double*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
+  }
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_vec_download_device(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* dev_lex) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && v, "null argument");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  ddamg_require_device_array(c, dev_lex, (size_t)v->V * v->ndof * 2 * sizeof(double), "ddamg_hip_vec_download_device");
+  const int* tab = c->levels[v->level]->d_lex_of_site;
+  if (v->aos) {
+    if (v->precision == 32) aos_to_lex<float>(dev_lex, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
+    else aos_to_lex<double>(dev_lex, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
+  } else {
+    if (v->precision == 32) vec_to_lex<float>(dev_lex, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
+    else vec_to_lex<double>(dev_lex, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
+  }
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }

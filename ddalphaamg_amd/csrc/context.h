@@ -54,6 +54,9 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   // fine operator in the reference's host storage (fp64) + device copies in both precisions
   std::vector<double> D_host, clover_host;
   bool have_operator = false;
+  // whether D_host / clover_host show the operator that is set: cleared by ddamg_hip_set_gauge*_device, which fills neither; who
+  // needs them then rebuilds them from the fp64 operator first (ddamg_hip_get_operator)
+  bool mirror_valid = false;
   // scale_clover: unscaled fp64 copy of the clover field on the device while the operator is scaled (ddamg_hip_scale_clover)
   ddamg::DeviceBuffer<double> clover_base;
   double scale_even = 1.0, scale_odd = 1.0;
@@ -92,3 +95,8 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   double last_relres = 0;
   std::vector<double> last_history;
 };
+
+// the *_device entry points (capi.cpp): throws unless [p, p + bytes) lies in one allocation in the memory of the context's device
+void ddamg_require_device_array(const ddamg_hip_ctx* c, const void* p, size_t bytes, const char* what);
+// ... and unless the output and the input array of a call are disjoint
+void ddamg_require_disjoint(const void* out, const void* in, size_t bytes, const char* what);

@@ -1,0 +1,225 @@
+// field_strength.h -- the bodies of the kernels that take the operator fields from links the caller keeps in device memory
+// (gauge_device.hip: field_strength_kernel, clover_assemble_kernel).  Reference: Q / Qdiff / set_clover src/dirac.c:304-402,
+// calc_plaq :568-622.
+//
+// One workgroup = one wave = an 8 x 8 tile of sites of ONE plane (mu, nu), mu < nu.  The four leaves of Q_{mu nu} at the sites
+// of the tile read U_mu on (8+1) x (8+2) and U_nu on (8+2) x (8+1) sites of the plane and no other link, so the workgroup
+// stages the (8+2) x (8+2) neighbourhood of both directions in LDS once (200 links for 128 of its own: every link leaves
+// memory 1.6 times per plane it lies in, three planes each) and all twelve products of a site read LDS only.
+// Q_{nu mu} = Q_{mu nu}^dagger, so the plane's contribution to the clover term is F = (Q - Q^dagger) / 16: anti-Hermitian,
+// kept as 9 reals per site and plane.  The plaquette is the trace of the first leaf.
+//
+// The bodies are plain functions of (workgroup, thread) so that a host program can run them thread by thread.
+#pragma once
+#include <cstddef>
+
+#if defined(__HIPCC__)
+#define DDAMG_FS_HD __host__ __device__ __forceinline__
+#else
+#define DDAMG_FS_HD inline
+#endif
+
+namespace ddamg {
+namespace fs {
+
+constexpr int TILE = 8;              // sites per direction of the plane tile
+constexpr int EXT = TILE + 2;        // with the neighbours one site away
+constexpr int NEXT = EXT * EXT;
+constexpr int PITCH = 19;            // doubles per staged link: 18 + 1, an odd number of 8-byte bank pairs
+constexpr int THREADS = TILE * TILE;
+constexpr int LDS_DOUBLES = 2 * NEXT * PITCH;
+
+struct cplx { double r, i; };
+struct M3 { cplx a[9]; };
+
+DDAMG_FS_HD M3 mul(const M3& x, const M3& y) {
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      double sr = 0, si = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const cplx a = x.a[3 * i + k], b = y.a[3 * k + j];
+        sr += a.r * b.r - a.i * b.i; si += a.r * b.i + a.i * b.r;
+      }
+      r.a[3 * i + j] = cplx{sr, si};
+    }
+  return r;
+}
+DDAMG_FS_HD M3 dag(const M3& x) {
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) r.a[3 * i + j] = cplx{x.a[3 * j + i].r, -x.a[3 * j + i].i};
+  return r;
+}
+
+// the six planes mu < nu in the order of the reference's loops, and the two directions outside each
+struct Planes {
+  int L[4];
+  int nblocks[6];   // workgroups of each plane
+  int max_blocks;
+};
+DDAMG_FS_HD int plane_mu(int p) { return p < 3 ? 0 : (p < 5 ? 1 : 2); }
+DDAMG_FS_HD int plane_nu(int p) { return p < 3 ? p + 1 : (p < 5 ? p - 1 : 3); }
+inline Planes make_planes(const int L[4]) {
+  Planes g;
+  g.max_blocks = 0;
+  size_t V = 1;
+  for (int d = 0; d < 4; d++) { g.L[d] = L[d]; V *= (size_t)L[d]; }
+  for (int p = 0; p < 6; p++) {
+    const int mu = plane_mu(p), nu = plane_nu(p);
+    const size_t outside = V / ((size_t)L[mu] * L[nu]);
+    const size_t nb = outside * ((L[mu] + TILE - 1) / TILE) * ((L[nu] + TILE - 1) / TILE);
+    g.nblocks[p] = (int)nb;
+    if (g.nblocks[p] > g.max_blocks) g.max_blocks = g.nblocks[p];
+  }
+  return g;
+}
+
+// where workgroup `block` of plane p sits: the lexicographic offset of the two outside coordinates and the tile origin
+struct Tile {
+  int mu, nu;
+  size_t outside;        // lexicographic site offset of the coordinates outside the plane
+  size_t smu, snu;       // site strides of mu and nu
+  int a0, b0;            // first mu / nu coordinate of the tile
+};
+DDAMG_FS_HD Tile tile_of(const Planes& g, int p, int block) {
+  Tile t;
+  t.mu = plane_mu(p); t.nu = plane_nu(p);
+  size_t stride[4];
+  stride[3] = 1; stride[2] = (size_t)g.L[3]; stride[1] = stride[2] * g.L[2]; stride[0] = stride[1] * g.L[1];
+  t.smu = stride[t.mu]; t.snu = stride[t.nu];
+  const int ntb = (g.L[t.nu] + TILE - 1) / TILE, nta = (g.L[t.mu] + TILE - 1) / TILE;
+  int r = block;
+  t.b0 = (r % ntb) * TILE; r /= ntb;
+  t.a0 = (r % nta) * TILE; r /= nta;
+  t.outside = 0;
+  for (int d = 3; d >= 0; d--)
+    if (d != t.mu && d != t.nu) { t.outside += (size_t)(r % g.L[d]) * stride[d]; r /= g.L[d]; }
+  return t;
+}
+
+// step 1, threads 0 .. 2 EXT - 1: site offset of every mu row (entries 0 .. EXT-1) and nu column (EXT .. 2 EXT - 1) of the
+// staged neighbourhood, periodic; flip[i] != 0: the mu links of row i carry the anti-periodic sign (mu = T, last time slice)
+DDAMG_FS_HD void stage_offsets(const Planes& g, const Tile& t, int anti_pbc, int tid, size_t* off, int* flip) {
+  if (tid >= 2 * EXT) return;
+  const bool row = tid < EXT;
+  const int i = row ? tid : tid - EXT;
+  const int Ld = g.L[row ? t.mu : t.nu];
+  const int c = ((row ? t.a0 : t.b0) + i - 1 + Ld) % Ld;
+  off[tid] = (size_t)c * (row ? t.smu : t.snu);
+  if (row) flip[i] = (anti_pbc && t.mu == 0 && c == g.L[0] - 1) ? 1 : 0;
+}
+
+// step 2, all threads: the links of both directions into LDS, lds[(w * NEXT + i * EXT + j) * PITCH + k], w = 0: U_mu, 1: U_nu;
+// consecutive threads read consecutive reals of the caller's array
+DDAMG_FS_HD void stage_links(const double* __restrict__ U, const Tile& t, int tid, const size_t* off, const int* flip, double* lds) {
+  constexpr int TOTAL = 2 * NEXT * 18, BATCH = 8;   // BATCH loads in flight per thread before the first store
+  for (int k0 = 0; k0 < TOTAL; k0 += THREADS * BATCH) {
+    double v[BATCH]; int dst[BATCH];
+#pragma unroll
+    for (int u = 0; u < BATCH; u++) {
+      const int k = k0 + u * THREADS + tid;
+      dst[u] = -1; v[u] = 0.0;
+      if (k < TOTAL) {
+        const int w = k / (NEXT * 18), rem = k - w * (NEXT * 18);
+        const int e = rem / 18, comp = rem - e * 18;
+        const int i = e / EXT, j = e - i * EXT;
+        const size_t lx = t.outside + off[i] + off[EXT + j];
+        const double u0 = U[(lx * 4 + (w ? t.nu : t.mu)) * 18 + comp];
+        v[u] = (w == 0 && flip[i]) ? -u0 : u0;
+        dst[u] = (w * NEXT + e) * PITCH + comp;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < BATCH; u++) if (dst[u] >= 0) lds[dst[u]] = v[u];
+  }
+}
+
+DDAMG_FS_HD M3 staged(const double* lds, int w, int e) {
+  M3 m; const double* p = lds + (w * NEXT + e) * PITCH;
+#pragma unroll
+  for (int k = 0; k < 9; k++) m.a[k] = cplx{p[2 * k], p[2 * k + 1]};
+  return m;
+}
+
+// step 3, one thread per site of the tile: F (9 reals: the imaginary parts of the diagonal, then (0,1), (0,2), (1,2)) and the
+// real trace of the first leaf.  Returns false for a thread outside the lattice (tile tail).
+DDAMG_FS_HD bool site_field_strength(const Planes& g, const Tile& t, int tid, const double* lds, size_t* lex, double (&F)[9], double* plaq) {
+  const int a = tid / TILE, b = tid - a * TILE;
+  if (t.a0 + a >= g.L[t.mu] || t.b0 + b >= g.L[t.nu]) return false;
+  *lex = t.outside + (size_t)(t.a0 + a) * t.smu + (size_t)(t.b0 + b) * t.snu;
+  const int x = (a + 1) * EXT + (b + 1);          // this site in the staged neighbourhood
+  constexpr int PM = EXT, PN = 1;                 // one step in mu / nu there
+  // the four leaves in the reference's order of factors (src/dirac.c:304-358); only the anti-Hermitian part of their sum is kept
+#pragma unroll
+  for (int r = 0; r < 9; r++) F[r] = 0.0;
+  auto add = [&](const M3& l) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) F[i] += l.a[4 * i].i + l.a[4 * i].i;
+    int k = 3;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = i + 1; j < 3; j++, k += 2) { F[k] += l.a[3 * i + j].r - l.a[3 * j + i].r; F[k + 1] += l.a[3 * i + j].i + l.a[3 * j + i].i; }
+  };
+  M3 l = mul(mul(mul(staged(lds, 0, x), staged(lds, 1, x + PM)), dag(staged(lds, 0, x + PN))), dag(staged(lds, 1, x)));
+  *plaq = l.a[0].r + l.a[4].r + l.a[8].r;
+  add(l);
+  add(mul(mul(mul(staged(lds, 1, x), dag(staged(lds, 0, x + PN - PM))), dag(staged(lds, 1, x - PM))), staged(lds, 0, x - PM)));
+  add(mul(mul(mul(dag(staged(lds, 0, x - PM)), dag(staged(lds, 1, x - PM - PN))), staged(lds, 0, x - PM - PN)), staged(lds, 1, x - PN)));
+  add(mul(mul(mul(dag(staged(lds, 1, x - PN)), staged(lds, 0, x - PN)), staged(lds, 1, x - PN + PM)), dag(staged(lds, 0, x))));
+  // F = (Q - Q^dagger) / 16
+#pragma unroll
+  for (int r = 0; r < 9; r++) F[r] /= 16.0;
+  return true;
+}
+
+struct GammaProducts { double re[6][16], im[6][16]; };   // gamma_mu gamma_nu for the six planes mu < nu
+
+// the clover term of one site, 42 complex in the reference's packing (src/dirac.c:386-398), from the six F of the site:
+// Fs[(p * 9 + r) * V + lex]
+DDAMG_FS_HD void site_clover(const double* __restrict__ Fs, size_t V, size_t lex, double m0, double csw, const GammaProducts& gp,
+                             double* __restrict__ out) {
+  double clr[42], cli[42];
+#pragma unroll
+  for (int k = 0; k < 42; k++) { clr[k] = k < 12 ? 4.0 + m0 : 0.0; cli[k] = 0.0; }
+#pragma unroll
+  for (int p = 0; p < 6; p++) {
+    double f[9];
+#pragma unroll
+    for (int r = 0; r < 9; r++) f[r] = Fs[((size_t)p * 9 + r) * V + lex];
+    cplx qd[9];
+    qd[0] = cplx{0.0, f[0]}; qd[4] = cplx{0.0, f[1]}; qd[8] = cplx{0.0, f[2]};
+    qd[1] = cplx{f[3], f[4]}; qd[3] = cplx{-f[3], f[4]};
+    qd[2] = cplx{f[5], f[6]}; qd[6] = cplx{-f[5], f[6]};
+    qd[5] = cplx{f[7], f[8]}; qd[7] = cplx{-f[7], f[8]};
+    // tensor = -csw * (gamma_mu gamma_nu) (x) F; the diagonal and the strict upper parts of both 6x6 blocks
+    auto add = [&](int k, int i, int j) {
+      const int gi = 4 * (i / 3) + (j / 3), c = 3 * (i % 3) + (j % 3);
+      const double gr = gp.re[p][gi], gm = gp.im[p][gi];
+      clr[k] += -csw * (gr * qd[c].r - gm * qd[c].i);
+      cli[k] += -csw * (gr * qd[c].i + gm * qd[c].r);
+    };
+#pragma unroll
+    for (int k = 0; k < 12; k++) add(k, k, k);
+    int k = 12;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = i + 1; j < 6; j++, k++) add(k, i, j);
+#pragma unroll
+    for (int i = 6; i < 12; i++)
+#pragma unroll
+      for (int j = i + 1; j < 12; j++, k++) add(k, i, j);
+  }
+#pragma unroll
+  for (int k = 0; k < 42; k++) { out[lex * 84 + 2 * k] = clr[k]; out[lex * 84 + 2 * k + 1] = cli[k]; }
+}
+
+}  // namespace fs
+}  // namespace ddamg

@@ -50,6 +50,15 @@ class FineOp {
   // D_ref: [V][4][9] complex (lexicographic sites), clover_ref: [V][42] complex, both fp64 as the
   // reference holds them in g.op_double (src/dirac.c:60-168)
   void upload(const Geometry& g, const double* D_ref, const double* clover_ref, const Knobs& knobs, hipStream_t st);
+  // the same from arrays that are in device memory already (dD, dC: the two arrays of upload, read only): everything upload does
+  // behind its copy -- layout kernel, two-row links, 56-real clover term, neighbour tables -- except the halo buffers, which the
+  // caller asks for with init_halo once it has released dD and dC.  Waits for the stream.
+  void upload_staged(const Geometry& g, const double* dD, const double* dC, const Knobs& knobs, hipStream_t st);
+  void init_halo(const Geometry& g);
+  // the operator back in the reference's storage, into device arrays dD_lex [V][36] complex and dC_lex [V][42] complex: the inverse
+  // of the layout kernel.  clover64: another clover field in this operator's layout (the unscaled copy of a scaled operator), or
+  // null for the operator's own.  T = double only.
+  void export_lex(double* dD_lex, double* dC_lex, const double* clover64, hipStream_t st) const;
   // mass shift without a new upload (shift_update_PRECISION src/dirac_generic.c:504-551): the 12 real diagonal clover entries
   // of every site become those of `clover64` plus `diff`, and the 6x6 inverses the odd-even kernels read are rebuilt from the
   // same fp64 values.  clover64: the fp64 operator's clover field (its own one for T = double, where diff is applied in
@@ -87,6 +96,8 @@ class FineOp {
   void parity_select(T* out, const T* a, const T* b, int keep, hipStream_t st) const;
 
  private:
+  void ensure_storage(const Geometry& g, hipStream_t st);   // the fields and the site tables, at the first upload
+  void layout_staged(const Geometry& g, const double* dD, const double* dC, const Knobs& knobs, hipStream_t st);
   DeviceBuffer<T> D_, clover_, clover_inv_;
   DeviceBuffer<int> nb_;
   DeviceBuffer<int> lex_;      // lexicographic index of every device site (for the layout kernel)
@@ -105,6 +116,8 @@ class FineOp {
 
 template <>
 void FineOp<double>::apply_f32in(double* eta, const float* phi, hipStream_t st) const;
+template <>
+void FineOp<double>::export_lex(double* dD_lex, double* dC_lex, const double* clover64, hipStream_t st) const;
 
 #ifdef __HIPCC__
 }  // namespace ddamg

@@ -668,7 +668,7 @@ __global__ __launch_bounds__(128) void clover_compress_kernel(T* __restrict__ cl
 }
 
 template <typename T>
-void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clover_ref, const Knobs& knobs, hipStream_t st) {
+void FineOp<T>::ensure_storage(const Geometry& g, hipStream_t st) {
   const size_t V = g.V;
   V_ = g.V;
   if (!D_) {
@@ -682,11 +682,36 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
     for (size_t i = 0; i < V; i++) par[i] = (unsigned char)g.parity[i];
     parity_.upload(par);
   }
+}
+
+template <typename T>
+void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clover_ref, const Knobs& knobs, hipStream_t st) {
+  const size_t V = g.V;
+  ensure_storage(g, st);
   DeviceBuffer<double> dD, dC;   // staging of the lexicographic fp64 arrays
   dD.alloc(72 * V);
   dC.alloc(84 * V);
   DDAMG_HIP_CHECK(hipMemcpyAsync(dD, D_ref, sizeof(double) * 72 * V, hipMemcpyHostToDevice, st));
   DDAMG_HIP_CHECK(hipMemcpyAsync(dC, clover_ref, sizeof(double) * 84 * V, hipMemcpyHostToDevice, st));
+  layout_staged(g, dD, dC, knobs, st);
+  dD.reset(); dC.reset();   // before the halo buffers are allocated
+  init_halo(g);
+}
+
+template <typename T>
+void FineOp<T>::upload_staged(const Geometry& g, const double* dD, const double* dC, const Knobs& knobs, hipStream_t st) {
+  ensure_storage(g, st);
+  layout_staged(g, dD, dC, knobs, st);
+}
+
+template <typename T>
+void FineOp<T>::init_halo(const Geometry& g) {
+  if (g.distributed() && !halo_.active()) halo_.init(g);
+}
+
+template <typename T>
+void FineOp<T>::layout_staged(const Geometry& g, const double* dD, const double* dC, const Knobs& knobs, hipStream_t st) {
+  const size_t V = g.V;
   hipLaunchKernelGGL(operator_layout_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, D_, clover_, clover_inv_, dD, dC, lex_, (int)V);
   DDAMG_HIP_CHECK(hipGetLastError());
   // two-row links (a third less link traffic in dirac_apply_lds_kernel and the Schwarz block solver) when every link allows it
@@ -730,8 +755,33 @@ void FineOp<T>::upload(const Geometry& g, const double* D_ref, const double* clo
     DDAMG_HIP_CHECK(hipMemcpyAsync(tnb_, g.blk_wrap_nb.data(), sizeof(unsigned short) * 8 * 256, hipMemcpyHostToDevice, st));
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
-  dD.reset(); dC.reset();   // before the halo buffers are allocated
-  if (g.distributed() && !halo_.active()) halo_.init(g);
+}
+
+// the fp64 operator back into the reference's storage: the exact inverse of operator_layout_kernel<double> (a permutation; the
+// imaginary parts of the clover diagonal, which the device does not keep, are zero)
+__global__ __launch_bounds__(128) void operator_export_kernel(double* __restrict__ D_lex, double* __restrict__ clover_lex, const double* __restrict__ D,
+                                                              const double* __restrict__ clover, const int* __restrict__ lex_of_site, int V) {
+  const size_t s = (size_t)blockIdx.x * 128 + threadIdx.x;
+  if (s >= (size_t)V) return;
+  const size_t lx = lex_of_site[s];
+  for (int mu = 0; mu < 4; mu++)
+    for (int r = 0; r < 18; r++)
+      D_lex[(lx * 36 + mu * 9) * 2 + r] = D[(size_t)mu * 18 * V + soa_index_dev<double>(18, V, s, r)];
+  double* c = clover_lex + lx * 42 * 2;
+  for (int b = 0; b < 2; b++) {
+    const int r0 = 36 * b;
+    for (int i = 0; i < 6; i++) { c[2 * (6 * b + i)] = clover[soa_index_dev<double>(72, V, s, r0 + i)]; c[2 * (6 * b + i) + 1] = 0.0; }
+    for (int k = 0; k < 15; k++) {
+      c[2 * (12 + 15 * b + k)] = clover[soa_index_dev<double>(72, V, s, r0 + 6 + 2 * k)];
+      c[2 * (12 + 15 * b + k) + 1] = clover[soa_index_dev<double>(72, V, s, r0 + 6 + 2 * k + 1)];
+    }
+  }
+}
+template <>
+void FineOp<double>::export_lex(double* dD_lex, double* dC_lex, const double* clover64, hipStream_t st) const {
+  DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
+  hipLaunchKernelGGL(operator_export_kernel, dim3((unsigned)((V_ + 127) / 128)), dim3(128), 0, st, dD_lex, dC_lex, D_, clover64 ? clover64 : clover_.get(), lex_, (int)V_);
+  DDAMG_HIP_CHECK(hipGetLastError());
 }
 
 // ---- global odd-even pieces ------------------------------------------------------------------------

@@ -14,6 +14,17 @@ double clover_and_plaquette_extended_device(const int L[4], const int halo[4], c
 // the same on a process grid: gauge_in is the process's own part; the links of the neighbouring processes that the
 // clover leaves reach (one site deep, corners included) are fetched first (the reference exchanges the ghost shell of
 // the gauge field in dirac_setup, src/dirac.c:88-120); the plaquette is the global average
+// links that stay in device memory (ddamg_hip_set_gauge_device): dU_hopp / dU_clover [V][4][9] complex fp64 lexicographic on the
+// device, read in place and never written (the anti-periodic sign is applied in the loads); writes the device arrays dD [V][36]
+// complex = U_hopp / 2 with the sign and dC [V][42] complex, the clover term of U_clover; returns the average plaquette of
+// U_clover, summed on the device.  Single process.  Waits for the stream.
+double gauge_to_operator_resident(const int L[4], const double* dU_hopp, const double* dU_clover, int anti_pbc, double m0, double csw, double* dD,
+                                  double* dC, hipStream_t st);
+// measurement (ddamg_hip_clover_kernel_time): `reps` launches, after one untimed, of the field-strength kernel (which = 0), of the
+// host path's clover_kernel (1) or of the field-strength, assembly and plaquette-sum kernels (2) on the links dU, between the
+// events e0 and e1; *ms = milliseconds per launch; returns the average plaquette that the kernels give
+double clover_kernels_timed(const int L[4], const double* dU, double m0, double csw, int which, int reps, hipEvent_t e0, hipEvent_t e1, hipStream_t st,
+                            float* ms);
 struct Geometry;
 struct Comm;
 double gauge_to_operator_dist(const Geometry& g, Comm* comm, const double* gauge_in, int anti_pbc, double m0, double csw,

@@ -4,6 +4,7 @@
 // One thread per lexicographic site; links are read straight from the reference layout [V][4][3x3] complex fp64.
 #include "gauge.h"
 #include "common.h"
+#include "field_strength.h"
 #include <vector>
 
 namespace ddamg {
@@ -184,6 +185,147 @@ double clover_and_plaquette_extended_device(const int L[4], const int halo[4], c
   DDAMG_HIP_CHECK(hipMemcpyAsync(dU, U_ext_host, sizeof(double) * 72 * Ve, hipMemcpyHostToDevice, st));
   const double plaq = clover_and_plaquette_on_device(dU, ext, loc, h, m0, csw, clover_out, st);
   return plaq;
+}
+
+
+// ---- links that the caller keeps in device memory (ddamg_hip_set_gauge_device) ----------------------------------------------
+// The links are read in place and never written: the anti-periodic sign is applied in the loads.  Kernel bodies: field_strength.h.
+namespace {
+// F of one plane for an 8 x 8 tile of its sites (grid: x = tiles, y = the six planes) and the tile's sum of plaquette traces
+__global__ __launch_bounds__(fs::THREADS) void field_strength_kernel(double* __restrict__ F, double* __restrict__ plaq_block, const double* __restrict__ U,
+                                                                      fs::Planes g, size_t V, int anti_pbc) {
+  __shared__ double lds[fs::LDS_DOUBLES];
+  __shared__ size_t off[2 * fs::EXT];
+  __shared__ int flip[fs::EXT];
+  const int p = blockIdx.y, block = blockIdx.x, tid = threadIdx.x;
+  const size_t slot = (size_t)p * g.max_blocks + block;
+  if (block >= g.nblocks[p]) {   // planes of a lattice with unequal extents have unequal numbers of tiles
+    if (tid == 0) plaq_block[slot] = 0.0;
+    return;
+  }
+  const fs::Tile t = fs::tile_of(g, p, block);
+  fs::stage_offsets(g, t, anti_pbc, tid, off, flip);
+  __syncthreads();
+  fs::stage_links(U, t, tid, off, flip, lds);
+  __syncthreads();
+  size_t lex = 0; double f[9]; double pl = 0.0;
+  if (fs::site_field_strength(g, t, tid, lds, &lex, f, &pl)) {
+#pragma unroll
+    for (int r = 0; r < 9; r++) F[((size_t)p * 9 + r) * V + lex] = f[r];
+  } else {
+    pl = 0.0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) pl += __shfl_down(pl, o, 64);   // the workgroup is one wave
+  if (tid == 0) plaq_block[slot] = pl;
+}
+
+__global__ __launch_bounds__(128) void clover_assemble_kernel(double* __restrict__ clover, const double* __restrict__ F, size_t V, double m0, double csw,
+                                                              fs::GammaProducts gp) {
+  const size_t lex = (size_t)blockIdx.x * 128 + threadIdx.x;
+  if (lex >= V) return;
+  fs::site_clover(F, V, lex, m0, csw, gp, clover);
+}
+
+// second stage of the plaquette sum: one workgroup, every thread a fixed subsequence, then a tree -- the same sum on every run
+__global__ __launch_bounds__(256) void plaquette_sum_kernel(double* __restrict__ out, const double* __restrict__ part, size_t n) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (size_t i = threadIdx.x; i < n; i += 256) s += part[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+// D = U/2 with the anti-periodic sign of the T-links of the last time slice (src/io.c:536-541, src/dirac.c:80); one real per thread
+__global__ __launch_bounds__(256) void links_to_D_kernel(double* __restrict__ D, const double* __restrict__ U, size_t n, int anti_pbc, size_t first_last_slice) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double u = U[i];
+  D[i] = (anti_pbc && i >= first_last_slice && ((i / 18) % 4) == 0) ? -0.5 * u : 0.5 * u;
+}
+
+fs::GammaProducts gamma_products_fs() {
+  const GammaProducts a = gamma_products();
+  fs::GammaProducts b;
+  for (int p = 0; p < 6; p++) for (int k = 0; k < 16; k++) { b.re[p][k] = a.re[p][k]; b.im[p][k] = a.im[p][k]; }
+  return b;
+}
+
+// work space of the three kernels: F (54 reals per site), the tiles' plaquette sums and the total
+struct ResidentWork {
+  fs::Planes planes;
+  size_t V;
+  DeviceBuffer<double> F, part;
+  ResidentWork(const int L[4]) : planes(fs::make_planes(L)), V((size_t)L[0] * L[1] * L[2] * L[3]) {
+    F.alloc(54 * V);
+    part.alloc(6 * (size_t)planes.max_blocks + 1);
+  }
+  double* total() { return part + 6 * (size_t)planes.max_blocks; }
+  void field_strength(const double* dU, int anti_pbc, hipStream_t st) {
+    hipLaunchKernelGGL(field_strength_kernel, dim3((unsigned)planes.max_blocks, 6), dim3(fs::THREADS), 0, st, F, part, dU, planes, V, anti_pbc);
+    DDAMG_HIP_CHECK(hipGetLastError());
+  }
+  void assemble(double* dC, double m0, double csw, hipStream_t st) {
+    hipLaunchKernelGGL(clover_assemble_kernel, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, dC, F, V, m0, csw, gamma_products_fs());
+    DDAMG_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(plaquette_sum_kernel, dim3(1), dim3(256), 0, st, total(), part, 6 * (size_t)planes.max_blocks);
+    DDAMG_HIP_CHECK(hipGetLastError());
+  }
+  double plaquette(hipStream_t st) {   // average over sites and planes; waits for the stream
+    double sum = 0;
+    DDAMG_HIP_CHECK(hipMemcpyAsync(&sum, total(), sizeof(double), hipMemcpyDeviceToHost, st));
+    DDAMG_HIP_CHECK(hipStreamSynchronize(st));
+    return sum / ((double)V * 6.0);
+  }
+};
+}  // namespace
+
+double gauge_to_operator_resident(const int L[4], const double* dU_hopp, const double* dU_clover, int anti_pbc, double m0, double csw, double* dD,
+                                  double* dC, hipStream_t st) {
+  ResidentWork w(L);
+  const size_t n = 72 * w.V, vol3 = (size_t)L[1] * L[2] * L[3];
+  hipLaunchKernelGGL(links_to_D_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dD, dU_hopp, n, anti_pbc, (size_t)(L[0] - 1) * vol3 * 72);
+  DDAMG_HIP_CHECK(hipGetLastError());
+  w.field_strength(dU_clover, anti_pbc, st);
+  w.assemble(dC, m0, csw, st);
+  return w.plaquette(st);
+}
+
+double clover_kernels_timed(const int L[4], const double* dU, double m0, double csw, int which, int reps, hipEvent_t e0, hipEvent_t e1, hipStream_t st,
+                            float* ms) {
+  DDAMG_REQUIRE(which >= 0 && which <= 2 && reps >= 1, "clover_kernels_timed: which is 0, 1 or 2 and reps >= 1");
+  ResidentWork w(L);
+  DeviceBuffer<double> dC, dP;
+  dC.alloc(84 * w.V);
+  Lat g, none; for (int mu = 0; mu < 4; mu++) { g.L[mu] = L[mu]; none.L[mu] = 0; }
+  if (which == 1) dP.alloc(w.V);
+  for (int r = -1; r < reps; r++) {   // r = -1: untimed first launch
+    if (r == 0) DDAMG_HIP_CHECK(hipEventRecord(e0, st));
+    if (which == 1) {
+      hipLaunchKernelGGL(clover_kernel, dim3((unsigned)((w.V + 63) / 64)), dim3(64), 0, st, dC, dP, dU, g, g, none, (int)w.V, m0, csw, gamma_products());
+      DDAMG_HIP_CHECK(hipGetLastError());
+    } else {
+      w.field_strength(dU, 0, st);
+      if (which == 2) w.assemble(dC, m0, csw, st);
+    }
+  }
+  DDAMG_HIP_CHECK(hipEventRecord(e1, st));
+  DDAMG_HIP_CHECK(hipEventSynchronize(e1));
+  DDAMG_HIP_CHECK(hipEventElapsedTime(ms, e0, e1));
+  *ms /= (float)reps;
+  if (which == 1) {
+    std::vector<double> hp(w.V);
+    DDAMG_HIP_CHECK(hipMemcpy(hp.data(), dP, sizeof(double) * w.V, hipMemcpyDeviceToHost));
+    double s = 0; for (size_t i = 0; i < w.V; i++) s += hp[i];
+    return s / ((double)w.V * 6.0);
+  }
+  if (which == 0) w.assemble(dC, m0, csw, st);
+  return w.plaquette(st);
 }
 
 }  // namespace ddamg

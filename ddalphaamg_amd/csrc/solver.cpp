@@ -681,6 +681,22 @@ int ddamg_hip_solve(ddamg_hip_ctx* c, double* x_lex, const double* b_lex, double
   DDAMG_API_END
 }
 
+int ddamg_hip_solve_device(ddamg_hip_ctx* c, double* x_dev_lex, const double* b_dev_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c, "null argument");
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 24 * V;
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  ddamg_require_device_array(c, x_dev_lex, nb, "ddamg_hip_solve_device");
+  ddamg_require_device_array(c, b_dev_lex, nb, "ddamg_hip_solve_device");
+  ddamg_require_disjoint(x_dev_lex, b_dev_lex, nb, "ddamg_hip_solve_device");
+  solve_core(c, tol,
+             [&](double* dst) { vec_from_lex<double>(dst, b_dev_lex, c->levels[0]->d_lex_of_site, V, 12, c->stream); },
+             [&](const double* src) { vec_to_lex<double>(x_dev_lex, src, c->levels[0]->d_lex_of_site, V, 12, c->stream); },
+             iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
 int ddamg_hip_solve_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c && x && b, "null argument");
@@ -750,6 +766,27 @@ int ddamg_hip_preconditioner(ddamg_hip_ctx* c, double* out_lex, const double* in
   c->outer.prec(c->outer.x, nullptr, c->outer.b, NO_RES);
   vec_to_lex<double>(st, c->outer.x, c->levels[0]->d_lex_of_site, V, 12, c->stream);
   DDAMG_HIP_CHECK(hipMemcpyAsync(out_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->last_coarse_iter = c->mg32 ? c->mg32->coarse_iter_count : c->mg64->coarse_iter_count;
+  DDAMG_API_END
+}
+
+int ddamg_hip_preconditioner_device(ddamg_hip_ctx* c, double* out_dev_lex, const double* in_dev_lex) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c, "null argument");
+  DDAMG_REQUIRE(c->setup_done && c->par.method > 0, "setup has not been run");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 24 * V;
+  ddamg_require_device_array(c, out_dev_lex, nb, "ddamg_hip_preconditioner_device");
+  ddamg_require_device_array(c, in_dev_lex, nb, "ddamg_hip_preconditioner_device");
+  ddamg_require_disjoint(out_dev_lex, in_dev_lex, nb, "ddamg_hip_preconditioner_device");
+  ensure_outer(c);
+  vec_from_lex<double>(c->outer.b, in_dev_lex, c->levels[0]->d_lex_of_site, V, 12, c->stream);
+  if (c->mg32) c->mg32->coarse_iter_count = 0;
+  if (c->mg64) c->mg64->coarse_iter_count = 0;
+  c->outer.prec(c->outer.x, nullptr, c->outer.b, NO_RES);
+  vec_to_lex<double>(out_dev_lex, c->outer.x, c->levels[0]->d_lex_of_site, V, 12, c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   c->last_coarse_iter = c->mg32 ? c->mg32->coarse_iter_count : c->mg64->coarse_iter_count;
   DDAMG_API_END

@@ -93,6 +93,33 @@ int ddamg_hip_set_gauge(ddamg_hip_ctx* ctx, const double* gauge_lex, int anti_pb
  * from `clover_gauge_lex` (open boundaries: time links dropped from the hopping term near the boundary). */
 int ddamg_hip_set_gauge2(ddamg_hip_ctx* ctx, const double* hopp_gauge_lex, const double* clover_gauge_lex, int anti_pbc, double* plaquette);
 
+/* ---- fields that live in device memory ----------------------------------------------------------------------
+ * Twins of the entry points that carry lattice data, for a host application that keeps its fields on the context's GPU (an
+ * HMC or measurement code on the same card, a torch program).  The arrays have exactly the element order of their host twins
+ * -- links [V][4][3x3 row-major complex] fp64, vectors [V][ndof] complex fp64, both lexicographic T,Z,Y,X with X fastest -- and
+ * lie in the memory of the context's device.  Every device pointer is checked with hipPointerGetAttributes before anything is
+ * launched: a null pointer, a host pointer, memory of another device or an allocation that is too small returns non-zero with a
+ * message and leaves the context as it was.  Input arrays are never written; the output and the input array of one call must
+ * not overlap.  The calls are synchronous towards the host, as their twins are: they return after the result is complete, and
+ * the caller guarantees that whatever produced the input has finished (the context works on a stream of its own). */
+/* ddamg_hip_set_gauge (dirac_setup, src/dirac.c:60-168) from links in device memory.  Nothing crosses PCIe: D = U/2 and the clover
+ * term are computed into device staging arrays straight from the caller's links (the anti-periodic sign, which read_conf writes
+ * into the links, src/io.c:536-541, is applied in the loads), the plaquette is summed on the device, and both precisions'
+ * operators are laid out from the staging arrays.  Same effect on the context as ddamg_hip_set_gauge, except that the host copy
+ * behind ddamg_hip_get_operator is not filled: it is rebuilt from the fp64 operator when it is asked for.  Refused, with a message
+ * that names ddamg_hip_set_gauge, on a context whose fine level is divided over processes (process_grid entries > 1 or -1),
+ * because the clover term then needs the neighbours' links. */
+int ddamg_hip_set_gauge_device(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int anti_pbc, double* plaquette);
+/* ddamg_hip_set_gauge2 (dirac_setup( hopp, clover ), src/dirac.c:60-168) from two fields in device memory: D from the first, the
+ * clover term and the plaquette from the second, one layout pass.  Equal pointers behave as ddamg_hip_set_gauge_device. */
+int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* ctx, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette);
+/* Milliseconds per launch of the kernels that turn links in device memory into the clover term, between the context's timer events
+ * (as ddamg_hip_timer_begin / _end) after one untimed launch: which = 0 the field-strength kernel of ddamg_hip_set_gauge_device,
+ * 1 the clover kernel of ddamg_hip_set_gauge, 2 the field-strength, assembly and plaquette-sum kernels together.  *plaquette: the
+ * average plaquette the kernels give.  The context is not changed.  For measurements (tools/device_interface_bench.py).  No
+ * counterpart in the reference. */
+int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int which, int reps, float* milliseconds, double* plaquette);
+
 /* direct upload of an operator in the reference's own storage (g.op_double.D: [V][36] complex,
  * g.op_double.clover: [V][42] complex; src/dirac.c:80,386-398) -- the path behind
  * dd_alpha_amg_get_gauge_pointer / dd_alpha_amg_get_clover_pointer (src/dirac.c:171-176). */
@@ -116,6 +143,11 @@ int ddamg_hip_vec_destroy(ddamg_hip_ctx* ctx, ddamg_hip_vec* v);
 /* replaces trans_PRECISION / trans_back_PRECISION (src/schwarz_generic.c:1807-1846) */
 int ddamg_hip_vec_upload(ddamg_hip_ctx* ctx, ddamg_hip_vec* v, const double* host_lex);
 int ddamg_hip_vec_download(ddamg_hip_ctx* ctx, const ddamg_hip_vec* v, double* host_lex);
+
+/* the same from / into an array in device memory (contract: "fields that live in device memory" above): trans_PRECISION /
+ * trans_back_PRECISION (src/schwarz_generic.c:1807-1846) without the copy through the staging buffer */
+int ddamg_hip_vec_upload_device(ddamg_hip_ctx* ctx, ddamg_hip_vec* v, const double* dev_lex);
+int ddamg_hip_vec_download_device(ddamg_hip_ctx* ctx, const ddamg_hip_vec* v, double* dev_lex);
 
 /* replaces d_plus_clover_float / d_plus_clover_double (src/dirac_generic.c:159-277) */
 int ddamg_hip_dirac_apply(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in);
@@ -249,12 +281,19 @@ int ddamg_hip_kcycle_many(ddamg_hip_ctx* ctx, int ncols, ddamg_hip_vec* const* x
  * relres = true relative residual ||b - D x|| / ||b|| recomputed in fp64 (FGMRES_RESTEST). */
 int ddamg_hip_solve(ddamg_hip_ctx* ctx, double* x_lex, const double* b_lex, double tol,
                     int* iterations, int* coarse_iterations, double* relres);
-/* the same solve on device-resident vectors (fine level, precision 64, filled with ddamg_hip_vec_upload or by other
- * device code): nothing crosses PCIe -- the form a GPU-resident host application uses */
+/* the same solve on device-resident vectors (fine level, precision 64, filled with ddamg_hip_vec_upload, ddamg_hip_vec_upload_device
+ * or by other device code): nothing crosses PCIe -- the form a GPU-resident host application uses */
 int ddamg_hip_solve_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
                         int* iterations, int* coarse_iterations, double* relres);
 /* replaces preconditioner() (src/preconditioner.c:25-69): one V-cycle, fp64 lexicographic in/out */
 int ddamg_hip_preconditioner(ddamg_hip_ctx* ctx, double* out_lex, const double* in_lex);
+/* ddamg_hip_solve (wilson_driver -> fgmres_double + preconditioner, src/top_level.c:64-104) and ddamg_hip_preconditioner
+ * (preconditioner(), src/preconditioner.c:25-69) on lexicographic fp64 arrays in device memory (contract: "fields that live in
+ * device memory" above): the layout kernels read and write the caller's arrays, nothing crosses PCIe.  They work on process grids
+ * as their twins do: the arrays are the process's own part. */
+int ddamg_hip_solve_device(ddamg_hip_ctx* ctx, double* x_dev_lex, const double* b_dev_lex, double tol,
+                           int* iterations, int* coarse_iterations, double* relres);
+int ddamg_hip_preconditioner_device(ddamg_hip_ctx* ctx, double* out_dev_lex, const double* in_dev_lex);
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES) */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
 
