@@ -67,23 +67,12 @@ Multigrid<T>::Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const s
       if (d == 0) {
         // the forward faces of an aggregate in compact form (AggFaces, transfer.h) -- where every aggregate has the same shape
         // and site order (it has, with the aggregate -> block -> parity ordering, unless blocks of odd extent alternate)
-        const int as = lv.fip.agg_sites, nagg = lv.fip.num_aggs;
-        bool same = as > 0 && as < 65536 && (size_t)as * nagg == (size_t)g.V;
-        for (int s = 0; same && s < g.V; s++) same = (g.agg_face[s] & 0xF) == (g.agg_face[s % as] & 0xF);
-        if (same) {
-          std::vector<unsigned short> tab((size_t)4 * as, 0), list;
-          AggFaces& af = lv.agg_faces;
-          af.agg_sites = as;
-          for (int mu = 0; mu < 4; mu++) {
-            af.loff[mu] = (int)list.size();
-            for (int i = 0; i < as; i++)
-              if (g.agg_face[i] & (1u << mu)) { tab[(size_t)mu * as + i] = (unsigned short)(list.size() - af.loff[mu]); list.push_back((unsigned short)i); }
-            af.nface[mu] = (int)list.size() - af.loff[mu];
-          }
-          tab.insert(tab.end(), list.begin(), list.end());
+        std::vector<unsigned short> tab;
+        AggFaces& af = lv.agg_faces;
+        if (agg_face_tables(g, af, tab)) {
           lv.d_agg_tables.upload(tab);
           af.rank = lv.d_agg_tables;
-          af.list = lv.d_agg_tables + (size_t)4 * as;
+          af.list = lv.d_agg_tables + (size_t)4 * af.agg_sites;
         }
       }
       for (int mu = 0; mu < 4; mu++) {

@@ -13,6 +13,7 @@
 #pragma once
 #include "common.h"
 #include "geometry.h"
+#include <vector>
 
 namespace ddamg {
 
@@ -37,6 +38,28 @@ struct AggFaces {
     return naggs * o;
   }
 };
+
+// The host side of AggFaces for the level g: af's counts and offsets, and `tab` = rank [4][agg_sites] followed by the face lists
+// (the caller uploads it: af.rank = its start, af.list = its start + 4 * agg_sites).  False, with af left as it was, where the
+// aggregates do not all have the same shape and site order (they have, with the aggregate -> block -> parity ordering, unless
+// blocks of odd extent alternate).
+inline bool agg_face_tables(const Geometry& g, AggFaces& af, std::vector<unsigned short>& tab) {
+  const int as = g.agg_sites, nagg = g.num_aggs;
+  bool same = as > 0 && as < 65536 && (size_t)as * nagg == (size_t)g.V;
+  for (int s = 0; same && s < g.V; s++) same = (g.agg_face[s] & 0xF) == (g.agg_face[s % as] & 0xF);
+  if (!same) return false;
+  std::vector<unsigned short> list;
+  tab.assign((size_t)4 * as, 0);
+  af.agg_sites = as;
+  for (int mu = 0; mu < 4; mu++) {
+    af.loff[mu] = (int)list.size();
+    for (int i = 0; i < as; i++)
+      if (g.agg_face[i] & (1u << mu)) { tab[(size_t)mu * as + i] = (unsigned short)(list.size() - af.loff[mu]); list.push_back((unsigned short)i); }
+    af.nface[mu] = (int)list.size() - af.loff[mu];
+  }
+  tab.insert(tab.end(), list.begin(), list.end());
+  return true;
+}
 
 template <typename T>
 struct Interpolation {

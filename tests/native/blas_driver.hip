@@ -10,66 +10,11 @@
 #include "blas.h"
 #include "krylov.h"
 #include "coarse_lockstep.h"
-#include <cstring>
-#include <fstream>
-#include <map>
-#include <sstream>
+#include "driver_case.h"
 
 using namespace ddamg;
 
-static void need(bool ok, const std::string& what) { if (!ok) throw std::runtime_error("blas_driver: " + what); }
-
-struct Case {
-  std::string dir;
-  std::map<std::string, std::string> kv;
-  explicit Case(const std::string& d) : dir(d) {
-    std::ifstream f(dir + "/case.txt");
-    need((bool)f, "cannot read " + dir + "/case.txt");
-    std::string k, v;
-    while (f >> k >> v) kv[k] = v;
-  }
-  bool has(const std::string& k) const { return kv.count(k) != 0; }
-  const std::string& str(const std::string& k) const {
-    auto it = kv.find(k);
-    need(it != kv.end(), "case lacks '" + k + "'");
-    return it->second;
-  }
-  long long i(const std::string& k) const { return std::stoll(str(k)); }
-  long long i(const std::string& k, long long dflt) const { return has(k) ? i(k) : dflt; }
-  unsigned long long u(const std::string& k) const { return std::stoull(str(k)); }
-  double d(const std::string& k) const { return std::stod(str(k)); }
-  double d(const std::string& k, double dflt) const { return has(k) ? d(k) : dflt; }
-
-  template <typename U> std::vector<U> read(const std::string& name) const {
-    std::ifstream f(dir + "/" + name + ".bin", std::ios::binary | std::ios::ate);
-    need((bool)f, "cannot read " + name + ".bin");
-    const size_t bytes = (size_t)f.tellg();
-    need(bytes % sizeof(U) == 0, name + ".bin: not a whole number of elements");
-    std::vector<U> v(bytes / sizeof(U));
-    f.seekg(0);
-    f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)bytes);
-    return v;
-  }
-  template <typename U> void write(const std::string& name, const U* p, size_t n) const {
-    std::ofstream f(dir + "/out_" + name + ".bin", std::ios::binary);
-    f.write(reinterpret_cast<const char*>(p), (std::streamsize)(sizeof(U) * n));
-    need((bool)f, "cannot write out_" + name + ".bin");
-  }
-  View view() const {
-    return View{(int)i("rows"), (size_t)i("stride"), (size_t)i("off"), (size_t)i("len")};
-  }
-};
-
-// device array with its length
-template <typename U>
-struct Dev {
-  DeviceBuffer<U> p;
-  size_t n = 0;
-  void from(const std::vector<U>& h) { n = h.size(); p.alloc(n ? n : 1); if (n) DDAMG_HIP_CHECK(hipMemcpy(p, h.data(), sizeof(U) * n, hipMemcpyHostToDevice)); }
-  void load(const Case& c, const std::string& name) { from(c.read<U>(name)); }
-  std::vector<U> host() const { std::vector<U> h(n); if (n) DDAMG_HIP_CHECK(hipMemcpy(h.data(), p, sizeof(U) * n, hipMemcpyDeviceToHost)); return h; }
-  void store(const Case& c, const std::string& name) const { auto h = host(); c.write(name, h.data(), h.size()); }
-};
+static View view_of(const Case& c) { return View{(int)c.i("rows"), (size_t)c.i("stride"), (size_t)c.i("off"), (size_t)c.i("len")}; }
 
 // one past the last real the view touches
 static size_t view_end(const View& v) { return v.total() == 0 ? 0 : v.off + (size_t)(v.rows - 1) * v.stride + v.len; }
@@ -86,7 +31,7 @@ static void run_ew(const Case& c, hipStream_t st) {
     const long long vv[4] = {v.rows, (long long)v.stride, (long long)v.off, (long long)v.len};
     c.write("view", vv, 4);
   } else {
-    v = c.view();
+    v = view_of(c);
   }
   const bool inplace = c.i("inplace", 0) != 0;
   Dev<T> z, x, y;
@@ -116,7 +61,7 @@ static void run_ew(const Case& c, hipStream_t st) {
 template <typename T>
 static void run_reduce(const Case& c, hipStream_t st) {
   const std::string op = c.str("op");
-  const View v = c.view();
+  const View v = view_of(c);
   ReduceWork rw;
   rw.init((int)c.i("max_m", 12));
   Dev<T> x, y;
@@ -146,7 +91,7 @@ static void run_reduce(const Case& c, hipStream_t st) {
 
 template <typename T>
 static void run_multi_axpy(const Case& c, hipStream_t st) {
-  const View v = c.view();
+  const View v = view_of(c);
   const int m = (int)c.i("m");
   const size_t xstride = (size_t)c.i("xstride");
   Dev<T> w, X;
@@ -160,7 +105,7 @@ static void run_multi_axpy(const Case& c, hipStream_t st) {
 
 template <typename T>
 static void run_panel(const Case& c, hipStream_t st) {
-  const View v = c.view();
+  const View v = view_of(c);
   const int m = (int)c.i("m"), nb = (int)c.i("nb");
   const size_t xstride = (size_t)c.i("xstride"), wstride = (size_t)c.i("wstride");
   ReduceWork rw;
@@ -477,6 +422,7 @@ static void run_typed(const Case& c, const std::string& op, hipStream_t st) {
 
 int main(int argc, char** argv) {
   if (argc != 2) { fprintf(stderr, "usage: blas_driver <case directory>\n"); return 64; }
+  driver_name = "blas_driver";
   try {
     const Case c(argv[1]);
     const std::string op = c.str("op");

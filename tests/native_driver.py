@@ -1,4 +1,5 @@
-"""Starts tests/native/blas_driver (one operation of blas.h / krylov.h per process) and reads what it wrote.
+"""Starts a host program of tests/native/ -- blas_driver (one operation of blas.h / krylov.h per process) or transfer_driver
+(operations of transfer.h / coarse_mg.h on one transfer object per process) -- and reads what it wrote.
 
 A case is a directory: case.txt with "key value" lines and raw little-endian arrays <name>.bin; the driver answers with
 out_<name>.bin.  Every invocation is a child process with a time limit.  A driver that died of a signal, aborted, or ran into
@@ -10,7 +11,7 @@ import subprocess
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(REPO, "tests", "native", "blas_driver")
+NATIVE = os.path.join(REPO, "tests", "native")
 
 _dead = None   # why the driver is not started any more
 
@@ -27,8 +28,8 @@ class Result:
         return np.fromfile(os.path.join(self.path, "out_" + name + ".bin"), dtype=dtype)
 
 
-def run(path, scalars, arrays, timeout=60, expect_error=None):
-    """Write the case into `path` (a fresh directory of the test), run the driver once, return a Result.
+def run(path, scalars, arrays, timeout=60, expect_error=None, driver="blas_driver"):
+    """Write the case into `path` (a fresh directory of the test), run the program `driver` once, return a Result.
 
     scalars: {key: value} for case.txt; arrays: {name: ndarray}, written as they are (dtype included).
     expect_error: a text the driver must refuse the case with (exit status 2, text on stderr); otherwise status 0 is required.
@@ -36,8 +37,9 @@ def run(path, scalars, arrays, timeout=60, expect_error=None):
     global _dead
     if _dead is not None:
         raise DriverError("the native driver is not started again in this session: " + _dead)
-    if not os.path.isfile(DRIVER):
-        raise DriverError("tests/native/blas_driver is not built (make -C ddalphaamg_amd/csrc)")
+    program = os.path.join(NATIVE, driver)
+    if not os.path.isfile(program):
+        raise DriverError(f"tests/native/{driver} is not built (make -C ddalphaamg_amd/csrc)")
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "case.txt"), "w") as f:
         for k, v in scalars.items():
@@ -45,7 +47,7 @@ def run(path, scalars, arrays, timeout=60, expect_error=None):
     for name, a in arrays.items():
         np.ascontiguousarray(a).tofile(os.path.join(path, name + ".bin"))
     try:
-        p = subprocess.run([DRIVER, str(path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
+        p = subprocess.run([program, str(path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
     except subprocess.TimeoutExpired:
         _dead = f"a case ran into its time limit of {timeout} s ({scalars.get('op')})"
         raise DriverError(_dead)
