@@ -48,7 +48,7 @@ class CoarseMulti {
   size_t batch_elems() const { return (size_t)V_ * n_ * LOCKSTEP_COLS; }      // complex numbers per batch
   size_t next_batch_elems() const { return (size_t)Vc_ * nc_ * LOCKSTEP_COLS; }
   float2* work(int i);                      // lazily allocated batches of this level (i < 24)
-  float2* next_work(int i);                 // ... of the next level (i < 4)
+  float2* next_work(int i);                 // ... of the next level (i < 4): 0 restricted right-hand side, 1 nested solution, 2 next_iterate()
 
   void gather(float2* Wb, const float* src, size_t sstride, int ncols) const { batch_gather(Wb, src, sstride, ncols, (size_t)V_ * n_, st_); }
   void scatter(float* dst, size_t dstride, const float2* Wb, int ncols) const { batch_scatter(dst, dstride, Wb, ncols, (size_t)V_ * n_, st_); }
@@ -66,20 +66,38 @@ class CoarseMulti {
   void scale_inv(float2* out, const float2* w, const double* d_norm2) const { batch_scale_inv(out, w, d_norm2, batch_elems(), st_); }
   void normalize_columns(float2* w) { dots(w, batch_elems(), 1, w, d_h_); scale_inv(w, w, d_h_); }   // w_c <- w_c / ||w_c||
 
-  // vcycle_PRECISION(phi, NULL, eta, _NO_RES) on this level for all columns, the next level being the coarsest:
+  // vcycle_PRECISION(phi, NULL, eta, _NO_RES) on this level for all columns.  Next level the coarsest (nested == nullptr):
   //   restriction -> coarsest solves in lockstep (a column that needs more steps than the lockstep basis holds goes through
   //   `one_solve(column vector b -> x)`) -> interpolation -> post_smooth cycles of the smoother.  Returns the coarsest iterations.
-  // active[c] == 0: the column is left out of the coarsest solve (its interpolated correction is zero).
+  // Next level another intermediate one (nested): restriction -> that level's K-cycle for all columns, with its own restart
+  //   length, tolerance and smoother counts (fgmres_PRECISION(&l->next_level->p), src/vcycle_generic.c:103-114) -> interpolation
+  //   -> smoother.  The coarsest solver and the hand-over go down with it.
+  // active[c] == 0: the column is left out of everything below this level (its interpolated correction is zero).
   // one_solve(): the one-at-a-time coarsest solve of the column vector cvec_b into cvec_x (it counts its own iterations)
   typedef std::function<void()> OneSolve;
+  struct Nested {
+    CoarseMulti* level = nullptr;      // the next level
+    int m = 0, cycles = 0;             // its K-cycle: restart length, restart cycles,
+    double tol = 0;                    // relative tolerance
+    int post_smooth = 0;               // smoother cycles of its V-cycle
+    const Nested* nested = nullptr;    // the level below it, nullptr: the coarsest
+  };
   int vcycle(float2* phi, const float2* eta, int ncols, int post_smooth, LockstepCoarseSolver& coarsest, const OneSolve& one_solve,
-             float* cvec_x, float* cvec_b, const unsigned char* active);
+             float* cvec_x, float* cvec_b, const unsigned char* active, const Nested* nested = nullptr);
 
   // fgmres_PRECISION with the V-cycle above as right preconditioner, all columns in lockstep (the K-cycle of the level: restart
   // length m, at most `cycles` restart cycles, relative tolerance tol, initial guess zero).  X, B: batches.  iters[c]: iterations
   // of column c.  Returns the number of coarsest-level iterations.
+  // active[c] == 0 (active != nullptr): column c takes no part -- neither X nor iters[c] is written for it, and it is left out
+  // of every V-cycle.  The Arnoldi state lives in this object's own slab: a nested level's K-cycle does not touch it.
   int kcycle(float2* X, const float2* B, int ncols, int m, int cycles, double tol, int post_smooth, LockstepCoarseSolver& coarsest,
-             const OneSolve& one_solve, float* cvec_x, float* cvec_b, int* iters);
+             const OneSolve& one_solve, float* cvec_x, float* cvec_b, int* iters, const unsigned char* active = nullptr,
+             const Nested* nested = nullptr);
+  // nested form: the next level's K-cycle iterate of every column as the last V-cycle in which the column was active left it
+  // (test_vector_PRECISION_update of the deeper level reads it, src/setup_generic.c:418-438); a batch of the next level
+  float2* next_iterate() { return next_work(2); }
+  // dst[.][c] = src[.][c] for the columns c with active[c] != 0 (nullptr: all); other columns of dst are not written
+  void copy_columns(float2* dst, const float2* src, size_t elems, int ncols, const unsigned char* active) const;
 
  private:
   const CoarseOp<float>* op_ = nullptr;
@@ -91,7 +109,7 @@ class CoarseMulti {
   DeviceBuffer<short> d_blk_nb_;          // [8][BS] in-block neighbour or -1
   DeviceBuffer<float2> r_, latest_, x_;   // smoother state (batches)
   std::vector<DeviceBuffer<float2>> work_, next_work_;
-  DeviceBuffer<float2> kslab_;            // K-cycle: r, w, V[0..m], Z[0..m-1] in one slab
+  DeviceBuffer<float2> kslab_;            // K-cycle: r, w, the iterate, V[0..m], Z[0..m-1] in one slab
   int kslab_m_ = 0;
   mutable DeviceBuffer<double> d_partial_;
   DeviceBuffer<double> d_h_, d_coef_;

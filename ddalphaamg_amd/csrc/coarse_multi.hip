@@ -300,6 +300,11 @@ __global__ void cm_set_column_kernel(float2* __restrict__ Wb, const float2* __re
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < rows) Wb[e * NC + c] = src[e];
 }
+// the columns whose bit is set in `mask`
+__global__ void cm_copy_columns_kernel(float2* __restrict__ dst, const float2* __restrict__ src, unsigned mask, size_t elems) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < elems && ((mask >> (unsigned)(e % NC)) & 1u)) dst[e] = src[e];
+}
 __global__ void cm_sub_kernel(float2* __restrict__ z, const float2* __restrict__ a, const float2* __restrict__ b, size_t elems) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < elems) { const float2 u = a[e], v = b[e]; z[e] = make_float2(u.x - v.x, u.y - v.y); }
@@ -364,8 +369,8 @@ void CoarseMulti::init(const Geometry& g, const CoarseOp<float>* op, const Coars
 
 size_t CoarseMulti::workspace_bytes(const Geometry& g, int n, int restart_length) {
   const size_t batch = sizeof(float2) * (size_t)g.V * n * LOCKSTEP_COLS;
-  // r, latest, x of the smoother; residual, w and the two bases of the K-cycle; up to six work() batches of the callers
-  return batch * (size_t)(3 + 2 * restart_length + 3 + 6) + sizeof(float4) * (size_t)g.V * 9 * mfma_op_matrix_elems(n);
+  // r, latest, x of the smoother; residual, w, iterate and the two bases of the K-cycle; up to six work() batches of the callers
+  return batch * (size_t)(3 + 2 * restart_length + 4 + 6) + sizeof(float4) * (size_t)g.V * 9 * mfma_op_matrix_elems(n);
 }
 
 float2* CoarseMulti::work(int i) {
@@ -375,7 +380,10 @@ float2* CoarseMulti::work(int i) {
 }
 float2* CoarseMulti::next_work(int i) {
   if ((int)next_work_.size() <= i) next_work_.resize(i + 1);
-  if (!next_work_[i]) next_work_[i].alloc(next_batch_elems());
+  if (!next_work_[i]) {
+    next_work_[i].alloc(next_batch_elems());
+    DDAMG_HIP_CHECK(hipMemsetAsync(next_work_[i], 0, sizeof(float2) * next_batch_elems(), st_));   // next_iterate(): columns that never took part read as zero
+  }
   return next_work_[i];
 }
 
@@ -468,11 +476,34 @@ void CoarseMulti::column_norms2(const float2* w, double* norms2) {
   for (int c = 0; c < NC; c++) norms2[c] = h_h_[2 * c];
 }
 
+void CoarseMulti::copy_columns(float2* dst, const float2* src, size_t elems, int ncols, const unsigned char* active) const {
+  unsigned mask = 0;
+  for (int c = 0; c < ncols; c++) if (!active || active[c]) mask |= 1u << c;
+  if (!mask) return;
+  hipLaunchKernelGGL(cm_copy_columns_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st_, dst, src, mask, elems);
+  DDAMG_HIP_CHECK(hipGetLastError());
+}
+
 int CoarseMulti::vcycle(float2* phi, const float2* eta, int ncols, int post_smooth, LockstepCoarseSolver& coarsest, const OneSolve& one_solve,
-                        float* cvec_x, float* cvec_b, const unsigned char* active) {
-  float2 *bc = next_work(0), *xc = coarsest.batch(0);
-  const size_t crows = (size_t)Vc_ * nc_;
+                        float* cvec_x, float* cvec_b, const unsigned char* active, const Nested* nested) {
+  float2* bc = next_work(0);
   restrict_to(bc, eta);
+  if (nested) {
+    // the next level's K-cycle for all columns; a column that is left out gets a zero correction, and its last iterate stays
+    CoarseMulti& nx = *nested->level;
+    DDAMG_REQUIRE(nx.ready() && nx.batch_elems() == next_batch_elems(), "nested V-cycle: the next level's batches do not match this level's transfer");
+    float2* xc = next_work(1);
+    std::vector<int> its(ncols, 0);
+    DDAMG_HIP_CHECK(hipMemsetAsync(xc, 0, sizeof(float2) * next_batch_elems(), st_));
+    const int total = nx.kcycle(xc, bc, ncols, nested->m, nested->cycles, nested->tol, nested->post_smooth, coarsest, one_solve, cvec_x, cvec_b, its.data(), active,
+                                nested->nested);
+    copy_columns(next_iterate(), xc, next_batch_elems(), ncols, active);
+    interpolate(phi, xc, false);
+    smooth(phi, eta, post_smooth, RES);
+    return total;
+  }
+  float2* xc = coarsest.batch(0);
+  const size_t crows = (size_t)Vc_ * nc_;
   std::vector<int> its(ncols, 0);
   const int total = coarsest.solve_batch(nullptr, bc, ncols, its.data(), active);   // bc is kept: the solve works on a copy
   for (int c = 0; c < ncols; c++)
@@ -490,21 +521,23 @@ int CoarseMulti::vcycle(float2* phi, const float2* eta, int ncols, int post_smoo
 
 // fgmres_PRECISION (src/linsolve_generic.c:219-413) for all columns: the control flow of Gmres<T>::solve (krylov.h) with an index
 int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles, double tol, int post_smooth, LockstepCoarseSolver& coarsest,
-                        const OneSolve& one_solve, float* cvec_x, float* cvec_b, int* iters) {
+                        const OneSolve& one_solve, float* cvec_x, float* cvec_b, int* iters, const unsigned char* active, const Nested* nested) {
   typedef std::complex<double> cd;
   DDAMG_REQUIRE(ready() && ncols <= NC && m + 2 <= ld_h_, "lockstep K-cycle: not set up, or restart length too large");
   const size_t el = batch_elems(), bytes = sizeof(float2) * el;
   if (!kslab_ || kslab_m_ < m) {
-    kslab_.alloc(el * (size_t)(2 * m + 3));
+    kslab_.alloc(el * (size_t)(2 * m + 4));
     kslab_m_ = m;
   }
-  float2 *r = kslab_, *w = kslab_ + el, *Vb = kslab_ + 2 * el, *Zb = Vb + (size_t)(m + 1) * el;
+  // the iterate is built in the slab and handed to the caller's batch at the end, the columns that take part only
+  float2 *r = kslab_, *w = kslab_ + el, *Xk = kslab_ + 2 * el, *Vb = kslab_ + 3 * el, *Zb = Vb + (size_t)(m + 1) * el;
   const int ld = m + 2;
   struct Col { std::vector<cd> H, gamma, c, s; double norm_r0 = 1; int j = -1, iter = 0; bool finish = false; };
   std::vector<Col> cols(ncols);
   for (auto& q : cols) { q.H.assign((size_t)(m + 1) * ld, cd(0)); q.gamma.assign(ld, cd(0)); q.c.assign(ld, cd(0)); q.s.assign(ld, cd(0)); }
   std::vector<unsigned char> in_cycle(ncols, 1);
-  DDAMG_HIP_CHECK(hipMemsetAsync(X, 0, bytes, st_));
+  for (int c = 0; c < ncols; c++) if (active && !active[c]) cols[c].finish = true;
+  DDAMG_HIP_CHECK(hipMemsetAsync(Xk, 0, bytes, st_));
   int coarse_total = 0;
   for (int ol = 0; ol < cycles; ol++) {
     int open = 0;
@@ -512,7 +545,7 @@ int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles
     if (!open) break;
     if (ol == 0) DDAMG_HIP_CHECK(hipMemcpyAsync(r, B, bytes, hipMemcpyDeviceToDevice, st_));
     else {
-      apply(w, X);
+      apply(w, Xk);
       hipLaunchKernelGGL(cm_sub_kernel, dim3((unsigned)((el + 255) / 256)), dim3(256), 0, st_, r, B, w, el);
     }
     dots(r, el, 1, r, d_h_);
@@ -534,7 +567,7 @@ int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles
     for (int il = 0; il < m && open > 0; il++) {
       steps++;
       float2 *Vj = Vb + (size_t)il * el, *Zj = Zb + (size_t)il * el;
-      coarse_total += vcycle(Zj, Vj, ncols, post_smooth, coarsest, one_solve, cvec_x, cvec_b, in_cycle.data());
+      coarse_total += vcycle(Zj, Vj, ncols, post_smooth, coarsest, one_solve, cvec_x, cvec_b, in_cycle.data(), nested);
       apply(w, Zj);
       dots(Vb, el, il + 1, w, d_h_);                                // classical Gram-Schmidt + separate norm
       axpy(w, Vb, el, il + 1, d_h_, -1.0);
@@ -583,11 +616,12 @@ int CoarseMulti::kcycle(float2* X, const float2* B, int ncols, int m, int cycles
         q.j = -1;
       }
       DDAMG_HIP_CHECK(hipMemcpyAsync(d_coef_, h_coef_, sizeof(double) * 2 * NC * steps, hipMemcpyHostToDevice, st_));
-      axpy(X, Zb, el, steps, d_coef_, +1.0);
+      axpy(Xk, Zb, el, steps, d_coef_, +1.0);
       DDAMG_HIP_CHECK(hipStreamSynchronize(st_));    // h_coef_ is rewritten by the next cycle
     }
   }
-  for (int c = 0; c < ncols; c++) iters[c] = cols[c].iter;
+  copy_columns(X, Xk, el, ncols, active);
+  for (int c = 0; c < ncols; c++) if (!active || active[c]) iters[c] = cols[c].iter;
   return coarse_total;
 }
 

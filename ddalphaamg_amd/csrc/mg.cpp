@@ -471,7 +471,7 @@ bool Multigrid<T>::coarsest_apply_many(T* out, size_t ostride, const T* in, size
   return false;
 }
 
-// ---- the intermediate level of a three-level hierarchy for many right-hand sides (coarse_multi.h) -------------------------
+// ---- the intermediate levels for many right-hand sides (coarse_multi.h): level 1 of three levels, levels 1 and 2 of four -------
 template <typename T>
 void Multigrid<T>::ensure_lockstep() {
   if constexpr (sizeof(T) == 4) {
@@ -480,24 +480,47 @@ void Multigrid<T>::ensure_lockstep() {
   }
 }
 template <typename T>
-bool Multigrid<T>::level1_multi_ready(int ncols) {
+bool Multigrid<T>::multi_refuse(int l, const char* why) {
+  if (knobs_.setup_timing && !multi_noticed_[l]) fprintf(stderr, "[ddamg setup] level %d one vector at a time: %s\n", l, why);
+  multi_noticed_[l] = true;
+  return false;
+}
+template <typename T>
+bool Multigrid<T>::multi_ready(int l, int ncols) {
   if constexpr (sizeof(T) == 4) {
+    const int L = num_levels();
+    if (l < 1 || l > L - 2 || ncols < 2 || ncols > LOCKSTEP_COLS) return false;
     // mixed precision 2: the K-cycle takes D*phi out of the smoother's residual (src/linsolve_generic.c:757,828-835), which the
     // batched smoother does not return -- one vector at a time there
-    if (num_levels() != 3 || gath_.on || comm_ != nullptr || par_.mixed_precision == 2 || !par_.odd_even || ncols < 2 || ncols > LOCKSTEP_COLS) return false;
-    MGLevel<T>& l1 = *lv_[1];
-    if (l1.nvec > 32 || !CoarseMulti::available(*l1.g, l1.cop, par_.method) || !LockstepCoarseSolver::available(lv_[2]->cop, ncols, true)) return false;
-    if (!multi1_.ready()) {
+    if (comm_ != nullptr) return multi_refuse(l, "process grid");
+    if (gath_.on) return multi_refuse(l, "gathered coarsest level");
+    if (par_.mixed_precision == 2) return multi_refuse(l, "mixed_precision = 2");
+    if (!par_.odd_even) return multi_refuse(l, "odd_even = 0");
+    // every intermediate level from this one down, or none: a V-cycle of level l goes through all of them
+    size_t need = 0;
+    for (int d = l; d <= L - 2; d++) {
+      MGLevel<T>& ld = *lv_[d];
+      if (ld.nvec > 32) return multi_refuse(d, "more than 32 test vectors");
+      if (!CoarseMulti::available(*ld.g, ld.cop, par_.method)) return multi_refuse(d, "method, dof count, block size or block colouring not covered");
+      if (!multi_[d].ready()) need += CoarseMulti::workspace_bytes(*ld.g, ld.n, ld.gm.restart_length);
+    }
+    if (!LockstepCoarseSolver::available(lv_[L - 1]->cop, ncols, true)) return multi_refuse(L - 1, "coarsest level not covered by the lockstep solver");
+    if (need > 0) {
       // the batches are tens of GB at 64^4: next to a context that already holds its solver workspace they may not fit, and a
-      // failed allocation in the middle of a setup is worse than the one-vector-at-a-time path
+      // failed allocation in the middle of a setup is worse than the one-vector-at-a-time path.  All levels involved together,
+      // before any of them allocates.
       size_t free_b = 0, total_b = 0;
       DDAMG_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      const size_t need = CoarseMulti::workspace_bytes(*l1.g, l1.n, l1.gm.restart_length);
       if (need + need / 8 > free_b) {
-        if (knobs_.setup_timing) fprintf(stderr, "[ddamg setup] level 1 one vector at a time: %zu bytes free, %zu needed\n", free_b, need);
+        if (knobs_.setup_timing) fprintf(stderr, "[ddamg setup] level %d one vector at a time: %zu bytes free, %zu needed from this level down\n", l, free_b, need);
         return false;
       }
-      multi1_.init(*l1.g, &l1.cop, &l1.cip, par_.block_iter[1], st_);
+      for (int d = l; d <= L - 2; d++) {
+        if (multi_[d].ready()) continue;
+        MGLevel<T>& ld = *lv_[d];
+        multi_[d].init(*ld.g, &ld.cop, &ld.cip, par_.block_iter[d], st_);
+        if (knobs_.setup_timing) fprintf(stderr, "[ddamg setup] level %d all vectors at once: %d dof per site, %d sites\n", d, ld.n, ld.g->V);
+      }
     }
     ensure_lockstep();
     return true;
@@ -505,68 +528,105 @@ bool Multigrid<T>::level1_multi_ready(int ncols) {
   return false;
 }
 template <typename T>
-int Multigrid<T>::multi1_vcycle(float2* phi, const float2* eta, int ncols) {
+const CoarseMulti::Nested* Multigrid<T>::multi_nested(int l, CoarseMulti::Nested* chain) {
+  if constexpr (sizeof(T) == 4) {
+    const int L = num_levels();
+    const CoarseMulti::Nested* below = nullptr;
+    for (int d = L - 2; d > l; d--) {       // from the deepest intermediate level up to l + 1
+      MGLevel<T>& ld = *lv_[d];
+      chain[d].level = &multi_[d];
+      chain[d].m = ld.gm.restart_length; chain[d].cycles = ld.gm.num_restart; chain[d].tol = ld.gm.tol;
+      chain[d].post_smooth = par_.post_smooth_iter[d];
+      chain[d].nested = below;
+      below = &chain[d];
+    }
+    return below;
+  }
+  return nullptr;
+}
+template <typename T>
+int Multigrid<T>::multi_vcycle(int l, float2* phi, const float2* eta, int ncols) {
   if constexpr (sizeof(T) == 4) {
     MGLevel<T>& lc = *lv_.back();
-    const int it = multi1_.vcycle(phi, eta, ncols, par_.post_smooth_iter[1], lockstep_, [this] { this->coarse_solve(); }, lc.gm.x, lc.gm.b, nullptr);
+    CoarseMulti::Nested chain[DDAMG_HIP_MAX_LEVELS];
+    const int it = multi_[l].vcycle(phi, eta, ncols, par_.post_smooth_iter[l], lockstep_, [this] { this->coarse_solve(); }, lc.gm.x, lc.gm.b, nullptr, multi_nested(l, chain));
     coarse_iter_count += it;
     return it;
   }
   return 0;
 }
 template <typename T>
-int Multigrid<T>::multi1_kcycle(float2* X, const float2* B, int ncols, int* iters) {
+int Multigrid<T>::multi_kcycle(int l, float2* X, const float2* B, int ncols, int* iters) {
   if constexpr (sizeof(T) == 4) {
-    MGLevel<T>& l1 = *lv_[1];
+    MGLevel<T>& ll = *lv_[l];
     MGLevel<T>& lc = *lv_.back();
-    const int it = multi1_.kcycle(X, B, ncols, l1.gm.restart_length, l1.gm.num_restart, l1.gm.tol, par_.post_smooth_iter[1], lockstep_,
-                                  [this] { this->coarse_solve(); }, lc.gm.x, lc.gm.b, iters);
+    CoarseMulti::Nested chain[DDAMG_HIP_MAX_LEVELS];
+    const int it = multi_[l].kcycle(X, B, ncols, ll.gm.restart_length, ll.gm.num_restart, ll.gm.tol, par_.post_smooth_iter[l], lockstep_,
+                                    [this] { this->coarse_solve(); }, lc.gm.x, lc.gm.b, iters, nullptr, multi_nested(l, chain));
     coarse_iter_count += it;
     return it;
   }
   return 0;
 }
 template <typename T>
-bool Multigrid<T>::level1_apply_many(T* out, size_t ostride, const T* in, size_t istride, int ncols) {
+void Multigrid<T>::multi_update_deeper(int l, int ncols) {
   if constexpr (sizeof(T) == 4) {
-    if (!level1_multi_ready(ncols)) return false;
-    multi1_.gather(multi1_.work(0), in, istride, ncols);
-    multi1_.apply(multi1_.work(1), multi1_.work(0));
-    multi1_.scatter(out, ostride, multi1_.work(1), ncols);
+    // the one-vector code takes gm.x of the LAST level-d K-cycle that ran for vector i (bootstrap()); in lockstep that is the
+    // level-d iterate batch as the last V-cycle in which column i took part left it (CoarseMulti::next_iterate)
+    for (int d = num_levels() - 2; d > l; d--) {
+      float2* Xd = multi_[d - 1].next_iterate();
+      const int nup = std::min(ncols, lv_[d]->nvec);
+      multi_[d].normalize_columns(Xd);
+      multi_[d].scatter(tv_base(d), tv_stride(d), Xd, nup);
+    }
+  }
+}
+template <typename T>
+bool Multigrid<T>::multi_apply_many(int l, T* out, size_t ostride, const T* in, size_t istride, int ncols) {
+  if constexpr (sizeof(T) == 4) {
+    if (!multi_ready(l, ncols)) return false;
+    CoarseMulti& m = multi_[l];
+    m.gather(m.work(0), in, istride, ncols);
+    m.apply(m.work(1), m.work(0));
+    m.scatter(out, ostride, m.work(1), ncols);
     return true;
   }
   return false;
 }
 template <typename T>
-bool Multigrid<T>::level1_smooth_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols, int cycles, int res) {
+bool Multigrid<T>::multi_smooth_many(int l, T* phi, size_t pstride, const T* eta, size_t estride, int ncols, int cycles, int res) {
   if constexpr (sizeof(T) == 4) {
-    if (!level1_multi_ready(ncols)) return false;
-    multi1_.gather(multi1_.work(0), eta, estride, ncols);
-    if (res == RES) multi1_.gather(multi1_.work(1), phi, pstride, ncols);
-    multi1_.smooth(multi1_.work(1), multi1_.work(0), cycles, res);
-    multi1_.scatter(phi, pstride, multi1_.work(1), ncols);
+    if (!multi_ready(l, ncols)) return false;
+    CoarseMulti& m = multi_[l];
+    m.gather(m.work(0), eta, estride, ncols);
+    if (res == RES) m.gather(m.work(1), phi, pstride, ncols);
+    m.smooth(m.work(1), m.work(0), cycles, res);
+    m.scatter(phi, pstride, m.work(1), ncols);
     return true;
   }
   return false;
 }
 template <typename T>
-bool Multigrid<T>::level1_vcycle_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols) {
+bool Multigrid<T>::multi_vcycle_many(int l, T* phi, size_t pstride, const T* eta, size_t estride, int ncols) {
   if constexpr (sizeof(T) == 4) {
-    if (!level1_multi_ready(ncols)) return false;
-    multi1_.gather(multi1_.work(0), eta, estride, ncols);
-    multi1_vcycle(multi1_.work(1), multi1_.work(0), ncols);
-    multi1_.scatter(phi, pstride, multi1_.work(1), ncols);
+    // above another intermediate level the V-cycle runs that level's K-cycle in lockstep: without K-cycles one vector at a time
+    if (!multi_ready(l, ncols) || (l < num_levels() - 2 && !par_.kcycle)) return false;
+    CoarseMulti& m = multi_[l];
+    m.gather(m.work(0), eta, estride, ncols);
+    multi_vcycle(l, m.work(1), m.work(0), ncols);
+    m.scatter(phi, pstride, m.work(1), ncols);
     return true;
   }
   return false;
 }
 template <typename T>
-bool Multigrid<T>::level1_kcycle_many(T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters) {
+bool Multigrid<T>::multi_kcycle_many(int l, T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters) {
   if constexpr (sizeof(T) == 4) {
-    if (!level1_multi_ready(ncols) || !par_.kcycle) return false;
-    multi1_.gather(multi1_.work(0), b, bstride, ncols);
-    multi1_kcycle(multi1_.work(1), multi1_.work(0), ncols, iters);
-    multi1_.scatter(x, xstride, multi1_.work(1), ncols);
+    if (!multi_ready(l, ncols) || !par_.kcycle) return false;
+    CoarseMulti& m = multi_[l];
+    m.gather(m.work(0), b, bstride, ncols);
+    multi_kcycle(l, m.work(1), m.work(0), ncols, iters);
+    m.scatter(x, xstride, m.work(1), ncols);
     return true;
   }
   return false;
@@ -672,18 +732,19 @@ void Multigrid<T>::define_interpolation(int l) {
   const View all = whole(lv.nel);
   bool batched = false;
   if constexpr (sizeof(T) == 4) {
-    if (l == 1 && par_.method == 2 && level1_multi_ready(lv.nvec)) {
+    if (l >= 1 && par_.method == 2 && multi_ready(l, lv.nvec)) {
       // the three smoother passes of all test vectors of the level at once (coarse_multi.h); the random numbers in the
       // reference's order first
       double t0 = tick(nullptr, 0);
       for (int k = 0; k < lv.nvec; k++) random_vector(l, test_vector(l, k));
       t0 = tick("random test vectors", t0);
-      float2 *A = multi1_.work(0), *Bt = multi1_.work(1);
-      multi1_.gather(A, tv_base(l), tv_stride(l), lv.nvec);
-      multi1_.smooth(Bt, A, 1, NO_RES);
-      multi1_.smooth(A, Bt, 2, NO_RES);
-      multi1_.smooth(Bt, A, 3, NO_RES);
-      multi1_.scatter(tv_base(l), tv_stride(l), Bt, lv.nvec);
+      CoarseMulti& m = multi_[l];
+      float2 *A = m.work(0), *Bt = m.work(1);
+      m.gather(A, tv_base(l), tv_stride(l), lv.nvec);
+      m.smooth(Bt, A, 1, NO_RES);
+      m.smooth(A, Bt, 2, NO_RES);
+      m.smooth(Bt, A, 3, NO_RES);
+      m.scatter(tv_base(l), tv_stride(l), Bt, lv.nvec);
       tick("initial smoothing", t0);
       batched = true;
     }
@@ -852,7 +913,7 @@ void Multigrid<T>::release_setup_workspace() {
   DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
   gal_W_.reset(); gal_C_.reset(); gal_cwork_.reset();
   lockstep_.release();
-  multi1_.release();
+  for (auto& m : multi_) m.release();
 }
 
 template <typename T>
@@ -937,18 +998,21 @@ bool Multigrid<T>::bootstrap_vcycles_batched() {
     }
   }
   if constexpr (sizeof(T) == 4) {
-    if (!nx.coarsest && par_.kcycle && level1_multi_ready(N)) {
-      // three levels: the N K-cycles of the intermediate level in lockstep -- operator, Schwarz smoother, transfers and the
-      // coarsest solves for all columns at once (coarse_multi.h), every column with its own FGMRES recurrence
-      float2 *B1 = multi1_.work(0), *X1 = multi1_.work(1);
+    if (!nx.coarsest && par_.kcycle && multi_ready(1, N)) {
+      // three and four levels: the N K-cycles of level 1 in lockstep -- operator, Schwarz smoother, transfers and the coarsest
+      // solves for all columns at once (coarse_multi.h), every column with its own FGMRES recurrence; on four levels the K-cycles
+      // of level 2 inside every V-cycle of level 1 the same way
+      CoarseMulti& m1 = multi_[1];
+      float2 *B1 = m1.work(0), *X1 = m1.work(1);
       std::vector<int> its(N);
-      multi1_.gather(B1, Cb, cs, N);
-      multi1_kcycle(X1, B1, N, its.data());
-      multi1_.scatter(Cx, cs, X1, N);
-      // test_vector_PRECISION_update of the intermediate level from the K-cycle iterates
+      m1.gather(B1, Cb, cs, N);
+      multi_kcycle(1, X1, B1, N, its.data());
+      m1.scatter(Cx, cs, X1, N);
+      // test_vector_PRECISION_update of the intermediate levels from their K-cycle iterates: the deeper level first
+      multi_update_deeper(1, N);
       const int nup = std::min(N, nx.nvec);
-      multi1_.normalize_columns(X1);
-      multi1_.scatter(tv_base(1), tv_stride(1), X1, nup);
+      m1.normalize_columns(X1);
+      m1.scatter(tv_base(1), tv_stride(1), X1, nup);
       in_lockstep = true;
     }
   }
@@ -1019,13 +1083,16 @@ void Multigrid<T>::bootstrap(int l, int iters) {
     }
     bool level_batched = false;
     if constexpr (sizeof(T) == 4) {
-      if (l == 1 && level1_multi_ready(lv.nvec)) {
-        // the V-cycles of all test vectors of the intermediate level at once (coarse_multi.h)
-        float2 *E = multi1_.work(0), *Phi = multi1_.work(1);
-        multi1_.gather(E, tv_base(1), tv_stride(1), lv.nvec);
-        multi1_vcycle(Phi, E, lv.nvec);
-        multi1_.normalize_columns(Phi);
-        multi1_.scatter(tv_base(1), tv_stride(1), Phi, lv.nvec);
+      if (l >= 1 && (par_.kcycle || lv_[l + 1]->coarsest) && multi_ready(l, lv.nvec)) {
+        // the V-cycles of all test vectors of an intermediate level at once (coarse_multi.h); above another intermediate level
+        // with that level's K-cycles inside (kcycle = 0: one vector at a time there), and its test vectors updated from their iterates
+        CoarseMulti& m = multi_[l];
+        float2 *E = m.work(0), *Phi = m.work(1);
+        m.gather(E, tv_base(l), tv_stride(l), lv.nvec);
+        multi_vcycle(l, Phi, E, lv.nvec);
+        multi_update_deeper(l, lv.nvec);
+        m.normalize_columns(Phi);
+        m.scatter(tv_base(l), tv_stride(l), Phi, lv.nvec);
         level_batched = true;
       }
     }

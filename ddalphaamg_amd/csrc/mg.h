@@ -109,16 +109,18 @@ class Multigrid {
   // ncols right-hand sides in lockstep (coarse_lockstep.h); X, B: columns of ordinary coarsest-level vectors; false if the shape is not covered
   bool coarse_solve_many(T* X, size_t xstride, const T* B, size_t bstride, int ncols, int* iters);
   bool coarsest_apply_many(T* out, size_t ostride, const T* in, size_t istride, int ncols);   // the coarsest operator itself, all columns (ls_self_kernel + ls_hop_kernel)
-  void release_many_workspace() { lockstep_.release(); multi1_.release(); }                   // what the *_many entry points allocate lazily
+  void release_many_workspace() { lockstep_.release(); for (auto& m : multi_) m.release(); }                  // what the *_many entry points allocate lazily
   void import_interpolation_level(int l, const double* P_lex_host);                           // level-l interpolation vectors as they are, then the operators below
   void vcycle(int l, T* phi, T* Dphi, const T* eta, int res);
-  // ---- many right-hand sides on the intermediate level of a three-level hierarchy (coarse_multi.h; fp32, single process) ------
-  // columns: ordinary level-1 vectors, column c at base + c * stride.  false if the shape is not covered.
-  bool level1_multi_ready(int ncols);
-  bool level1_apply_many(T* out, size_t ostride, const T* in, size_t istride, int ncols);
-  bool level1_smooth_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols, int cycles, int res);
-  bool level1_vcycle_many(T* phi, size_t pstride, const T* eta, size_t estride, int ncols);
-  bool level1_kcycle_many(T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters);
+  // ---- many right-hand sides on the intermediate levels (coarse_multi.h; fp32, single process): level 1 of three levels, levels 1
+  // and 2 of four -- the V-cycle of level 1 then runs the K-cycles of level 2 for all columns inside it ------
+  // columns: ordinary level-l vectors, column c at base + c * stride.  false if the shape is not covered.
+  // multi_ready: level l AND every intermediate level below it take the many-vector path (else none of them does)
+  bool multi_ready(int l, int ncols);
+  bool multi_apply_many(int l, T* out, size_t ostride, const T* in, size_t istride, int ncols);
+  bool multi_smooth_many(int l, T* phi, size_t pstride, const T* eta, size_t estride, int ncols, int cycles, int res);
+  bool multi_vcycle_many(int l, T* phi, size_t pstride, const T* eta, size_t estride, int ncols);
+  bool multi_kcycle_many(int l, T* x, size_t xstride, const T* b, size_t bstride, int ncols, int* iters);
   int kcycle_solve(int l);                                       // the K-cycle FGMRES of level l on level(l).gm.b -> gm.x, one vector
   // ---- 16-bit storage for the solve (half_storage.h; fp32 V-cycle): bits 32 or 16 per kind ----
   // 16: the kind's products read a 16-bit copy that their first use makes.  Coarse: the one-right-hand-side coarsest Schur complement
@@ -184,10 +186,17 @@ class Multigrid {
     ~SetupStorage() { bits = saved; }
   };
   LockstepCoarseSolver lockstep_;   // the bootstrap's coarsest-level solves, all test vectors at once (fp32, single process)
-  CoarseMulti multi1_;              // three levels: the intermediate level for all test vectors at once (coarse_multi.h)
+  CoarseMulti multi_[DDAMG_HIP_MAX_LEVELS];   // [l]: intermediate level l for all test vectors at once (coarse_multi.h); l = 1, 2
+  bool multi_noticed_[DDAMG_HIP_MAX_LEVELS] = {};
   void ensure_lockstep();
-  int multi1_vcycle(float2* phi, const float2* eta, int ncols);
-  int multi1_kcycle(float2* X, const float2* B, int ncols, int* iters);
+  bool multi_refuse(int l, const char* why);                 // the DDAMG_SETUP_TIMING notice, once per level; returns false
+  // the K-cycle parameters of the levels below l for the nested V-cycle (chain: storage of the caller); nullptr: l + 1 is the coarsest
+  const CoarseMulti::Nested* multi_nested(int l, CoarseMulti::Nested* chain);
+  int multi_vcycle(int l, float2* phi, const float2* eta, int ncols);
+  int multi_kcycle(int l, float2* X, const float2* B, int ncols, int* iters);
+  // test_vector_PRECISION_update of the intermediate levels below l from the K-cycle iterates the last multi_vcycle / multi_kcycle
+  // of level l left (the first ncols test vectors of each)
+  void multi_update_deeper(int l, int ncols);
   void setup_gathered_coarsest();
   void schur(T* out, const T* in);
   void schur_on(bool gathered, int V, T* t0, T* t1, T* out, const T* in);

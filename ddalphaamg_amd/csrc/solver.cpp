@@ -398,6 +398,7 @@ struct Columns {
 int many_level(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* a, const ddamg_hip_vec* const* b) {
   DDAMG_REQUIRE(c && c->mg32 && a && b, "the many-right-hand-side entry points need the fp32 hierarchy (mixed_precision >= 1)");
   DDAMG_REQUIRE(ncols >= 2 && ncols <= 32, "2 <= ncols <= 32");
+  for (int k = 0; k < ncols; k++) DDAMG_REQUIRE(a[k] && b[k], "null vector among the columns");
   const int lvl = a[0]->level;
   DDAMG_REQUIRE(lvl >= 1 && lvl < c->par.num_levels, "coarse-level vectors expected");
   for (int k = 0; k < ncols; k++) {
@@ -563,55 +564,59 @@ int ddamg_hip_kcycle(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b,
 // ---- many right-hand sides on a coarse level: the kernels of the batched setup through the boundary (tests, measurements) ----
 int ddamg_hip_coarse_apply_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* out, const ddamg_hip_vec* const* in) {
   DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && out && in, "null context or null vector array");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, out, in);
   Columns I(in[0]->data.bytes() / sizeof(float), ncols), O(in[0]->data.bytes() / sizeof(float), ncols);
   pack(c, I, in, ncols);
-  const bool ok = lvl == c->par.num_levels - 1 ? c->mg32->coarsest_apply_many(O.p, O.cs, I.p, I.cs, ncols) : (lvl == 1 && c->mg32->level1_apply_many(O.p, O.cs, I.p, I.cs, ncols));
+  const bool ok = lvl == c->par.num_levels - 1 ? c->mg32->coarsest_apply_many(O.p, O.cs, I.p, I.cs, ncols) : c->mg32->multi_apply_many(lvl, O.p, O.cs, I.p, I.cs, ncols);
   if (ok) unpack(c, out, O, ncols);
   c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "coarse_apply_many: shape not covered (fp32, single process; the coarsest level, or the intermediate level of three)");
+  DDAMG_REQUIRE(ok, "coarse_apply_many: shape not covered (fp32, single process; the coarsest level, or an intermediate level of three or four levels)");
   DDAMG_API_END
 }
 
 int ddamg_hip_smoother_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta, int cycles, int initial_guess_zero) {
   DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && phi && eta, "null context or null vector array");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, phi, eta);
   Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
   pack(c, E, eta, ncols); pack(c, P, phi, ncols);
-  const bool ok = lvl == 1 && c->mg32->level1_smooth_many(P.p, P.cs, E.p, E.cs, ncols, cycles, initial_guess_zero ? NO_RES : RES);
+  const bool ok = c->mg32->multi_smooth_many(lvl, P.p, P.cs, E.p, E.cs, ncols, cycles, initial_guess_zero ? NO_RES : RES);
   if (ok) unpack(c, phi, P, ncols);
   c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "smoother_many: shape not covered (the intermediate level of a three-level hierarchy, red-black Schwarz, fp32, single process)");
+  DDAMG_REQUIRE(ok, "smoother_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)");
   DDAMG_API_END
 }
 
 int ddamg_hip_vcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
+  DDAMG_REQUIRE(c && phi && eta, "null context or null vector array");
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, phi, eta);
   Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
   pack(c, E, eta, ncols);
-  const bool ok = lvl == 1 && c->mg32->level1_vcycle_many(P.p, P.cs, E.p, E.cs, ncols);
+  const bool ok = c->mg32->multi_vcycle_many(lvl, P.p, P.cs, E.p, E.cs, ncols);
   if (ok) unpack(c, phi, P, ncols);
   c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "vcycle_many: shape not covered (the intermediate level of a three-level hierarchy, red-black Schwarz, fp32, single process)");
+  DDAMG_REQUIRE(ok, "vcycle_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)");
   DDAMG_API_END
 }
 
 int ddamg_hip_kcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* x, const ddamg_hip_vec* const* b, int* iterations) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done && iterations, "setup has not been run");
+  DDAMG_REQUIRE(c && x && b && iterations, "null context, null vector array or null iteration counts");
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
   DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lvl = many_level(c, ncols, x, b);
   Columns B(b[0]->data.bytes() / sizeof(float), ncols), X(b[0]->data.bytes() / sizeof(float), ncols);
   pack(c, B, b, ncols);
-  const bool ok = lvl == 1 && c->mg32->level1_kcycle_many(X.p, X.cs, B.p, B.cs, ncols, iterations);
+  const bool ok = c->mg32->multi_kcycle_many(lvl, X.p, X.cs, B.p, B.cs, ncols, iterations);
   if (ok) unpack(c, x, X, ncols);
   c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "kcycle_many: shape not covered (the intermediate level of a three-level hierarchy with the K-cycle, red-black Schwarz, fp32, single process)");
+  DDAMG_REQUIRE(ok, "kcycle_many: shape not covered (an intermediate level of three or four levels with the K-cycle, red-black Schwarz, fp32, single process)");
   DDAMG_API_END
 }
 

@@ -268,9 +268,15 @@ int ddamg_hip_kcycle(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* 
  * (the reference: one test vector at a time, src/setup_generic.c:191-275,441-503): every coupling of a site becomes a complex
  * (n x n) x (n x 32) product on the matrix cores (v_mfma_f32_16x16x4_f32), the coupling matrices read once for all columns;
  * every column keeps its own MinRes coefficients, Hessenberg matrix and stopping test.  fp32 V-cycle, single process.
- *   coarse_apply_many: apply_coarse_operator_PRECISION on the coarsest level or on the intermediate level of three levels;
+ * The level of the vectors selects the level: the intermediate level of three levels, or level 1 or 2 of four.
+ *   coarse_apply_many: apply_coarse_operator_PRECISION on the coarsest level or on an intermediate level;
  *   smoother_many / vcycle_many / kcycle_many: red-black Schwarz smoother, V-cycle and K-cycle (iterations[c] per column) of
- *   the intermediate level of a three-level hierarchy. */
+ *   an intermediate level.  On level 1 of four levels the V-cycle runs the K-cycles of level 2 for all columns inside it
+ *   (vcycle_PRECISION -> fgmres_PRECISION(&l->next_level->p), src/vcycle_generic.c:103-114), every level with its own restart
+ *   length, tolerance and smoother counts; that form needs kcycle = 1.
+ * Non-zero, with the reason in ddamg_hip_last_error, for a null argument and where the many-vector path does not cover the
+ * context (mixed_precision == 2, odd_even == 0, methods other than 2, process grids, more than 32 test vectors or 64 dof on
+ * any intermediate level from the vectors' level down). */
 int ddamg_hip_coarse_apply_many(ddamg_hip_ctx* ctx, int ncols, ddamg_hip_vec* const* out, const ddamg_hip_vec* const* in);
 int ddamg_hip_smoother_many(ddamg_hip_ctx* ctx, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta, int cycles, int initial_guess_zero);
 int ddamg_hip_vcycle_many(ddamg_hip_ctx* ctx, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta);
