@@ -148,6 +148,7 @@ def load_library():
         "ddamg_hip_timer_begin": [vp],
         "ddamg_hip_timer_end": [vp, ctypes.POINTER(ctypes.c_float)],
         "ddamg_hip_sync": [vp],
+        "ddamg_hip_link_reals": [vp, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_memory_in_use": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
     }
     for name, args in sigs.items():
@@ -408,6 +409,12 @@ class Context:
         D = np.empty((V, 36, 2)); cl = np.empty((V, 42, 2))
         _check(self._lib.ddamg_hip_get_operator(self._h, _dp(D), _dp(cl)))
         return D, cl
+
+    def link_reals(self):
+        """reals per link that the fp32 fine operator reads: 18 (full links), 12 (two-row form) or 10 (pivot form)"""
+        n = ctypes.c_int(0)
+        _check(self._lib.ddamg_hip_link_reals(self._h, ctypes.byref(n)))
+        return n.value
 
     def vector(self, level=0, precision=32):
         return Vector(self, level, precision)

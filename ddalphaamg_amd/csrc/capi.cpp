@@ -185,6 +185,13 @@ int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes) {
   return 0;
 }
 
+int ddamg_hip_link_reals(ddamg_hip_ctx* c, int* reals) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c->have_operator, "link_reals: no operator uploaded");
+  *reals = c->fop32.link_reals();
+  DDAMG_API_END
+}
+
 int ddamg_hip_set_coarse_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Coarse, bits, "coarse"); }
 int ddamg_hip_set_transfer_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Transfer, bits, "transfer"); }
 int ddamg_hip_set_intermediate_storage(ddamg_hip_ctx* c, int bits) { return set_storage(c, Intermediate, bits, "intermediate"); }

@@ -14,6 +14,12 @@
 //            g_i = (A_ii - Dd_ii)/2 (i = 0..2), the 3 complex strict-upper entries of A, the 9 complex entries of B (row-major);
 //            block b starts at cloverc + b*28*V (seven 16-byte chunk rows each)
 //   nb     : 8 x V int32 neighbour sites (+T,+Z,+Y,+X,-T,-Z,-Y,-X)
+//   Dp, Dpb: (float only, null unless the two-row check passed on every link, a tile is one 4^4 block and DDAMG_LINK_PIVOT is not 0)
+//            the links in 10 reals + 1 byte: row 0 and the two entries of row 1 outside the pivot column p, the smallest column
+//            that maximises |row0[k]|^2 of the fp32-rounded row 0.  Rows 0 and 1 of U/2 are orthogonal, so
+//            row1[p] = -(sum_{k != p} row1[k] conj(row0[k])) row0[p] / |row0[p]|^2 with |row0[p]| >= |row0| / sqrt(3); the byte is
+//            sgn * (1 + p), sgn as in Dsgn.  A second copy next to D and Dc, read by dirac_apply_lds_kernel only: 164 B of device
+//            memory per site more
 #pragma once
 #include "common.h"
 #include "geometry.h"
@@ -40,7 +46,14 @@ struct FineOpDev {
   const T* Dc;
   const signed char* Dsgn;        // [4][V]
   const T* cloverc;               // the clover term in 56 reals per site (see above), read by dirac_apply_lds_kernel only
+  // pivot storage of the links (see above; null unless Dc is set too): 10 reals per link in two 16-byte chunk rows and one 8-byte
+  // tail row, direction mu at Dp + mu*10*V, and the byte sgn * (1 + p)
+  const T* Dp;
+  const signed char* Dpb;         // [4][V]
 };
+
+// how a kernel reads the links: all 18 reals, rows 0 and 1 (Dc, Dsgn), or row 0 and two entries of row 1 (Dp, Dpb)
+enum class LinkForm { Full, TwoRow, Pivot };
 
 template <typename T>
 class FineOp {
@@ -70,8 +83,10 @@ class FineOp {
   void scale_clover(const double* base64, double scale_even, double scale_odd, hipStream_t st);
   // eta = D_W phi; with a process grid: pack -> exchange (overlapped with the interior tiles) -> boundary tiles
   void apply(T* eta, const T* phi, hipStream_t st) const;
-  FineOpDev<T> dev() const { return FineOpDev<T>{D_, clover_, clover_inv_, nb_, V_, halo_.recv(), halo_.dev(), tile_nb_, tnb_, parity_, Dc_, Dsgn_, Cc_}; }
+  FineOpDev<T> dev() const { return FineOpDev<T>{D_, clover_, clover_inv_, nb_, V_, halo_.recv(), halo_.dev(), tile_nb_, tnb_, parity_, Dc_, Dsgn_, Cc_, Dp_, Dpb_}; }
   bool links_compressed() const { return Dc_ != nullptr; }
+  // reals per link that apply() reads: 18, 12 (two-row form) or 10 (pivot form, fp32 only)
+  int link_reals() const { return Dp_ ? 10 : Dc_ ? 12 : 18; }
   int V() const { return V_; }
   // the fp64 operator on an fp32 input vector (converted in the loads); T = double only
   void apply_f32in(T* eta, const float* phi, hipStream_t st) const;
@@ -108,6 +123,9 @@ class FineOp {
   DeviceBuffer<signed char> Dsgn_;
   T* Cc_ = nullptr;            // 56-real clover (fp32 operators whose clover blocks have the chiral structure): Cc_store_ or null
   DeviceBuffer<T> Cc_store_;
+  T* Dp_ = nullptr;            // pivot links (fp32 operators with two-row links and DDAMG_LINK_PIVOT on): Dp_store_ or null
+  DeviceBuffer<T> Dp_store_;
+  DeviceBuffer<signed char> Dpb_;
   DeviceBuffer<unsigned short> tnb_;
   int V_ = 0;
   mutable Halo<T> halo_;
@@ -125,14 +143,38 @@ void FineOp<double>::export_lex(double* dD_lex, double* dC_lex, const double* cl
 namespace ddamg {
 // the link U_mu(s): 18 reals from the full storage, or 12 reals + the reconstruction of the third row
 //   row2 = sgn * 2 conj(row0 x row1)      (links hold U/2: |row| = 1/2, so conj(row0 x row1) = row2 / (2 sgn))
-template <typename T, int MU, bool CMP>
+// or 10 reals + the byte sgn * (1 + p): row1[p] from the orthogonality of rows 0 and 1 first (one IEEE division per link)
+template <typename T, int MU, LinkForm LF>
 __device__ __forceinline__ void load_link(const FineOpDev<T>& op, size_t V, size_t s, T (&U)[18]) {
-  if constexpr (!CMP) {
+  if constexpr (LF == LinkForm::Full) {
     load_site<T, 18>(op.D + (size_t)MU * 18 * V, V, s, U);
   } else {
     T r[12];
-    load_site<T, 12>(op.Dc + (size_t)MU * 12 * V, V, s, r);
-    const T sg = (T)2 * (T)op.Dsgn[(size_t)MU * V + s];
+    T sg;
+    if constexpr (LF == LinkForm::TwoRow) {
+      load_site<T, 12>(op.Dc + (size_t)MU * 12 * V, V, s, r);
+      sg = (T)2 * (T)op.Dsgn[(size_t)MU * V + s];
+    } else {
+      T c[10];
+      load_site<T, 10>(op.Dp + (size_t)MU * 10 * V, V, s, c);
+      const int b = op.Dpb[(size_t)MU * V + s];
+      sg = b < 0 ? (T)-2 : (T)2;
+      const int p = (b < 0 ? -b : b) - 1;
+      // kept columns ka < kb of row 1 = (c[6], c[7]), (c[8], c[9]):  p = 0: 1, 2;  p = 1: 0, 2;  p = 2: 0, 1
+      const T ar = p == 0 ? c[2] : c[0], ai = p == 0 ? c[3] : c[1];     // row0[ka]
+      const T br = p == 2 ? c[2] : c[4], bi = p == 2 ? c[3] : c[5];     // row0[kb]
+      const T pr = p == 0 ? c[0] : p == 1 ? c[2] : c[4], pi = p == 0 ? c[1] : p == 1 ? c[3] : c[5];   // row0[p]
+      // n = row1[ka] conj(row0[ka]) + row1[kb] conj(row0[kb]);  x = -(n row0[p]) / |row0[p]|^2
+      const T nr = c[6] * ar + c[7] * ai + (c[8] * br + c[9] * bi);
+      const T ni = c[7] * ar - c[6] * ai + (c[9] * br - c[8] * bi);
+      const T inv = (T)1 / (pr * pr + pi * pi);
+      const T xr = -(nr * pr - ni * pi) * inv, xi = -(nr * pi + ni * pr) * inv;
+#pragma unroll
+      for (int k = 0; k < 6; k++) r[k] = c[k];
+      r[6] = p == 0 ? xr : c[6];                  r[7] = p == 0 ? xi : c[7];
+      r[8] = p == 0 ? c[6] : p == 1 ? xr : c[8];  r[9] = p == 0 ? c[7] : p == 1 ? xi : c[9];
+      r[10] = p == 2 ? xr : c[8];                 r[11] = p == 2 ? xi : c[9];
+    }
 #pragma unroll
     for (int k = 0; k < 12; k++) U[k] = r[k];
 #pragma unroll

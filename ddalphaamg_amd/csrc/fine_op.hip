@@ -54,13 +54,13 @@ __device__ __forceinline__ void load_site_as(const TIN* __restrict__ base, size_
 
 // CCL is not used here: it gives each kernel its own instantiation (one tile_dir shared by the CCL and the non-CCL kernel is
 // optimised once before it is inlined into both, and both then need 143 VGPRs instead of 120)
-template <typename T, int MU, bool ARITH, bool CMP, bool HB2, typename TIN = T, bool CCL = false>
+template <typename T, int MU, bool ARITH, LinkForm LF, bool HB2, typename TIN = T, bool CCL = false>
 __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const FineOpDev<T>& op, size_t s, bool live, int tile0, const uint4& q,
                                          const T (&p)[24], T (&e)[24], T* __restrict__ sp, T* __restrict__ hb) {
   const size_t V = op.V;
   const int t = threadIdx.x;
   T U[18];
-  if (live) load_link<T, MU, CMP>(op, V, s, U);
+  if (live) load_link<T, MU, LF>(op, V, s, U);
   // (a) backward product for my +mu neighbour:  U_mu(s)^dagger (1+gamma_mu) phi(s)
   {
     T h[12], g[12];
@@ -99,7 +99,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
     } else {
       T pn[24], Un[18];
       load_site_as<T, TIN, 24>(phi, V, j, pn);
-      load_link<T, MU, CMP>(op, V, (size_t)j, Un);
+      load_link<T, MU, LF>(op, V, (size_t)j, Un);
       hop_accumulate<T, MU, false>(Un, pn, e);
     }
   }
@@ -107,7 +107,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
 }
 
 // CCL: the clover term from its 56-real form (FineOpDev::cloverc, fp32 only)
-template <typename T, bool ARITH, bool CMP = false, typename TIN = T, bool CCL = false>
+template <typename T, bool ARITH, LinkForm LF = LinkForm::Full, typename TIN = T, bool CCL = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds_kernel(T* __restrict__ eta, const TIN* __restrict__ phi, FineOpDev<T> op, int ntiles,
                                                                   const int* __restrict__ tile_list) {
   // fp32: two buffers for the backward products, used in turn, so that one barrier per direction is enough (48 KB of LDS,
@@ -151,10 +151,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
     }
   }
   __syncthreads();
-  tile_dir<T, 0, ARITH, CMP, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 1, ARITH, CMP, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
-  tile_dir<T, 2, ARITH, CMP, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 3, ARITH, CMP, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
+  tile_dir<T, 0, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
+  tile_dir<T, 1, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
+  tile_dir<T, 2, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
+  tile_dir<T, 3, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
   if (live) store_site<T, 24, DDAMG_NT_STORE>(eta, V, s, e);
 }
 
@@ -267,9 +267,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_hop_parit
 
 template <typename T, bool CCL>
 static void launch_dirac_apply(T* eta, const T* phi, const FineOpDev<T>& op, int ntiles, const int* tile_list, hipStream_t st) {
-  if (op.tnb && op.Dc) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, true, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
-  else if (op.tnb) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, false, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
-  else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, false, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  if constexpr (sizeof(T) == 4) {
+    if (op.tnb && op.Dp) {
+      hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Pivot, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+      return;
+    }
+  }
+  if (op.tnb && op.Dc) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::TwoRow, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  else if (op.tnb) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Full, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, LinkForm::Full, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
 }
 
 template <typename T>
@@ -302,9 +308,9 @@ void FineOp<double>::apply_f32in(double* eta, const float* phi, hipStream_t st) 
   DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
   auto launch = [&](int ntiles, const int* tile_list) {
     if (ntiles == 0) return;
-    if (tnb_ && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, true, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-    else if (tnb_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
-    else hipLaunchKernelGGL((dirac_apply_lds_kernel<double, false, false, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    if (tnb_ && Dc_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, LinkForm::TwoRow, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else if (tnb_) hipLaunchKernelGGL((dirac_apply_lds_kernel<double, true, LinkForm::Full, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
+    else hipLaunchKernelGGL((dirac_apply_lds_kernel<double, false, LinkForm::Full, float>), dim3(ntiles), dim3(256), 0, st, eta, phi, dev(), ntiles, tile_list);
     DDAMG_HIP_CHECK(hipGetLastError());
   };
   if (!halo_.active()) { launch((V_ + 255) / 256, nullptr); return; }
@@ -616,10 +622,12 @@ void FineOp<T>::scale_clover(const double* base64, double scale_even, double sca
 }
 
 // two-row link storage from the reference's links (lexicographic fp64, U/2): rows 0 and 1 in fp32, the sign with which
-// 2 conj(row0 x row1) gives row 2, and -- in *bad -- whether any link is not of that form (then the full storage is used)
+// 2 conj(row0 x row1) gives row 2, and -- in *bad -- whether any link is not of that form (then the full storage is used).
+// With Dp: the pivot form as well (fine_op.h): row 0, the two entries of row 1 outside the pivot column p, and the byte sgn * (1 + p)
 template <typename T>
 __global__ __launch_bounds__(128) void link_compress_kernel(T* __restrict__ Dc, signed char* __restrict__ sgn, int* __restrict__ bad,
-                                                            const double* __restrict__ D_lex, const int* __restrict__ lex_of_site, int V) {
+                                                            const double* __restrict__ D_lex, const int* __restrict__ lex_of_site, int V,
+                                                            T* __restrict__ Dp, signed char* __restrict__ pb) {
   const size_t s = (size_t)blockIdx.x * 128 + threadIdx.x;
   if (s >= (size_t)V) return;
   const size_t lx = lex_of_site[s];
@@ -643,6 +651,23 @@ __global__ __launch_bounds__(128) void link_compress_kernel(T* __restrict__ Dc, 
     if ((plus ? dev_p : dev_m) > accept * (nrm > 0 ? nrm : 1.0) || nrm == 0) atomicOr(bad, 1);
     sgn[(size_t)mu * V + s] = plus ? 1 : -1;
     for (int r = 0; r < 12; r++) Dc[(size_t)mu * 12 * V + soa_index_dev<T>(12, V, s, r)] = (T)u[r];
+    if (Dp) {
+      // p: the smallest column that maximises |row0[k]|^2 of the rounded row 0 (the squares and their sum in fp64: the products
+      // of two rounded entries are exact there, so no contraction of the compiler's can move the choice)
+      int p = 0;
+      double best = -1.0;
+      for (int k = 0; k < 3; k++) {
+        const double re = (double)(T)u[2 * k], im = (double)(T)u[2 * k + 1];
+        const double n2 = re * re + im * im;
+        if (n2 > best) { best = n2; p = k; }
+      }
+      T* const out = Dp + (size_t)mu * 10 * V;
+      for (int r = 0; r < 6; r++) out[soa_index_dev<T>(10, V, s, r)] = (T)u[r];
+      const int ka = p == 0 ? 1 : 0, kb = p == 2 ? 1 : 2;
+      out[soa_index_dev<T>(10, V, s, 6)] = (T)u[6 + 2 * ka]; out[soa_index_dev<T>(10, V, s, 7)] = (T)u[6 + 2 * ka + 1];
+      out[soa_index_dev<T>(10, V, s, 8)] = (T)u[6 + 2 * kb]; out[soa_index_dev<T>(10, V, s, 9)] = (T)u[6 + 2 * kb + 1];
+      pb[(size_t)mu * V + s] = (signed char)((plus ? 1 : -1) * (1 + p));
+    }
   }
 }
 
@@ -715,21 +740,30 @@ void FineOp<T>::layout_staged(const Geometry& g, const double* dD, const double*
   hipLaunchKernelGGL(operator_layout_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, D_, clover_, clover_inv_, dD, dC, lex_, (int)V);
   DDAMG_HIP_CHECK(hipGetLastError());
   // two-row links (a third less link traffic in dirac_apply_lds_kernel and the Schwarz block solver) when every link allows it
+  // fp32: the pivot form next to them (a sixth less again, dirac_apply_lds_kernel only) when a tile is one 4^4 block
   Dc_ = nullptr;
+  Dp_ = nullptr;
   {
     if (knobs.link_compression && g.block_sites == 256) {
       if (!Dc_store_) {
         Dc_store_.alloc(48 * V);
         Dsgn_.alloc(4 * V, sizeof(int));
       }
+      const bool pivot = sizeof(T) == 4 && knobs.link_pivot && g.B[0] == 4 && g.B[1] == 4 && g.B[2] == 4 && g.B[3] == 4;
+      if (pivot && !Dp_store_) {
+        Dp_store_.alloc(40 * V);
+        Dpb_.alloc(4 * V);
+      }
       int* d_bad = reinterpret_cast<int*>(Dsgn_ + 4 * V);   // one flag behind the signs
       DDAMG_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), st));
-      hipLaunchKernelGGL(link_compress_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, Dc_store_, Dsgn_, d_bad, dD, lex_, (int)V);
+      hipLaunchKernelGGL(link_compress_kernel<T>, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, Dc_store_, Dsgn_, d_bad, dD, lex_, (int)V,
+                         pivot ? Dp_store_.get() : nullptr, pivot ? Dpb_.get() : nullptr);
       DDAMG_HIP_CHECK(hipGetLastError());
       int bad = 1;
       DDAMG_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
       DDAMG_HIP_CHECK(hipStreamSynchronize(st));
       if (!bad) Dc_ = Dc_store_;
+      if (!bad && pivot) Dp_ = Dp_store_;
     }
   }
   // 56-real clover for the fp32 apply (dirac_apply_lds_kernel; a fifth less clover traffic) when every block allows it

@@ -21,6 +21,7 @@ struct OptionalInt {
 struct Knobs {
   // ---- fine operator (FineOp<T>::upload) ----
   bool link_compression = true;     // DDAMG_LINK_COMPRESSION=0: full 18-real links instead of the two-row form
+  bool link_pivot = true;           // DDAMG_LINK_PIVOT=0: the fp32 apply reads the two-row links instead of the 10-real pivot form
   bool clover_compression = true;   // DDAMG_CLOVER_COMPRESSION=0: the 72-real clover instead of the 56-real form of the fp32 apply
 
   // ---- Schwarz smoother of the fine level (SapSmoother<T>::setup) ----
@@ -72,6 +73,7 @@ struct Knobs {
     const auto integer = [](const char* name) { const char* e = getenv(name); return e ? OptionalInt{true, atoi(e)} : OptionalInt{}; };
     Knobs k;
     k.link_compression = unless_zero("DDAMG_LINK_COMPRESSION");
+    k.link_pivot = unless_zero("DDAMG_LINK_PIVOT");
     k.clover_compression = unless_zero("DDAMG_CLOVER_COMPRESSION");
     if (const OptionalInt v = integer("DDAMG_SAP_VARIANT"); v.set) k.sap_variant = v.value;
     k.galerkin_unbatched = present("DDAMG_GALERKIN_UNBATCHED");

@@ -114,7 +114,7 @@ __device__ __forceinline__ void agg_tile_dir(const ColumnView<T>& v, const FineO
   const size_t V = op.V;
   const int t = threadIdx.x;
   T U[18];
-  if (live) load_link<T, MU, CMP>(op, V, s, U);
+  if (live) load_link<T, MU, CMP ? LinkForm::TwoRow : LinkForm::Full>(op, V, s, U);
   // (a) backward product for my +mu neighbour, if it belongs to my aggregate
   if (live && !(face & (1u << MU))) {
     T h[12], g[12];
@@ -181,7 +181,7 @@ __device__ __forceinline__ void agg_tile_dir(const ColumnView<T>& v, const FineO
       load_column<T, 12>(v, j, ph, 12 * CHIR);
 #pragma unroll
       for (int c = 0; c < 12; c++) { pn[12 * CHIR + c] = ph[c]; pn[12 * (1 - CHIR) + c] = 0; }
-      load_link<T, MU, CMP>(op, V, j, Un);
+      load_link<T, MU, CMP ? LinkForm::TwoRow : LinkForm::Full>(op, V, j, Un);
       hop_accumulate<T, MU, false>(Un, pn, e);
     }
   }

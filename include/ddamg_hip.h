@@ -349,6 +349,10 @@ const char* ddamg_hip_comm_stats(ddamg_hip_ctx* ctx, int reset);
  * diagnostic for leak checks: hipMemGetInfo is device-wide, so on a GPU shared with other processes its differences prove
  * nothing.  Needs no context; always returns 0. */
 int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes);
+/* Reals per link that the fp32 fine operator reads in ddamg_hip_dirac_apply: 18 (full links), 12 (two-row form) or 10 (pivot
+ * form); decided at every upload of an operator (DDAMG_LINK_COMPRESSION, DDAMG_LINK_PIVOT, the block lattice and the links
+ * themselves).  An error before the first operator. */
+int ddamg_hip_link_reals(ddamg_hip_ctx* ctx, int* reals);
 /* host-only helper (no GPU needed): the halo plan of one process.  For face d (0..3: +mu face sending to
  * +mu, 4..7: -mu face) returns the neighbour rank and, if lex_sites != NULL, the local lexicographic index
  * of the face sites in message (slot) order; *count = 0 when the direction is not split. */

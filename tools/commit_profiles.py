@@ -34,10 +34,10 @@ traffic = {
     "dirac_apply_lds_kernel<float>": {
         "kernel": key, "fetch_size_kib": fetch, "write_size_kib": write, "bytes_per_launch": byts,
         "algorithmic_bytes_per_launch": 816 * V, "ratio_to_algorithmic": byts / (816 * V),
-        "bytes_the_layout_moves_per_launch": 608 * V,
-        "workload": "32^4 fp32, bench.py --steps 25 (two-row links, 56-real clover, arithmetic neighbours, non-temporal clover loads and result stores)",
+        "bytes_the_layout_moves_per_launch": 576 * V,
+        "workload": "32^4 fp32, bench.py --steps 25 (10-real pivot links, 56-real clover, arithmetic neighbours, non-temporal clover loads and result stores)",
         "source": "profiles/" + R + "_pmc_bench.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, %d launches each)" % pmc[key]["FETCH_SIZE"]["launches"],
-        "note": "bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB: on gfx950 FETCH_SIZE tallies the 128 B requests of 16 B/lane streams at 64 B (MI355X_MICROARCH.md, HBM section; calibrated in round 1 with a known-byte copy, r01_pmc_dirac_gather.json). Infinity-Cache hits are counted, so this is fabric traffic and an upper bound on HBM traffic. 608 B/site is what the kernel's own layout has to move (24 in + 24 out + 48 link + 56 clover reals); the 816 B/site of the roofline figure is the reference's storage (SURVEY.md 8d).",
+        "note": "bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB: on gfx950 FETCH_SIZE tallies the 128 B requests of 16 B/lane streams at 64 B (MI355X_MICROARCH.md, HBM section; calibrated in round 1 with a known-byte copy, r01_pmc_dirac_gather.json). Infinity-Cache hits are counted, so this is fabric traffic and an upper bound on HBM traffic. 576 B/site is what the kernel's own layout has to move (24 in + 24 out + 40 link + 56 clover reals, the link bytes not counted); the 816 B/site of the roofline figure is the reference's storage (SURVEY.md 8d).",
     },
     "commit": commit, "kernel_source_sha16": bench.kernel_source_hash(),
 }
