@@ -91,6 +91,9 @@ def load_library():
         "ddamg_hip_set_gauge2": [vp, dp, dp, ctypes.c_int, dp],
         "ddamg_hip_set_gauge_device": [vp, dp, ctypes.c_int, dp],
         "ddamg_hip_set_gauge2_device": [vp, dp, dp, ctypes.c_int, dp],
+        "ddamg_hip_ildg_to_links_device": [vp, vp, ctypes.c_int, ctypes.c_longlong, dp],
+        "ddamg_hip_links_to_ildg_device": [vp, dp, ctypes.c_int, ctypes.c_longlong, vp],
+        "ddamg_hip_load_ildg_conf": [vp, ctypes.c_char_p, ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_clover_kernel_time": [vp, dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), dp],
         "ddamg_hip_vec_upload_device": [vp, vp, dp],
         "ddamg_hip_vec_download_device": [vp, vp, dp],
@@ -173,6 +176,13 @@ class VectorHeader(ctypes.Structure):
                 ("has_eigenvalues", ctypes.c_int), ("eigenvalues", ctypes.POINTER(ctypes.c_double))]
 
 
+class LimeInfo(ctypes.Structure):
+    """mirror of struct ddamg_hip_lime_info (include/ddamg_hip_io.h)"""
+    _fields_ = [("kind", ctypes.c_int), ("precision", ctypes.c_int), ("lattice", ctypes.c_int * 4), ("has_plaquette", ctypes.c_int),
+                ("plaquette", ctypes.c_double), ("data_offset", ctypes.c_longlong), ("data_length", ctypes.c_longlong),
+                ("num_records", ctypes.c_int)]
+
+
 def _io():
     lib = load_library()
     if not getattr(lib, "_io_ready", False):
@@ -185,6 +195,11 @@ def _io():
         lib.ddamg_hip_write_conf_multi.argtypes = [cs, ip, ip, ip, ctypes.c_int, dp, ctypes.c_double]
         lib.ddamg_hip_read_vectors.argtypes = [cs, ip, ip, ip, ctypes.c_int, ctypes.c_int, dp]
         lib.ddamg_hip_write_vectors.argtypes = [cs, ip, ip, ip, ctypes.c_int, ctypes.c_int, ctypes.POINTER(VectorHeader), dp]
+        lib.ddamg_hip_lime_info.argtypes = [cs, ctypes.POINTER(LimeInfo)]
+        lib.ddamg_hip_read_ildg_conf.argtypes = [cs, ip, ip, ip, dp, dp, ip]
+        lib.ddamg_hip_write_ildg_conf.argtypes = [cs, ip, ip, ip, ctypes.c_int, dp, ctypes.c_double]
+        lib.ddamg_hip_read_lime_vector.argtypes = [cs, ip, ip, ip, dp]
+        lib.ddamg_hip_write_lime_vector.argtypes = [cs, ip, ip, ip, ctypes.POINTER(VectorHeader), dp]
         lib._io_ready = True
     return lib
 
@@ -249,13 +264,73 @@ def write_vectors(path, global_lattice, vectors_local, header=None, process_grid
     n = a.size // (Vloc * 24)
     hp = None
     if header is not None:
-        ev = header.get("eigenvalues")
-        evbuf = np.ascontiguousarray(ev, dtype=np.float64) if ev is not None else None
-        h = VectorHeader(str(header.get("vector_type", "")).encode(), float(header.get("m0", 0)), float(header.get("csw", 0)),
-                         float(header.get("clov_plaq", 0)), float(header.get("hopp_plaq", 0)), str(header.get("clov_conf_name", "")).encode(),
-                         str(header.get("hopp_conf_name", "")).encode(), int(ev is not None), _dp(evbuf) if evbuf is not None else None)
+        h, _keep = _vector_header(header)
         hp = ctypes.byref(h)
     _io_check(_io().ddamg_hip_write_vectors(os.fsencode(path), _i4(global_lattice), _i4(process_grid), _i4(process_coords), n, int(big_endian), hp, _dp(a)))
+
+
+def _vector_header(header):
+    """(ddamg_hip_vector_header, what it points into) from the dict write_vectors documents"""
+    ev = header.get("eigenvalues")
+    evbuf = np.ascontiguousarray(ev, dtype=np.float64) if ev is not None else None
+    h = VectorHeader(str(header.get("vector_type", "")).encode(), float(header.get("m0", 0)), float(header.get("csw", 0)),
+                     float(header.get("clov_plaq", 0)), float(header.get("hopp_plaq", 0)), str(header.get("clov_conf_name", "")).encode(),
+                     str(header.get("hopp_conf_name", "")).encode(), int(ev is not None), _dp(evbuf) if evbuf is not None else None)
+    return h, evbuf
+
+
+LIME_KINDS = {0: None, 1: "gauge", 2: "vector"}
+
+
+def lime_info(path):
+    """what the record headers of a LIME file say (include/ddamg_hip_io.h): dict with kind (None, "gauge", "vector"), precision,
+    lattice [T,Z,Y,X], has_plaquette, plaquette (the file's number, in [0,1]), data_offset, data_length, num_records"""
+    info = LimeInfo()
+    _io_check(_io().ddamg_hip_lime_info(os.fsencode(path), ctypes.byref(info)))
+    return dict(kind=LIME_KINDS[info.kind], precision=info.precision, lattice=list(info.lattice), has_plaquette=bool(info.has_plaquette),
+                plaquette=info.plaquette, data_offset=info.data_offset, data_length=info.data_length, num_records=info.num_records)
+
+
+def read_ildg_conf(path, global_lattice, process_grid=(1, 1, 1, 1), process_coords=(0, 0, 0, 0), out=None):
+    """this process's part of an ILDG configuration (fp64 or fp32 file): ([V_local][4][9][2] links in the order T,Z,Y,X, plaquette
+    in [0,3] or None if the file has none); `out` takes the links instead of a fresh array"""
+    Vloc = int(np.prod([g // max(p, 1) for g, p in zip(global_lattice, process_grid)]))
+    if out is None:
+        out = np.zeros((Vloc, 4, 9, 2))
+    if out.dtype != np.float64 or not out.flags.c_contiguous or out.size != Vloc * 72:
+        raise DDAMGError("read_ildg_conf: `out` must be a C-contiguous float64 array of V_local*4*9 complex numbers")
+    plaq = ctypes.c_double(0); has = ctypes.c_int(0)
+    _io_check(_io().ddamg_hip_read_ildg_conf(os.fsencode(path), _i4(global_lattice), _i4(process_grid), _i4(process_coords), _dp(out),
+                                             ctypes.byref(plaq), ctypes.byref(has)))
+    return out, (plaq.value if has.value else None)
+
+
+def write_ildg_conf(path, global_lattice, gauge_local, plaq, process_grid=(1, 1, 1, 1), process_coords=(0, 0, 0, 0), precision=64):
+    """plaq in [0,3], as set_gauge returns it; the file carries plaq / 3"""
+    a = np.ascontiguousarray(gauge_local, dtype=np.float64)
+    _io_check(_io().ddamg_hip_write_ildg_conf(os.fsencode(path), _i4(global_lattice), _i4(process_grid), _i4(process_coords), int(precision), _dp(a), float(plaq)))
+
+
+def read_lime_vector(path, global_lattice, process_grid=(1, 1, 1, 1), process_coords=(0, 0, 0, 0), out=None):
+    """this process's part ([V_local][12][2]) of the spinor of a SciDAC/ETMC LIME file (fp64 or fp32)"""
+    Vloc = int(np.prod([g // max(p, 1) for g, p in zip(global_lattice, process_grid)]))
+    if out is None:
+        out = np.zeros((Vloc, 12, 2))
+    if out.dtype != np.float64 or not out.flags.c_contiguous or out.size != Vloc * 24:
+        raise DDAMGError("read_lime_vector: `out` must be a C-contiguous float64 array of V_local*12 complex numbers")
+    _io_check(_io().ddamg_hip_read_lime_vector(os.fsencode(path), _i4(global_lattice), _i4(process_grid), _i4(process_coords), _dp(out)))
+    return out
+
+
+def write_lime_vector(path, global_lattice, vector_local, header=None, process_grid=(1, 1, 1, 1), process_coords=(0, 0, 0, 0)):
+    """one spinor as the reference's four records (lime_write_info, src/lime_io.c:163-217); header: the dict of write_vectors"""
+    a = np.ascontiguousarray(vector_local, dtype=np.float64)
+    Vloc = int(np.prod([g // max(p, 1) for g, p in zip(global_lattice, process_grid)]))
+    if a.size != Vloc * 24:
+        raise DDAMGError("write_lime_vector: expected [V_local][12] complex numbers")
+    h, _keep = _vector_header(header) if header is not None else (None, None)
+    _io_check(_io().ddamg_hip_write_lime_vector(os.fsencode(path), _i4(global_lattice), _i4(process_grid), _i4(process_coords),
+                                                ctypes.byref(h) if h is not None else None, _dp(a)))
 
 
 def _check(rc):
@@ -288,6 +363,23 @@ def _dev(a, reals, what):
             raise DDAMGError(f"{what}: expected {reals} reals, got {a.numel()}")
         torch.cuda.current_stream(a.device).synchronize()
     return ctypes.cast(ctypes.c_void_p(int(a.data_ptr())), ctypes.POINTER(ctypes.c_double))
+
+
+def _dev_raw(a, what):
+    """the address of raw bytes in device memory (the library checks device, size and alignment): an integer address, or an object
+    with data_ptr() -- a torch tensor of any dtype, which must be contiguous and on the device, and whose stream is waited for"""
+    if isinstance(a, int):
+        return ctypes.c_void_p(a)
+    if not hasattr(a, "data_ptr"):
+        raise DDAMGError(f"{what}: expected an integer device address or an object with data_ptr(), got {type(a).__name__}")
+    if hasattr(a, "is_cuda"):
+        import torch
+        if not a.is_cuda:
+            raise DDAMGError(f"{what}: the tensor is in host memory")
+        if not a.is_contiguous():
+            raise DDAMGError(f"{what}: the tensor must be contiguous")
+        torch.cuda.current_stream(a.device).synchronize()
+    return ctypes.c_void_p(int(a.data_ptr()))
 
 
 def default_params():
@@ -379,6 +471,28 @@ class Context:
         _check(self._lib.ddamg_hip_set_gauge2_device(self._h, _dev(hopp_gauge_dev_lex, n, "set_gauge2_device"),
                                                      _dev(clover_gauge_dev_lex, n, "set_gauge2_device"), int(bool(anti_pbc)), ctypes.byref(plaq)))
         return plaq.value
+
+    def load_ildg_conf(self, path, anti_pbc=True):
+        """the configuration of an ILDG file becomes the operator (file -> pinned staging -> device links -> operator on a single
+        process; read_ildg_conf + set_gauge on a process grid).  Returns (plaquette computed from the links, the file's plaquette
+        times three or None if it has none), both in [0,3]"""
+        plaq = ctypes.c_double(0); fplaq = ctypes.c_double(0); has = ctypes.c_int(0)
+        _check(self._lib.ddamg_hip_load_ildg_conf(self._h, os.fsencode(path), int(bool(anti_pbc)), ctypes.byref(plaq), ctypes.byref(fplaq),
+                                                  ctypes.byref(has)))
+        return plaq.value, (fplaq.value if has.value else None)
+
+    def ildg_to_links_device(self, raw_dev, precision, nsites, links_dev):
+        """the data of an ildg-binary-data record in device memory (big-endian, fp64 or fp32, directions X,Y,Z,T) -> links
+        [nsites][4][9] complex float64 as set_gauge_device takes them; returns links_dev"""
+        _check(self._lib.ddamg_hip_ildg_to_links_device(self._h, _dev_raw(raw_dev, "ildg_to_links_device"), int(precision), int(nsites),
+                                                        _dev(links_dev, int(nsites) * 72, "ildg_to_links_device")))
+        return links_dev
+
+    def links_to_ildg_device(self, links_dev, precision, nsites, raw_dev):
+        """the inverse: links in device memory -> the bytes of an ildg-binary-data record (fp32: rounded to nearest); returns raw_dev"""
+        _check(self._lib.ddamg_hip_links_to_ildg_device(self._h, _dev(links_dev, int(nsites) * 72, "links_to_ildg_device"), int(precision), int(nsites),
+                                                        _dev_raw(raw_dev, "links_to_ildg_device")))
+        return raw_dev
 
     def clover_kernel_time(self, gauge_dev_lex, which, reps=10):
         """(milliseconds per launch, plaquette) of the field-strength kernel (which = 0), the host path's clover kernel (1) or

@@ -2,8 +2,11 @@
 #include "context.h"
 #include "gauge.h"
 #include "storage_refusal.h"
+#include "ildg_device.h"
+#include "io_common.h"
 #include <cstring>
 #include <string>
+#include <fcntl.h>
 
 using namespace ddamg;
 
@@ -234,16 +237,11 @@ static void ensure_host_mirror(ddamg_hip_ctx* c) {
   c->mirror_valid = true;
 }
 
-// links in device memory -> both fine operators, nothing through the host (ddamg_hip_set_gauge_device / _set_gauge2_device)
-static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+// links in device memory -> both fine operators, nothing through the host: what ddamg_hip_set_gauge_device / _set_gauge2_device
+// run on the caller's arrays and ddamg_hip_load_ildg_conf on its own
+static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette) {
   const Geometry& g = c->levels[0]->geom;
-  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": links in device memory are taken on a single process only, because the clover term on a "
-                                   "process grid needs the neighbours' links: use ddamg_hip_set_gauge there").c_str());
   const size_t V = g.V;
-  ddamg_require_device_array(c, hopp_dev, sizeof(double) * 72 * V, name);
-  if (clover_dev != hopp_dev) ddamg_require_device_array(c, clover_dev, sizeof(double) * 72 * V, name);
   DeviceBuffer<double> dD, dC;   // the staging arrays of FineOp::upload, filled on the device
   dD.alloc(72 * V);
   dC.alloc(84 * V);
@@ -258,6 +256,18 @@ static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const d
   std::vector<double>().swap(c->D_host);
   std::vector<double>().swap(c->clover_host);
   operator_replaced(c);
+}
+
+static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": links in device memory are taken on a single process only, because the clover term on a "
+                                   "process grid needs the neighbours' links: use ddamg_hip_set_gauge there").c_str());
+  const size_t V = g.V;
+  ddamg_require_device_array(c, hopp_dev, sizeof(double) * 72 * V, name);
+  if (clover_dev != hopp_dev) ddamg_require_device_array(c, clover_dev, sizeof(double) * 72 * V, name);
+  links_to_operator(c, hopp_dev, clover_dev, anti_pbc, plaquette);
 }
 
 // gauge field -> operator fields in the reference's storage (dirac_setup, src/dirac.c:60-168), no upload
@@ -311,6 +321,118 @@ int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* c, const double* hopp_gauge_dev_l
   // D from the first field, clover term and plaquette from the second, one layout pass
   DDAMG_API_BEGIN
   set_gauge_resident(c, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge2_device");
+  DDAMG_API_END
+}
+
+// ---- ILDG configurations ----
+static void require_ildg_arrays(const ddamg_hip_ctx* c, const void* raw_dev, int precision, long long nsites, const double* links_dev, const char* name) {
+  DDAMG_REQUIRE(c, "null context");
+  DDAMG_REQUIRE(precision == 32 || precision == 64, (std::string(name) + ": precision must be 32 or 64").c_str());
+  DDAMG_REQUIRE(nsites >= 0, (std::string(name) + ": negative number of sites").c_str());
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const size_t raw_bytes = (size_t)nsites * 72 * (precision / 8), link_bytes = (size_t)nsites * 72 * sizeof(double);
+  ddamg_require_device_array(c, raw_dev, raw_bytes, name);
+  ddamg_require_device_array(c, links_dev, link_bytes, name);
+  DDAMG_REQUIRE((uintptr_t)raw_dev % (precision == 64 ? 16 : 8) == 0 && (uintptr_t)links_dev % 16 == 0,
+                (std::string(name) + ": the arrays must be 16-byte aligned (fp32 file data: 8)").c_str());
+  const char* a = (const char*)raw_dev; const char* b = (const char*)links_dev;
+  DDAMG_REQUIRE(a + raw_bytes <= b || b + link_bytes <= a, (std::string(name) + ": the output and the input array overlap").c_str());
+}
+
+int ddamg_hip_ildg_to_links_device(ddamg_hip_ctx* c, const void* raw_dev, int precision, long long nsites, double* links_dev) {
+  DDAMG_API_BEGIN
+  require_ildg_arrays(c, raw_dev, precision, nsites, links_dev, "ddamg_hip_ildg_to_links_device");
+  ildg_to_links(raw_dev, precision, (size_t)nsites, links_dev, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_links_to_ildg_device(ddamg_hip_ctx* c, const double* links_dev, int precision, long long nsites, void* raw_dev) {
+  DDAMG_API_BEGIN
+  require_ildg_arrays(c, raw_dev, precision, nsites, links_dev, "ddamg_hip_links_to_ildg_device");
+  links_to_ildg(links_dev, precision, (size_t)nsites, raw_dev, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+namespace {
+struct Event {   // one per staging chunk of ddamg_hip_load_ildg_conf
+  hipEvent_t e = nullptr;
+  Event() { DDAMG_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+};
+struct File {
+  int fd;
+  explicit File(const char* path) : fd(open(path, O_RDONLY)) {}
+  ~File() { if (fd >= 0) close(fd); }
+  File(const File&) = delete;
+  File& operator=(const File&) = delete;
+};
+}  // namespace
+
+// file -> pinned staging -> device: the record of `info` as links [V][4][9] complex fp64 in `links`.  The pread of chunk k + 1
+// runs while the copy and the kernel of chunk k are on the stream; a pinned chunk is read into again once the copy out of it
+// (its event) is done, the one raw chunk on the device is reused in stream order.
+static void ildg_record_to_links(ddamg_hip_ctx* c, const char* path, const struct ddamg_hip_lime_info& info, size_t V, double* links) {
+  const size_t site_bytes = (size_t)72 * (info.precision / 8);
+  size_t chunk_sites = ((size_t)64 << 20) / site_bytes;
+  if (c->knobs.ildg_chunk_sites.set && c->knobs.ildg_chunk_sites.value > 0) chunk_sites = (size_t)c->knobs.ildg_chunk_sites.value;
+  if (chunk_sites > V) chunk_sites = V;
+  File file(path);
+  DDAMG_REQUIRE(file.fd >= 0, (std::string("cannot open LIME file '") + path + "'").c_str());
+  PinnedBuffer<char> pinned[2];
+  Event copied[2];
+  DeviceBuffer<char> raw;
+  pinned[0].alloc(chunk_sites * site_bytes);
+  if (chunk_sites < V) pinned[1].alloc(chunk_sites * site_bytes);
+  raw.alloc(chunk_sites * site_bytes);
+  bool in_flight[2] = {false, false};
+  size_t k = 0;
+  try {
+    for (size_t first = 0; first < V; first += chunk_sites, k++) {
+      const size_t n = V - first < chunk_sites ? V - first : chunk_sites;
+      const int b = (int)(k & 1);
+      if (in_flight[b]) DDAMG_HIP_CHECK(hipEventSynchronize(copied[b].e));
+      if (ddamg_io::pread_all(file.fd, pinned[b].get(), n * site_bytes, (off_t)(info.data_offset + (long long)(first * site_bytes))))
+        throw std::runtime_error(std::string("LIME file '") + path + "' ends early");
+      DDAMG_HIP_CHECK(hipMemcpyAsync(raw.get(), pinned[b].get(), n * site_bytes, hipMemcpyHostToDevice, c->stream));
+      DDAMG_HIP_CHECK(hipEventRecord(copied[b].e, c->stream));
+      in_flight[b] = true;
+      ildg_to_links(raw.get(), info.precision, n, links + first * 72, c->stream);
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(c->stream);   // nothing of the staging may be in use when it is released
+    throw;
+  }
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* c, const char* path, int anti_pbc, double* plaquette_out, double* file_plaquette_out, int* has_file_plaquette_out) {
+  DDAMG_API_BEGIN
+  DDAMG_REQUIRE(c && path, "null argument");
+  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  const Geometry& g = c->levels[0]->geom;
+  int G[4];
+  for (int mu = 0; mu < 4; mu++) G[mu] = g.L[mu] * g.P[mu];
+  double file_plaq = 0; int has_plaq = 0;
+  if (g.distributed()) {
+    // this process's part through the host, then the path that fetches the neighbours' links
+    std::vector<double> U((size_t)g.V * 72);
+    if (ddamg_hip_read_ildg_conf(path, G, g.P, g.pc, U.data(), &file_plaq, &has_plaq)) throw std::runtime_error(ddamg_hip_io_last_error());
+    if (ddamg_hip_set_gauge(c, U.data(), anti_pbc, plaquette_out)) return 1;   // the message is set
+  } else {
+    struct ddamg_hip_lime_info info;
+    if (ddamg_io::ildg_checked_info(path, G, &info)) throw std::runtime_error(ddamg_hip_io_last_error());
+    file_plaq = 3.0 * info.plaquette; has_plaq = info.has_plaquette;
+    DeviceBuffer<double> links;
+    links.alloc((size_t)g.V * 72);
+    ildg_record_to_links(c, path, info, (size_t)g.V, links);
+    links_to_operator(c, links, links, anti_pbc, plaquette_out);
+  }
+  if (file_plaquette_out) *file_plaquette_out = file_plaq;
+  if (has_file_plaquette_out) *has_file_plaquette_out = has_plaq;
   DDAMG_API_END
 }
 

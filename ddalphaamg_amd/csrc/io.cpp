@@ -1,5 +1,6 @@
 // io.cpp -- see include/ddamg_hip_io.h.  Host code only.
 #include "../../include/ddamg_hip_io.h"
+#include "io_common.h"
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -10,12 +11,15 @@
 #include <unistd.h>
 
 namespace {
-
 thread_local char g_err[512] = "";
-int fail(const char* fmt, ...) {
+}
+int ddamg_io::fail(const char* fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
   return -1;
 }
+using namespace ddamg_io;
+
+namespace {
 
 void swap8(void* p, size_t n) {
   unsigned char* b = static_cast<unsigned char*>(p);
@@ -26,43 +30,6 @@ void swap4(void* p, size_t n) {
   unsigned char* b = static_cast<unsigned char*>(p);
   for (size_t i = 0; i < n; i++, b += 4)
     for (int k = 0; k < 2; k++) { unsigned char t = b[k]; b[k] = b[3 - k]; b[3 - k] = t; }
-}
-
-struct Part {
-  int G[4], L[4], O[4];   // global extents, local extents, origin of this process
-  size_t Vloc, Vglob;
-};
-bool make_part(const int G[4], const int P[4], const int C[4], Part& p) {
-  p.Vloc = 1; p.Vglob = 1;
-  for (int mu = 0; mu < 4; mu++) {
-    const int np = P[mu] < 1 ? 1 : P[mu];
-    if (G[mu] < 1 || G[mu] % np || C[mu] < 0 || C[mu] >= np) return false;
-    p.G[mu] = G[mu]; p.L[mu] = G[mu] / np; p.O[mu] = C[mu] * p.L[mu];
-    p.Vloc *= p.L[mu]; p.Vglob *= G[mu];
-  }
-  return true;
-}
-
-// rows of L[X] consecutive sites: the unit the reference moves as well (read_size = 4*18*ll[X], bar_size = 24*ll[X])
-template <typename F>
-int for_rows(const Part& p, F&& f) {
-  size_t row = 0;
-  for (int t = 0; t < p.L[0]; t++) for (int z = 0; z < p.L[1]; z++) for (int y = 0; y < p.L[2]; y++, row++) {
-    const size_t gsite = (((size_t)(p.O[0] + t) * p.G[1] + (p.O[1] + z)) * p.G[2] + (p.O[2] + y)) * p.G[3] + p.O[3];
-    if (int rc = f(row, gsite)) return rc;
-  }
-  return 0;
-}
-
-int pread_all(int fd, void* buf, size_t n, off_t off) {
-  char* b = static_cast<char*>(buf);
-  while (n) { ssize_t r = pread(fd, b, n, off); if (r <= 0) return -1; b += r; off += r; n -= (size_t)r; }
-  return 0;
-}
-int pwrite_all(int fd, const void* buf, size_t n, off_t off) {
-  const char* b = static_cast<const char*>(buf);
-  while (n) { ssize_t r = pwrite(fd, b, n, off); if (r <= 0) return -1; b += r; off += r; n -= (size_t)r; }
-  return 0;
 }
 
 const size_t CONF_HEADER = 4 * sizeof(int32_t) + sizeof(double);
@@ -112,8 +79,6 @@ std::string format_header(const ddamg_hip_vector_header& h, const Part& p, int n
   s += "</header>\n";
   return s;
 }
-
-bool at_origin(const Part& p) { return p.O[0] == 0 && p.O[1] == 0 && p.O[2] == 0 && p.O[3] == 0; }
 
 }  // namespace
 

@@ -24,6 +24,9 @@ struct Knobs {
   bool link_pivot = true;           // DDAMG_LINK_PIVOT=0: the fp32 apply reads the two-row links instead of the 10-real pivot form
   bool clover_compression = true;   // DDAMG_CLOVER_COMPRESSION=0: the 72-real clover instead of the 56-real form of the fp32 apply
 
+  // ---- ILDG configuration files (ddamg_hip_load_ildg_conf) ----
+  OptionalInt ildg_chunk_sites;     // DDAMG_ILDG_CHUNK_SITES (tests): staging chunks of this many sites instead of 64 MiB of file data
+
   // ---- Schwarz smoother of the fine level (SapSmoother<T>::setup) ----
   // DDAMG_SAP_VARIANT  1: site-pair kernel, 2: thread-per-site kernel with resident operator, 3 (default): two blocks per
   // workgroup + face buffers where the shape allows (fp32, 4^4 blocks), else 2
@@ -75,6 +78,7 @@ struct Knobs {
     k.link_compression = unless_zero("DDAMG_LINK_COMPRESSION");
     k.link_pivot = unless_zero("DDAMG_LINK_PIVOT");
     k.clover_compression = unless_zero("DDAMG_CLOVER_COMPRESSION");
+    k.ildg_chunk_sites = integer("DDAMG_ILDG_CHUNK_SITES");
     if (const OptionalInt v = integer("DDAMG_SAP_VARIANT"); v.set) k.sap_variant = v.value;
     k.galerkin_unbatched = present("DDAMG_GALERKIN_UNBATCHED");
     k.galerkin_full_fields = present("DDAMG_GALERKIN_FULL_FIELDS");

@@ -120,6 +120,27 @@ int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* ctx, const double* hopp_gauge_dev
  * counterpart in the reference. */
 int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int which, int reps, float* milliseconds, double* plaquette);
 
+/* ---- ILDG configurations (file format: ddamg_hip_io.h) ----------------------------------------------------------------
+ * The raw data of an "ildg-binary-data" record in device memory -> links as ddamg_hip_set_gauge_device takes them, and back:
+ * raw_dev holds nsites x 4 x 9 complex numbers, big-endian, fp64 (precision 64) or fp32 (32), directions X,Y,Z,T per site;
+ * links_dev holds [nsites][4][9] complex fp64 in this library's order T,Z,Y,X.  One pass of a HIP kernel: byte order, direction
+ * order and precision (fp32 widened exactly on the way in, rounded to nearest on the way out; fp64 bit patterns pass through
+ * untouched).  For callers that read or write the record with their own parallel I/O; contract of "fields that live in device
+ * memory" above; both arrays 16-byte aligned (fp32 raw data: 8).  Replaces the host loops byteswap8 + swap_spin_in_conf of
+ * lime_read_conf (src/lime_io.c:50-72,273-314). */
+int ddamg_hip_ildg_to_links_device(ddamg_hip_ctx* ctx, const void* raw_dev, int precision, long long nsites, double* links_dev);
+int ddamg_hip_links_to_ildg_device(ddamg_hip_ctx* ctx, const double* links_dev, int precision, long long nsites, void* raw_dev);
+/* lime_read_conf + dirac_setup (src/lime_io.c:222-337, src/dirac.c:60-168): the configuration of an ILDG file becomes the
+ * operator.  Single process: the binary record is read in chunks (64 MiB of file data) into two pinned staging buffers, the read
+ * of one chunk overlapping the copy and the conversion kernel of the one before, and the links land in a device array from which
+ * the operator is built as ddamg_hip_set_gauge_device builds it; no host code touches a link.  On a process grid: this process's
+ * part through ddamg_hip_read_ildg_conf and ddamg_hip_set_gauge (a transport must be installed).  The file's lattice must be the
+ * context's global lattice.  *plaquette_out: the plaquette computed from the links, in [0,3]; *file_plaquette_out: three times the
+ * number of the file's "xlf-info" record if *has_file_plaquette_out (all three may be NULL).  A failure leaves the operator that
+ * was set before in place. */
+int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* ctx, const char* path, int anti_pbc, double* plaquette_out, double* file_plaquette_out,
+                             int* has_file_plaquette_out);
+
 /* direct upload of an operator in the reference's own storage (g.op_double.D: [V][36] complex,
  * g.op_double.clover: [V][42] complex; src/dirac.c:80,386-398) -- the path behind
  * dd_alpha_amg_get_gauge_pointer / dd_alpha_amg_get_clover_pointer (src/dirac.c:171-176). */
