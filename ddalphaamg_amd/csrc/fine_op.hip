@@ -38,6 +38,20 @@ __device__ __forceinline__ int tile_neighbor(const int* __restrict__ nb, size_t 
     return tn >= 0 ? tn * 256 + li : nb[(size_t)d * V + s];
   }
 }
+// the same with the tile's neighbour tile in direction d already in a scalar register (tn; dirac_apply_lds_kernel reads the eight
+// tile_nb entries of its tile once at its top: no scalar load and no wait for it in front of a face load)
+template <bool ARITH>
+__device__ __forceinline__ int tile_neighbor(const int* __restrict__ nb, size_t V, size_t s, int d, int tile0, const uint4& q, int tn) {
+  if constexpr (!ARITH) {
+    return nb[(size_t)d * V + s];
+  } else {
+    const unsigned w = (d >> 1) == 0 ? q.x : (d >> 1) == 1 ? q.y : (d >> 1) == 2 ? q.z : q.w;
+    const unsigned e = (d & 1) ? (w >> 16) : (w & 0xffffu);
+    const int li = (int)(e & 0x7fffu);
+    if (!(e & 0x8000u)) return tile0 + li;
+    return tn >= 0 ? tn * 256 + li : nb[(size_t)d * V + s];
+  }
+}
 
 // a site of an input vector of another precision (its own chunked layout), converted on the way in: the fp64 operator on the
 // fp32 iterates the V-cycle hands to the outer solver (FineOp<double>::apply_f32in)
@@ -56,7 +70,7 @@ __device__ __forceinline__ void load_site_as(const TIN* __restrict__ base, size_
 // optimised once before it is inlined into both, and both then need 143 VGPRs instead of 120)
 template <typename T, int MU, bool ARITH, LinkForm LF, bool HB2, typename TIN = T, bool CCL = false>
 __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const FineOpDev<T>& op, size_t s, bool live, int tile0, const uint4& q,
-                                         const T (&p)[24], T (&e)[24], T* __restrict__ sp, T* __restrict__ hb) {
+                                         const int (&tn)[8], const T (&p)[24], T (&e)[24], T* __restrict__ sp, T* __restrict__ hb) {
   const size_t V = op.V;
   const int t = threadIdx.x;
   T U[18];
@@ -71,7 +85,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
   }
   // (b) forward term with my own link
   if (live) {
-    const int j = tile_neighbor<ARITH>(op.nb, V, s, MU, tile0, q, op.tile_nb, (int)(V >> 8));
+    const int j = tile_neighbor<ARITH>(op.nb, V, s, MU, tile0, q, tn[MU]);
     if (j >= 0) {
       T pn[24];
       if (j - tile0 >= 0 && j - tile0 < 256) {
@@ -88,7 +102,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
   __syncthreads();
   // (c) backward term: product computed by site s-mu (in LDS) or, across the tile face, from global memory
   if (live) {
-    const int j = tile_neighbor<ARITH>(op.nb, V, s, 4 + MU, tile0, q, op.tile_nb, (int)(V >> 8));
+    const int j = tile_neighbor<ARITH>(op.nb, V, s, 4 + MU, tile0, q, tn[4 + MU]);
     if (j < 0) {
       halo_backward<T, MU>(op, -1 - j, e);
     } else if (j - tile0 >= 0 && j - tile0 < 256) {
@@ -105,6 +119,13 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
   }
   if constexpr (!HB2) __syncthreads();   // HB2: the caller alternates between two hb buffers, one barrier per direction
 }
+
+// The order in which dirac_apply_lds_kernel walks the directions (mu: 0 = T, 1 = Z, 2 = Y, 3 = X), shared by every instantiation:
+// X, Y, T, Z.  The X and Y neighbour tiles run on the same XCD at about the same time and staged their spinors at their start, so
+// these face reads come first, while the lines are still in the L2; a T face belongs to another XCD and misses whenever it is read,
+// and a Z neighbour (64 tiles away in the XCD's sequence) ran too long ago.  The order of the sum of the eight hop terms follows
+// the list, so results change by rounding with it (docs/design/04_kernels.md has what was measured for the other orders).
+constexpr int kDirOrder[4] = {3, 2, 0, 1};
 
 // CCL: the clover term from its 56-real form (FineOpDev::cloverc, fp32 only)
 template <typename T, bool ARITH, LinkForm LF = LinkForm::Full, typename TIN = T, bool CCL = false>
@@ -128,6 +149,12 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
   T p[24], e[24];
   uint4 q = make_uint4(0, 0, 0, 0);
   if constexpr (ARITH) q = reinterpret_cast<const uint4*>(op.tnb)[threadIdx.x];
+  // the tile's eight neighbour tiles: the index is wave-uniform, so these are scalar loads, issued once here
+  int tn[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (ARITH) {
+#pragma unroll
+    for (int d = 0; d < 8; d++) tn[d] = op.tile_nb[(size_t)d * (V >> 8) + tile];
+  }
   if (live) load_site_as<T, TIN, 24>(phi, V, s, p);
   else {
 #pragma unroll
@@ -151,10 +178,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
     }
   }
   __syncthreads();
-  tile_dir<T, 0, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 1, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
-  tile_dir<T, 2, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb);
-  tile_dir<T, 3, ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, p, e, sp, hb1);
+  // the two hb buffers alternate with the position in the list, whichever direction stands there
+  tile_dir<T, kDirOrder[0], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
+  tile_dir<T, kDirOrder[1], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
+  tile_dir<T, kDirOrder[2], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
+  tile_dir<T, kDirOrder[3], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
   if (live) store_site<T, 24, DDAMG_NT_STORE>(eta, V, s, e);
 }
 
