@@ -92,6 +92,13 @@ template <typename T> void vec_multi_dot(const T* X, size_t xstride, int m, cons
 void arnoldi_norm_from_dots(double* d_h, int m, hipStream_t st);
 // d_out[0] = ||x||_2
 template <typename T> void vec_norm(const T* x, View v, ReduceWork& rw, double* d_out, hipStream_t st);
+// ||x||_2 on the host: vec_norm, the copy of the one number and a wait for the stream
+template <typename T> double host_norm(const T* x, View v, ReduceWork& rw, hipStream_t st) {
+  vec_norm<T>(x, v, rw, rw.d_result, st);
+  DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double), hipMemcpyDeviceToHost, st));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(st));
+  return rw.h_result[0];
+}
 // fused pair used by MinRes-type updates:  d_out[0..1] = <x,y>, d_out[2] = <x,x>
 template <typename T> void vec_dot_and_norm2(const T* x, const T* y, View v, ReduceWork& rw, double* d_out, hipStream_t st);
 

@@ -1,5 +1,5 @@
 // capi.cpp -- implementation of the thin C-ABI (include/ddamg_hip.h).
-#include "context.h"
+#include "capi_common.h"
 #include "gauge.h"
 #include "storage_refusal.h"
 #include "ildg_device.h"
@@ -11,20 +11,6 @@
 using namespace ddamg;
 
 thread_local std::string g_ddamg_last_error;
-#define g_last_error g_ddamg_last_error
-
-#define DDAMG_API_BEGIN try {
-#define DDAMG_API_END                                  \
-  }                                                    \
-  catch (const std::exception& e) {                    \
-    g_last_error = e.what();                           \
-    return 1;                                          \
-  }                                                    \
-  catch (...) {                                        \
-    g_last_error = "unknown error";                    \
-    return 1;                                          \
-  }                                                    \
-  return 0;
 
 ddamg_hip_ctx::~ddamg_hip_ctx() {
   (void)hipSetDevice(device);
@@ -51,10 +37,9 @@ static const char* storage_refusal(const ddamg_hip_ctx* c, StorageKind kind) {
 // ddamg_hip_set_coarse_storage / _transfer_ / _intermediate_: name is the word their messages begin with
 static int set_storage(ddamg_hip_ctx* c, StorageKind kind, int bits, const char* name) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
+  enter(c);
   DDAMG_REQUIRE(bits == 16 || bits == 32, (std::string(name) + " storage: bits must be 16 or 32").c_str());
   if (bits == 16) if (const char* why = storage_refusal(c, kind)) throw std::runtime_error(why);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   if (c->mg32) c->mg32->set_storage(kind, bits);
   c->storage.bits[kind] = bits;
   DDAMG_API_END
@@ -83,7 +68,7 @@ void ddamg_require_disjoint(const void* out, const void* in, size_t bytes, const
 
 extern "C" {
 
-const char* ddamg_hip_last_error(void) { return g_last_error.c_str(); }
+const char* ddamg_hip_last_error(void) { return g_ddamg_last_error.c_str(); }
 
 void ddamg_hip_default_params(ddamg_hip_params* p) {
   // reference defaults: src/init.c:778-812 (per level), :833-868 (general), :946-953 (k-cycle)
@@ -190,6 +175,8 @@ int ddamg_hip_memory_in_use(size_t* device_bytes, size_t* pinned_bytes) {
 
 int ddamg_hip_link_reals(ddamg_hip_ctx* c, int* reals) {
   DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(reals, "null argument");
   DDAMG_REQUIRE(c->have_operator, "link_reals: no operator uploaded");
   *reals = c->fop32.link_reals();
   DDAMG_API_END
@@ -204,11 +191,15 @@ static void drop_clover_base(ddamg_hip_ctx* c) {
   c->scale_even = c->scale_odd = 1.0;
 }
 
+// the coarse operators of a hierarchy that is set up, from the fine operator as it is now
+static void rebuild_coarse_operators(ddamg_hip_ctx* c) {
+  if (c->setup_done) for_each_mg(c, [](auto& mg) { mg.operator_changed(); mg.release_setup_workspace(); });
+}
+
 // what follows the upload of a new fine operator, from host arrays or from device arrays
 static void operator_replaced(ddamg_hip_ctx* c) {
   c->have_operator = true;
-  if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
-  if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
+  rebuild_coarse_operators(c);
 }
 
 static void upload_operator(ddamg_hip_ctx* c) {
@@ -259,8 +250,7 @@ static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const do
 }
 
 static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   const Geometry& g = c->levels[0]->geom;
   DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": links in device memory are taken on a single process only, because the clover term on a "
                                    "process grid needs the neighbours' links: use ddamg_hip_set_gauge there").c_str());
@@ -281,35 +271,23 @@ static double gauge_fields(ddamg_hip_ctx* c, const double* gauge_lex, int anti_p
   return gauge_to_operator_device(g.L, gauge_lex, anti_pbc, c->par.m0, c->par.csw, D_out, clover_out, c->stream);
 }
 
-int ddamg_hip_set_gauge(ddamg_hip_ctx* c, const double* gauge_lex, int anti_pbc, double* plaquette) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && gauge_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const Geometry& g = c->levels[0]->geom;
-  c->D_host.resize((size_t)g.V * 72);
-  c->clover_host.resize((size_t)g.V * 84);
-  const double pl = gauge_fields(c, gauge_lex, anti_pbc, c->D_host.data(), c->clover_host.data());
-  if (plaquette) *plaquette = pl;
-  upload_operator(c);
-  DDAMG_API_END
-}
-
 int ddamg_hip_set_gauge2(ddamg_hip_ctx* c, const double* hopp_gauge_lex, const double* clover_gauge_lex, int anti_pbc, double* plaquette) {
   // D from the first field, clover term and plaquette from the second, ONE upload (and one rebuild of the hierarchy)
-  if (hopp_gauge_lex == clover_gauge_lex) return ddamg_hip_set_gauge(c, hopp_gauge_lex, anti_pbc, plaquette);
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && hopp_gauge_lex && clover_gauge_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(hopp_gauge_lex && clover_gauge_lex, "null argument");
   const Geometry& g = c->levels[0]->geom;
   c->D_host.resize((size_t)g.V * 72);
   c->clover_host.resize((size_t)g.V * 84);
-  std::vector<double> D_unused((size_t)g.V * 72), cl_unused((size_t)g.V * 84);
-  gauge_fields(c, hopp_gauge_lex, anti_pbc, c->D_host.data(), cl_unused.data());
-  const double pl = gauge_fields(c, clover_gauge_lex, anti_pbc, D_unused.data(), c->clover_host.data());
+  const bool two = hopp_gauge_lex != clover_gauge_lex;   // one field: both parts from one pass
+  std::vector<double> D_unused(two ? (size_t)g.V * 72 : 0), cl_unused(two ? (size_t)g.V * 84 : 0);
+  if (two) gauge_fields(c, hopp_gauge_lex, anti_pbc, c->D_host.data(), cl_unused.data());
+  const double pl = gauge_fields(c, clover_gauge_lex, anti_pbc, two ? D_unused.data() : c->D_host.data(), c->clover_host.data());
   if (plaquette) *plaquette = pl;
   upload_operator(c);
   DDAMG_API_END
 }
+int ddamg_hip_set_gauge(ddamg_hip_ctx* c, const double* gauge_lex, int anti_pbc, double* plaquette) { return ddamg_hip_set_gauge2(c, gauge_lex, gauge_lex, anti_pbc, plaquette); }
 
 int ddamg_hip_set_gauge_device(ddamg_hip_ctx* c, const double* gauge_dev_lex, int anti_pbc, double* plaquette) {
   DDAMG_API_BEGIN
@@ -326,10 +304,9 @@ int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* c, const double* hopp_gauge_dev_l
 
 // ---- ILDG configurations ----
 static void require_ildg_arrays(const ddamg_hip_ctx* c, const void* raw_dev, int precision, long long nsites, const double* links_dev, const char* name) {
-  DDAMG_REQUIRE(c, "null context");
+  enter(c);
   DDAMG_REQUIRE(precision == 32 || precision == 64, (std::string(name) + ": precision must be 32 or 64").c_str());
   DDAMG_REQUIRE(nsites >= 0, (std::string(name) + ": negative number of sites").c_str());
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const size_t raw_bytes = (size_t)nsites * 72 * (precision / 8), link_bytes = (size_t)nsites * 72 * sizeof(double);
   ddamg_require_device_array(c, raw_dev, raw_bytes, name);
   ddamg_require_device_array(c, links_dev, link_bytes, name);
@@ -411,8 +388,8 @@ static void ildg_record_to_links(ddamg_hip_ctx* c, const char* path, const struc
 
 int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* c, const char* path, int anti_pbc, double* plaquette_out, double* file_plaquette_out, int* has_file_plaquette_out) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && path, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(path, "null argument");
   const Geometry& g = c->levels[0]->geom;
   int G[4];
   for (int mu = 0; mu < 4; mu++) G[mu] = g.L[mu] * g.P[mu];
@@ -438,8 +415,8 @@ int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* c, const char* path, int anti_pbc, d
 
 int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* c, const double* gauge_dev_lex, int which, int reps, float* milliseconds, double* plaquette) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && milliseconds, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(milliseconds, "null argument");
   const Geometry& g = c->levels[0]->geom;
   DDAMG_REQUIRE(!g.distributed(), "ddamg_hip_clover_kernel_time: single process only");
   ddamg_require_device_array(c, gauge_dev_lex, sizeof(double) * 72 * g.V, "ddamg_hip_clover_kernel_time");
@@ -453,19 +430,16 @@ int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* c, const double* gauge_dev_lex, 
 // No upload, no Galerkin construction; the host copy handed out by dd_alpha_amg_get_clover_pointer follows.
 int ddamg_hip_shift_mass(ddamg_hip_ctx* c, double new_m0) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->have_operator, "no operator set");
+  enter(c);
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
   DDAMG_REQUIRE(c->scale_even == 1.0 && c->scale_odd == 1.0, "shift_mass on a scaled operator: undo ddamg_hip_scale_clover first (scale 1, 1)");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const double diff = new_m0 - c->par.m0;
   if (diff != 0.0) {
     drop_clover_base(c);
     const size_t V = c->levels[0]->geom.V;
     c->fop64.shift_diagonal(c->fop64.clover_field(), diff, c->stream);
     c->fop32.shift_diagonal(c->fop64.clover_field(), 0.0, c->stream);
-    if (c->setup_done) {
-      if (c->mg32) c->mg32->mass_shifted(diff);
-      if (c->mg64) c->mg64->mass_shifted(diff);
-    }
+    if (c->setup_done) for_each_mg(c, [&](auto& mg) { mg.mass_shifted(diff); });
     if (c->mirror_valid)   // a stale host copy stays stale: what rebuilds it reads the device fields shifted above
       for (size_t s = 0; s < V; s++)
         for (int k = 0; k < 12; k++) c->clover_host[(s * 42 + k) * 2] += diff;
@@ -482,8 +456,8 @@ int ddamg_hip_shift_mass(ddamg_hip_ctx* c, double new_m0) {
 // keeps the unscaled field, as the reference's does after its solve.
 int ddamg_hip_scale_clover(ddamg_hip_ctx* c, double scale_even, double scale_odd) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->have_operator, "no operator set");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
   if (scale_even == c->scale_even && scale_odd == c->scale_odd) return 0;
   const size_t bytes = sizeof(double) * 72 * (size_t)c->levels[0]->geom.V;
   if (!c->clover_base) {
@@ -493,8 +467,7 @@ int ddamg_hip_scale_clover(ddamg_hip_ctx* c, double scale_even, double scale_odd
   c->fop64.scale_clover(c->clover_base, scale_even, scale_odd, c->stream);
   c->fop32.scale_clover(c->clover_base, scale_even, scale_odd, c->stream);
   c->scale_even = scale_even; c->scale_odd = scale_odd;
-  if (c->mg32 && c->setup_done) { c->mg32->operator_changed(); c->mg32->release_setup_workspace(); }
-  if (c->mg64 && c->setup_done) { c->mg64->operator_changed(); c->mg64->release_setup_workspace(); }
+  rebuild_coarse_operators(c);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (scale_even == 1.0 && scale_odd == 1.0) c->clover_base.reset();
   DDAMG_API_END
@@ -502,8 +475,8 @@ int ddamg_hip_scale_clover(ddamg_hip_ctx* c, double scale_even, double scale_odd
 
 int ddamg_hip_set_operator(ddamg_hip_ctx* c, const double* D_lex, const double* clover_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && D_lex && clover_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(D_lex && clover_lex, "null argument");
   const Geometry& g = c->levels[0]->geom;
   if (D_lex != c->D_host.data()) c->D_host.assign(D_lex, D_lex + (size_t)g.V * 72);
   if (clover_lex != c->clover_host.data()) c->clover_host.assign(clover_lex, clover_lex + (size_t)g.V * 84);
@@ -524,8 +497,7 @@ static void install_comm(ddamg_hip_ctx* c, Comm* comm) {
   c->fop32.set_comm(comm);
   c->fop64.set_comm(comm);
   c->rw_outer.comm = comm; c->rw_blas.comm = comm; c->rw_mp.comm = comm;
-  if (c->mg32) c->mg32->set_comm(comm);
-  if (c->mg64) c->mg64->set_comm(comm);
+  for_each_mg(c, [&](auto& mg) { mg.set_comm(comm); });
   // creating a communicator may draw from libc rand() inside the communication library (observed: the first RCCL
   // communicator of a process does); the reference's test vectors come from the stream seeded at init and touched by
   // nothing else (src/init.c:870-873), so restore that state
@@ -534,16 +506,15 @@ static void install_comm(ddamg_hip_ctx* c, Comm* comm) {
 
 int ddamg_hip_comm_init_rccl(ddamg_hip_ctx* c, const void* id128) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && id128, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(id128, "null argument");
   install_comm(c, comm_create_rccl(c->levels[0]->geom, id128, comm_cus_for(c->knobs, c->par.num_levels)));
   DDAMG_API_END
 }
 
 int ddamg_hip_comm_init_host(ddamg_hip_ctx* c, ddamg_hip_exchange_fn fn, ddamg_hip_allreduce_fn reduce_fn, void* user) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   install_comm(c, comm_create_host(c->levels[0]->geom, fn, reduce_fn, user, comm_cus_for(c->knobs, c->par.num_levels)));
   DDAMG_API_END
 }
@@ -569,8 +540,8 @@ int ddamg_hip_halo_plan(const int local_lattice[4], const int process_grid[4], c
 
 int ddamg_hip_get_operator(ddamg_hip_ctx* c, double* D_lex, double* clover_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->have_operator, "no operator set");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
   ensure_host_mirror(c);
   if (D_lex) memcpy(D_lex, c->D_host.data(), sizeof(double) * c->D_host.size());
   if (clover_lex) memcpy(clover_lex, c->clover_host.data(), sizeof(double) * c->clover_host.size());
@@ -579,10 +550,10 @@ int ddamg_hip_get_operator(ddamg_hip_ctx* c, double* D_lex, double* clover_lex) 
 
 int ddamg_hip_vec_create(ddamg_hip_ctx* c, int level, int precision, ddamg_hip_vec** out) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && out, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(out, "null argument");
   DDAMG_REQUIRE(level >= 0 && level < (int)c->levels.size(), "level out of range");
   DDAMG_REQUIRE(precision == 32 || precision == 64, "precision must be 32 or 64");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   std::unique_ptr<ddamg_hip_vec> v(new ddamg_hip_vec);
   v->level = level; v->precision = precision;
   v->ndof = c->levels[level]->ndof;
@@ -596,46 +567,48 @@ int ddamg_hip_vec_create(ddamg_hip_ctx* c, int level, int precision, ddamg_hip_v
 
 int ddamg_hip_vec_destroy(ddamg_hip_ctx* c, ddamg_hip_vec* v) {
   DDAMG_API_BEGIN
-  if (!v) return 0;
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  if (!v) return 0;   // as free(NULL)
+  enter(c);
   (void)hipStreamSynchronize(c->stream);
   delete v;
   DDAMG_API_END
 }
 
+// fp64 numbers in lattice order in device memory -> the vector in its layout and precision, and back
+static void vec_from_lex_any(ddamg_hip_ctx* c, ddamg_hip_vec* v, const double* src_dev) {
+  const int* tab = c->levels[v->level]->d_lex_of_site;
+  with_vec(v, [&](auto* p) {
+    if (v->aos) aos_from_lex(p, src_dev, tab, v->V, v->ndof, c->stream);
+    else vec_from_lex(p, src_dev, tab, v->V, v->ndof, c->stream);
+  });
+}
+static void vec_to_lex_any(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* dst_dev) {
+  const int* tab = c->levels[v->level]->d_lex_of_site;
+  with_vec(v, [&](const auto* p) {
+    if (v->aos) aos_to_lex(dst_dev, p, tab, v->V, v->ndof, c->stream);
+    else vec_to_lex(dst_dev, p, tab, v->V, v->ndof, c->stream);
+  });
+}
+
 int ddamg_hip_vec_upload(ddamg_hip_ctx* c, ddamg_hip_vec* v, const double* host_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && v && host_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  size_t nb = (size_t)v->V * v->ndof * 2 * sizeof(double);
+  enter(c);
+  DDAMG_REQUIRE(v && host_lex, "null argument");
+  const size_t nb = sizeof(double) * vec_len(v);
   double* st = c->stage(nb);
   DDAMG_HIP_CHECK(hipMemcpyAsync(st, host_lex, nb, hipMemcpyHostToDevice, c->stream));
-  const int* tab = c->levels[v->level]->d_lex_of_site;
-  if (v->aos) {
-    if (v->precision == 32) aos_from_lex<float>((float*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
-    else aos_from_lex<double>((double*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
-  } else {
-    if (v->precision == 32) vec_from_lex<float>((float*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
-    else vec_from_lex<double>((double*)v->data.get(), st, tab, v->V, v->ndof, c->stream);
-  }
+  vec_from_lex_any(c, v, st);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }
 
 int ddamg_hip_vec_download(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* host_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && v && host_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  size_t nb = (size_t)v->V * v->ndof * 2 * sizeof(double);
+  enter(c);
+  DDAMG_REQUIRE(v && host_lex, "null argument");
+  const size_t nb = sizeof(double) * vec_len(v);
   double* st = c->stage(nb);
-  const int* tab = c->levels[v->level]->d_lex_of_site;
-  if (v->aos) {
-    if (v->precision == 32) aos_to_lex<float>(st, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
-    else aos_to_lex<double>(st, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
-  } else {
-    if (v->precision == 32) vec_to_lex<float>(st, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
-    else vec_to_lex<double>(st, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
-  }
+  vec_to_lex_any(c, v, st);
   DDAMG_HIP_CHECK(hipMemcpyAsync(host_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
@@ -643,54 +616,41 @@ int ddamg_hip_vec_download(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* hos
 
 int ddamg_hip_vec_upload_device(ddamg_hip_ctx* c, ddamg_hip_vec* v, const double* dev_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && v, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  ddamg_require_device_array(c, dev_lex, (size_t)v->V * v->ndof * 2 * sizeof(double), "ddamg_hip_vec_upload_device");
-  const int* tab = c->levels[v->level]->d_lex_of_site;
-  if (v->aos) {
-    if (v->precision == 32) aos_from_lex<float>((float*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
-    else aos_from_lex<double>((double*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
-  } else {
-    if (v->precision == 32) vec_from_lex<float>((float*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
-    else vec_from_lex<double>((double*)v->data.get(), dev_lex, tab, v->V, v->ndof, c->stream);
-  }
+  enter(c);
+  DDAMG_REQUIRE(v, "null argument");
+  ddamg_require_device_array(c, dev_lex, sizeof(double) * vec_len(v), "ddamg_hip_vec_upload_device");
+  vec_from_lex_any(c, v, dev_lex);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }
 
 int ddamg_hip_vec_download_device(ddamg_hip_ctx* c, const ddamg_hip_vec* v, double* dev_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && v, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  ddamg_require_device_array(c, dev_lex, (size_t)v->V * v->ndof * 2 * sizeof(double), "ddamg_hip_vec_download_device");
-  const int* tab = c->levels[v->level]->d_lex_of_site;
-  if (v->aos) {
-    if (v->precision == 32) aos_to_lex<float>(dev_lex, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
-    else aos_to_lex<double>(dev_lex, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
-  } else {
-    if (v->precision == 32) vec_to_lex<float>(dev_lex, (const float*)v->data.get(), tab, v->V, v->ndof, c->stream);
-    else vec_to_lex<double>(dev_lex, (const double*)v->data.get(), tab, v->V, v->ndof, c->stream);
-  }
+  enter(c);
+  DDAMG_REQUIRE(v, "null argument");
+  ddamg_require_device_array(c, dev_lex, sizeof(double) * vec_len(v), "ddamg_hip_vec_download_device");
+  vec_to_lex_any(c, v, dev_lex);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }
 
 int ddamg_hip_dirac_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && out && in, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(out && in, "null argument");
   DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
   DDAMG_REQUIRE(out->level == 0 && in->level == 0, "fine-level vectors expected");
   DDAMG_REQUIRE(out->precision == in->precision, "precision mismatch");
   DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place apply is not supported");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (in->precision == 32) c->fop32.apply((float*)out->data.get(), (const float*)in->data.get(), c->stream);
-  else c->fop64.apply((double*)out->data.get(), (const double*)in->data.get(), c->stream);
+  if (in->precision == 32) c->fop32.apply(vec_data<float>(out), vec_data<float>(in), c->stream);
+  else c->fop64.apply(vec_data<double>(out), vec_data<double>(in), c->stream);
   DDAMG_API_END
 }
 
 int ddamg_hip_get_site_order(ddamg_hip_ctx* c, int level, int* lex_of_site) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && lex_of_site, "null argument");
+  DDAMG_REQUIRE(c, "null context");   // host tables only: no device is selected
+  DDAMG_REQUIRE(lex_of_site, "null argument");
   DDAMG_REQUIRE(level >= 0 && level < (int)c->levels.size(), "level out of range");
   const Geometry& g = c->levels[level]->geom;
   for (int s = 0; s < g.V; s++) lex_of_site[s] = g.lex_of_site[s];
@@ -699,13 +659,14 @@ int ddamg_hip_get_site_order(ddamg_hip_ctx* c, int level, int* lex_of_site) {
 
 int ddamg_hip_timer_begin(ddamg_hip_ctx* c) {
   DDAMG_API_BEGIN
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   DDAMG_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
   DDAMG_API_END
 }
 int ddamg_hip_timer_end(ddamg_hip_ctx* c, float* ms) {
   DDAMG_API_BEGIN
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(ms, "null argument");
   DDAMG_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
   DDAMG_HIP_CHECK(hipEventSynchronize(c->ev1));
   DDAMG_HIP_CHECK(hipEventElapsedTime(ms, c->ev0, c->ev1));
@@ -713,7 +674,7 @@ int ddamg_hip_timer_end(ddamg_hip_ctx* c, float* ms) {
 }
 int ddamg_hip_sync(ddamg_hip_ctx* c) {
   DDAMG_API_BEGIN
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }

@@ -680,12 +680,7 @@ double Multigrid<T>::tick(const char* phase, double t0) {
 
 template <typename T>
 double Multigrid<T>::norm_of(int l, const T* v) {
-  MGLevel<T>& lv = *lv_[l];
-  ReduceWork& rw = lv_[l]->rw;
-  vec_norm<T>(v, whole(lv.nel), rw, rw.d_result, st_);
-  DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double), hipMemcpyDeviceToHost, st_));
-  DDAMG_HIP_CHECK(hipStreamSynchronize(st_));
-  return rw.h_result[0];
+  return host_norm<T>(v, whole(lv_[l]->nel), lv_[l]->rw, st_);
 }
 
 // vector_PRECISION_define_random (src/data_generic.c:42-56): libc rand(), in the order of the reference's

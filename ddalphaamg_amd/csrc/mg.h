@@ -82,6 +82,7 @@ struct GatheredCoarsest {
 template <typename T>
 class Multigrid {
  public:
+  typedef T real;
   // knobs: the context's switches (knobs.h); they outlive the hierarchy and reach every object created for it
   Multigrid(const ddamg_hip_params& par, const Knobs& knobs, const std::vector<const Geometry*>& geoms, const FineOp<T>* fop, hipStream_t st);
   ~Multigrid();   // waits for the stream; the members free themselves

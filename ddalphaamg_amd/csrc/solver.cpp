@@ -2,27 +2,11 @@
 // Reference: method_setup / method_update src/init.c:134-374, wilson_driver src/top_level.c:64-104,
 // fgmres_double + preconditioner (mixed precision 1) src/linsolve_generic.c:219-413, src/preconditioner.c:25-69.
 #include <chrono>
-#include "context.h"
+#include "capi_common.h"
 #include <cstring>
 #include <cstdio>
-#include <string>
 
 using namespace ddamg;
-
-extern thread_local std::string g_ddamg_last_error;
-
-#define DDAMG_API_BEGIN try {
-#define DDAMG_API_END                                  \
-  }                                                    \
-  catch (const std::exception& e) {                    \
-    g_ddamg_last_error = e.what();                     \
-    return 1;                                          \
-  }                                                    \
-  catch (...) {                                        \
-    g_ddamg_last_error = "unknown error";              \
-    return 1;                                          \
-  }                                                    \
-  return 0;
 
 static void ensure_mg(ddamg_hip_ctx* c) {
   if (c->levels[0]->geom.distributed()) {
@@ -128,12 +112,7 @@ static int solve_cgn(ddamg_hip_ctx* c, double tol, double* relres) {
     DDAMG_HIP_CHECK(hipStreamSynchronize(st));
     return cd(rw.h_result[0], rw.h_result[1]);
   };
-  auto norm = [&](const double* a) {
-    vec_norm<double>(a, all, rw, rw.d_result, st);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double), hipMemcpyDeviceToHost, st));
-    DDAMG_HIP_CHECK(hipStreamSynchronize(st));
-    return rw.h_result[0];
-  };
+  auto norm = [&](const double* a) { return host_norm<double>(a, all, rw, st); };
   auto axpy = [&](double* z, const double* xx, const double* y, cd a) { vec_axpy<double>(z, xx, y, a.real(), a.imag(), all, st); };
   const int maxiter = c->par.restart * c->par.max_restart;
   int iter = 0;
@@ -214,12 +193,7 @@ static int solve_mp(ddamg_hip_ctx* c, double tol, double* relres) {
   int iter = 0, finish = 0;
   double norm_r0 = 1, gamma_jp1 = 1;
   c->last_history.clear();
-  auto dnorm = [&](const double* v) {
-    vec_norm<double>(v, all, rw, rw.d_result, c->stream);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return rw.h_result[0];
-  };
+  auto dnorm = [&](const double* v) { return host_norm<double>(v, all, rw, c->stream); };
   for (int ol = 0; ol < c->par.max_restart && !finish; ol++) {
     if (ol == 0) vec_copy<double>(c->mp_r, c->mp_b, all, c->stream);
     else { c->fop64.apply(c->mp_r, c->mp_x, c->stream); vec_minus<double>(c->mp_r, c->mp_b, c->mp_r, all, c->stream); }
@@ -246,6 +220,87 @@ static int solve_mp(ddamg_hip_ctx* c, double tol, double* relres) {
   return iter;
 }
 
+// coarsest-level iterations since the last reset, of whichever hierarchy exists
+static void reset_coarse_iterations(ddamg_hip_ctx* c) { for_each_mg(c, [](auto& mg) { mg.coarse_iter_count = 0; }); }
+static int coarse_iterations_of(ddamg_hip_ctx* c) {
+  int n = 0;
+  for_each_mg(c, [&](auto& mg) { n += mg.coarse_iter_count; });
+  return n;
+}
+
+static void shift_mass_or_throw(ddamg_hip_ctx* c, double m0) {
+  if (ddamg_hip_shift_mass(c, m0)) throw std::runtime_error(g_ddamg_last_error);
+}
+
+// the num_vect[0] fine-level vectors column(mg, k) names, one after the other in lattice order into host memory
+template <typename Column>
+static void download_columns(ddamg_hip_ctx* c, double* host_lex, Column column) {
+  const int V = c->levels[0]->geom.V;
+  const size_t nel = (size_t)24 * V;
+  double* st = c->stage(sizeof(double) * nel);
+  with_mg(c, [&](auto& mg) {
+    for (int k = 0; k < c->par.num_vect[0]; k++) {
+      vec_to_lex(st, column(mg, k), c->levels[0]->d_lex_of_site, V, 12, c->stream);
+      DDAMG_HIP_CHECK(hipMemcpyAsync(host_lex + (size_t)k * nel, st, sizeof(double) * nel, hipMemcpyDeviceToHost, c->stream));
+      DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+  });
+}
+
+// the vector's numbers, once it is known to live on `level` in the precision of the hierarchy
+template <typename MG>
+static typename MG::real* check_vec(const MG&, const ddamg_hip_vec* v, int level) {
+  DDAMG_REQUIRE(v && v->level == level, "vector lives on the wrong level");
+  DDAMG_REQUIRE(v->precision == 8 * (int)sizeof(typename MG::real), "vector precision does not match the V-cycle precision");
+  return vec_data<typename MG::real>(v);
+}
+
+// whole-vector copy between a vector of the boundary and one that a Krylov solver owns
+static void copy_bytes(ddamg_hip_ctx* c, void* dst, const void* src, const ddamg_hip_vec* shape) {
+  DDAMG_HIP_CHECK(hipMemcpyAsync(dst, src, shape->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
+}
+
+// ---- many right-hand sides on a coarse level: the kernels of the batched setup through the boundary (tests, measurements) ----
+namespace {
+// columns next to each other in one device buffer, as the bootstrap holds them
+struct Columns {
+  DeviceBuffer<float> p; size_t cs = 0;
+  Columns(size_t cs_, int ncols) : cs(cs_) { p.alloc(cs * ncols); }
+};
+// the level the columns a[k], b[k] live on, once every one of them is known to be an fp32 vector of that coarse level
+int many_level(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* a, const ddamg_hip_vec* const* b) {
+  DDAMG_REQUIRE(a && b, "null context or null vector array");
+  DDAMG_REQUIRE(c->mg32, "the many-right-hand-side entry points need the fp32 hierarchy (mixed_precision >= 1)");
+  DDAMG_REQUIRE(ncols >= 2 && ncols <= 32, "2 <= ncols <= 32");
+  for (int k = 0; k < ncols; k++) DDAMG_REQUIRE(a[k] && b[k], "null vector among the columns");
+  const int lvl = a[0]->level;
+  DDAMG_REQUIRE(lvl >= 1 && lvl < c->par.num_levels, "coarse-level vectors expected");
+  for (int k = 0; k < ncols; k++) { check_vec(*c->mg32, a[k], lvl); check_vec(*c->mg32, b[k], lvl); }
+  return lvl;
+}
+void pack(ddamg_hip_ctx* c, Columns& C, const ddamg_hip_vec* const* v, int ncols) {
+  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(C.p + (size_t)k * C.cs, v[k]->data.get(), v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
+}
+void unpack(ddamg_hip_ctx* c, ddamg_hip_vec* const* v, const Columns& C, int ncols) {
+  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(v[k]->data.get(), C.p + (size_t)k * C.cs, v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+// the body of a *_many entry point: the columns of `in` (and, where the call starts from them, of `out`) packed, call(mg, level, O, I)
+// on the packed columns, O back into `out` where it returned true, the many-vector workspace released, `not_covered` thrown where not
+template <typename Call>
+void many_call(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* out, const ddamg_hip_vec* const* in, bool out_is_input, const char* not_covered, Call call) {
+  const int lvl = many_level(c, ncols, out, in);
+  const size_t cs = in[0]->data.bytes() / sizeof(float);
+  Columns I(cs, ncols), O(cs, ncols);     // freed on every path out of here
+  pack(c, I, in, ncols);
+  if (out_is_input) pack(c, O, out, ncols);
+  const bool ok = call(*c->mg32, lvl, O, I);
+  if (ok) unpack(c, out, O, ncols);
+  c->mg32->release_many_workspace();      // the batches are setup workspace: not kept next to the production solves
+  DDAMG_REQUIRE(ok, not_covered);
+}
+}  // namespace
+
 extern "C" {
 
 static int setup_impl(ddamg_hip_ctx* c, int setup_iterations, int* coarse_iterations, const double* setup_m0);
@@ -256,8 +311,7 @@ int ddamg_hip_setup_at_mass(ddamg_hip_ctx* c, int setup_iterations, double setup
 // the iterative setup, then the solver mass again; ONE lifetime of the setup workspace around all of it
 static int setup_impl(ddamg_hip_ctx* c, int setup_iterations, int* coarse_iterations, const double* setup_m0) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   if (c->par.method == 5) {   // no hierarchy: the reference switches the interpolation off (src/init.c:976-979)
     if (coarse_iterations) *coarse_iterations = 0;
     c->setup_done = true;
@@ -271,249 +325,225 @@ static int setup_impl(ddamg_hip_ctx* c, int setup_iterations, int* coarse_iterat
   const int iters = setup_iterations < 0 ? c->par.setup_iter[0] : setup_iterations;
   const double solver_m0 = c->par.m0;
   const bool other_mass = setup_m0 != nullptr && *setup_m0 != solver_m0 && iters > 0;
-  if (c->mg32) { c->mg32->coarse_iter_count = 0; c->mg32->initial_setup(); } else { c->mg64->coarse_iter_count = 0; c->mg64->initial_setup(); }
-  c->setup_done = true;       // the hierarchy exists: the mass shift below reaches every level
-  if (other_mass && ddamg_hip_shift_mass(c, *setup_m0)) throw std::runtime_error(g_ddamg_last_error);
-  if (c->mg32) c->mg32->iterative_setup(iters); else c->mg64->iterative_setup(iters);
-  if (other_mass && ddamg_hip_shift_mass(c, solver_m0)) throw std::runtime_error(g_ddamg_last_error);
-  if (coarse_iterations) *coarse_iterations = c->mg32 ? c->mg32->coarse_iter_count : c->mg64->coarse_iter_count;
-  const double t_r0 = wall();
-  if (c->mg32) c->mg32->release_setup_workspace(); else c->mg64->release_setup_workspace();
-  const double t_rel = wall() - t_r0;
-  auto report = [&](const std::vector<std::pair<std::string, double>>& t) {
-    if (t.empty()) return;      // DDAMG_SETUP_TIMING not set
+  with_mg(c, [&](auto& mg) {
+    mg.coarse_iter_count = 0;
+    mg.initial_setup();
+    c->setup_done = true;       // the hierarchy exists: the mass shift below reaches every level
+    if (other_mass) shift_mass_or_throw(c, *setup_m0);
+    try {
+      mg.iterative_setup(iters);
+    } catch (...) {
+      // no exit at the setup mass, and no hierarchy that stopped half-way through an iteration behind setup_done
+      if (other_mass) (void)ddamg_hip_shift_mass(c, solver_m0);
+      c->setup_done = false;
+      throw;
+    }
+    if (other_mass) shift_mass_or_throw(c, solver_m0);
+    if (coarse_iterations) *coarse_iterations = mg.coarse_iter_count;
+    const double t_r0 = wall();
+    mg.release_setup_workspace();
+    const double t_rel = wall() - t_r0;
+    if (mg.setup_times.empty()) return;      // DDAMG_SETUP_TIMING not set
     fprintf(stderr, "[ddamg setup] %-28s %8.3f s\n", "hierarchy: tables, buffers", t_hier);
-    for (auto& e : t) fprintf(stderr, "[ddamg setup] %-28s %8.3f s\n", e.first.c_str(), e.second);
+    for (auto& e : mg.setup_times) fprintf(stderr, "[ddamg setup] %-28s %8.3f s\n", e.first.c_str(), e.second);
     fprintf(stderr, "[ddamg setup] %-28s %8.3f s\n", "workspace released", t_rel);
-  };
-  if (c->mg32) report(c->mg32->setup_times); else report(c->mg64->setup_times);
+  });
   DDAMG_API_END
 }
 
 int ddamg_hip_setup_update(ddamg_hip_ctx* c, int iterations, int* coarse_iterations) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (c->mg32) { c->mg32->coarse_iter_count = 0; c->mg32->iterative_setup(iterations); if (coarse_iterations) *coarse_iterations = c->mg32->coarse_iter_count; }
-  else { c->mg64->coarse_iter_count = 0; c->mg64->iterative_setup(iterations); if (coarse_iterations) *coarse_iterations = c->mg64->coarse_iter_count; }
-  if (c->mg32) c->mg32->release_setup_workspace(); else c->mg64->release_setup_workspace();
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
+  with_mg(c, [&](auto& mg) {
+    mg.coarse_iter_count = 0;
+    mg.iterative_setup(iterations);
+    if (coarse_iterations) *coarse_iterations = mg.coarse_iter_count;
+    mg.release_setup_workspace();
+  });
   DDAMG_API_END
 }
 
 int ddamg_hip_set_test_vectors(ddamg_hip_ctx* c, const double* tv_lex, int orthonormalised) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && tv_lex, "null argument");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(tv_lex, "null argument");
   ensure_mg(c);
-  if (c->mg32) { if (orthonormalised) c->mg32->import_interpolation(tv_lex); else c->mg32->import_test_vectors(tv_lex); }
-  else { if (orthonormalised) c->mg64->import_interpolation(tv_lex); else c->mg64->import_test_vectors(tv_lex); }
-  if (c->mg32) c->mg32->release_setup_workspace(); else c->mg64->release_setup_workspace();
+  with_mg(c, [&](auto& mg) {
+    if (orthonormalised) mg.import_interpolation(tv_lex); else mg.import_test_vectors(tv_lex);
+    mg.release_setup_workspace();
+  });
   c->setup_done = true;
   DDAMG_API_END
 }
 
 int ddamg_hip_get_interpolation(ddamg_hip_ctx* c, double* P_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done && P_lex, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const size_t V = c->levels[0]->geom.V, nel = 24 * V;
-  const int nvec = c->par.num_vect[0];
-  double* st = c->stage(sizeof(double) * nel);
-  for (int k = 0; k < nvec; k++) {
-    // P is stored aggregate by aggregate (transfer.hip): column k into a vector in lattice order first
-    if (c->mg32) { float* v = c->mg32->level(0).buf[0]; c->mg32->level(0).fip.get_column(k, v, c->stream); vec_to_lex<float>(st, v, c->levels[0]->d_lex_of_site, (int)V, 12, c->stream); }
-    else { double* v = c->mg64->level(0).buf[0]; c->mg64->level(0).fip.get_column(k, v, c->stream); vec_to_lex<double>(st, v, c->levels[0]->d_lex_of_site, (int)V, 12, c->stream); }
-    DDAMG_HIP_CHECK(hipMemcpyAsync(P_lex + (size_t)k * nel, st, sizeof(double) * nel, hipMemcpyDeviceToHost, c->stream));
-    DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  }
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done && P_lex, "setup has not been run");
+  // P is stored aggregate by aggregate (transfer.hip): column k into a vector in lattice order first
+  download_columns(c, P_lex, [&](auto& mg, int k) {
+    real_of<decltype(mg)>* v = mg.level(0).buf[0];
+    mg.level(0).fip.get_column(k, v, c->stream);
+    return v;
+  });
   DDAMG_API_END
 }
 
 int ddamg_hip_get_test_vectors(ddamg_hip_ctx* c, double* tv_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done && tv_lex, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const size_t V = c->levels[0]->geom.V, nel = 24 * V;
-  const int nvec = c->par.num_vect[0];
-  double* st = c->stage(sizeof(double) * nel);
-  for (int k = 0; k < nvec; k++) {
-    if (c->mg32) vec_to_lex<float>(st, c->mg32->level(0).fip.test_vector(k), c->levels[0]->d_lex_of_site, (int)V, 12, c->stream);
-    else vec_to_lex<double>(st, c->mg64->level(0).fip.test_vector(k), c->levels[0]->d_lex_of_site, (int)V, 12, c->stream);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(tv_lex + (size_t)k * nel, st, sizeof(double) * nel, hipMemcpyDeviceToHost, c->stream));
-    DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  }
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done && tv_lex, "setup has not been run");
+  download_columns(c, tv_lex, [](auto& mg, int k) { return mg.level(0).fip.test_vector(k); });
   DDAMG_API_END
 }
 
 int ddamg_hip_get_coarse_operator_level(ddamg_hip_ctx* c, int level, double* D_lex, double* clover_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
   DDAMG_REQUIRE(level >= 1 && level < c->par.num_levels, "coarse operator: 1 <= level < num_levels");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (c->mg32) c->mg32->level(level).cop.export_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream);
-  else c->mg64->level(level).cop.export_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream);
+  with_mg(c, [&](auto& mg) { mg.level(level).cop.export_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream); });
   DDAMG_API_END
 }
 int ddamg_hip_get_coarse_operator(ddamg_hip_ctx* c, double* D_lex, double* clover_lex) { return ddamg_hip_get_coarse_operator_level(c, 1, D_lex, clover_lex); }
 
 int ddamg_hip_set_coarse_operator_level(ddamg_hip_ctx* c, int level, const double* D_lex, const double* clover_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && D_lex && clover_lex, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(D_lex && clover_lex, "null argument");
   DDAMG_REQUIRE(level >= 1 && level < c->par.num_levels, "coarse operator: 1 <= level < num_levels");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   ensure_mg(c);
-  if (c->mg32) c->mg32->level(level).cop.import_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream);
-  else c->mg64->level(level).cop.import_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream);
-  if (level == c->par.num_levels - 1) { if (c->mg32) c->mg32->regather_coarsest_operator(); else c->mg64->regather_coarsest_operator(); }
+  with_mg(c, [&](auto& mg) {
+    mg.level(level).cop.import_reference(c->levels[level]->geom, D_lex, clover_lex, c->stream);
+    if (level == c->par.num_levels - 1) mg.regather_coarsest_operator();
+  });
   DDAMG_API_END
 }
 int ddamg_hip_set_coarse_operator(ddamg_hip_ctx* c, const double* D_lex, const double* clover_lex) { return ddamg_hip_set_coarse_operator_level(c, 1, D_lex, clover_lex); }
 
 int ddamg_hip_set_interpolation_level(ddamg_hip_ctx* c, int level, const double* P_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && P_lex, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(P_lex, "null argument");
   DDAMG_REQUIRE(level >= 0 && level + 1 < c->par.num_levels, "interpolation vectors: 0 <= level < num_levels - 1");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   ensure_mg(c);
-  if (c->mg32) { c->mg32->import_interpolation_level(level, P_lex); c->mg32->release_setup_workspace(); }
-  else { c->mg64->import_interpolation_level(level, P_lex); c->mg64->release_setup_workspace(); }
+  with_mg(c, [&](auto& mg) { mg.import_interpolation_level(level, P_lex); mg.release_setup_workspace(); });
   c->setup_done = true;
   DDAMG_API_END
 }
 
-#define MG_CALL(expr32, expr64) do { if (c->mg32) { auto& mg = *c->mg32; typedef float T; (void)sizeof(T); expr32; } else { auto& mg = *c->mg64; typedef double T; (void)sizeof(T); expr64; } } while (0)
-
-static void check_vec(ddamg_hip_ctx* c, const ddamg_hip_vec* v, int level) {
-  DDAMG_REQUIRE(v && v->level == level, "vector lives on the wrong level");
-  DDAMG_REQUIRE(v->precision == (c->mg32 ? 32 : 64), "vector precision does not match the V-cycle precision");
-}
-
-// helpers of the many-right-hand-side entry points below
-namespace {
-// columns next to each other in one device buffer, as the bootstrap holds them
-struct Columns {
-  DeviceBuffer<float> p; size_t cs = 0;
-  Columns(size_t cs_, int ncols) : cs(cs_) { p.alloc(cs * ncols); }
-};
-int many_level(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* a, const ddamg_hip_vec* const* b) {
-  DDAMG_REQUIRE(c && c->mg32 && a && b, "the many-right-hand-side entry points need the fp32 hierarchy (mixed_precision >= 1)");
-  DDAMG_REQUIRE(ncols >= 2 && ncols <= 32, "2 <= ncols <= 32");
-  for (int k = 0; k < ncols; k++) DDAMG_REQUIRE(a[k] && b[k], "null vector among the columns");
-  const int lvl = a[0]->level;
-  DDAMG_REQUIRE(lvl >= 1 && lvl < c->par.num_levels, "coarse-level vectors expected");
-  for (int k = 0; k < ncols; k++) {
-    check_vec(c, a[k], lvl); check_vec(c, b[k], lvl);
-    DDAMG_REQUIRE(a[k]->precision == 32 && b[k]->precision == 32, "fp32 vectors expected");
-  }
-  return lvl;
-}
-void pack(ddamg_hip_ctx* c, Columns& C, const ddamg_hip_vec* const* v, int ncols) {
-  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(C.p + (size_t)k * C.cs, v[k]->data.get(), v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-}
-void unpack(ddamg_hip_ctx* c, ddamg_hip_vec* const* v, const Columns& C, int ncols) {
-  for (int k = 0; k < ncols; k++) DDAMG_HIP_CHECK(hipMemcpyAsync(v[k]->data.get(), C.p + (size_t)k * C.cs, v[k]->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-}  // namespace
-
 int ddamg_hip_smoother(ddamg_hip_ctx* c, ddamg_hip_vec* phi, const ddamg_hip_vec* eta, int cycles, int initial_guess_zero) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null context");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   ensure_mg(c);
   DDAMG_REQUIRE(phi && phi->level >= 0 && phi->level + 1 < c->par.num_levels, "smoother: the coarsest level has none");
   const int lvl = phi->level;
-  check_vec(c, phi, lvl); check_vec(c, eta, lvl);
-  if (c->mg32) c->mg32->smoother(lvl, (float*)phi->data.get(), nullptr, (const float*)eta->data.get(), cycles, initial_guess_zero ? NO_RES : RES);
-  else c->mg64->smoother(lvl, (double*)phi->data.get(), nullptr, (const double*)eta->data.get(), cycles, initial_guess_zero ? NO_RES : RES);
+  with_mg(c, [&](auto& mg) { mg.smoother(lvl, check_vec(mg, phi, lvl), nullptr, check_vec(mg, eta, lvl), cycles, initial_guess_zero ? NO_RES : RES); });
   DDAMG_API_END
 }
 
 int ddamg_hip_restrict(ddamg_hip_ctx* c, ddamg_hip_vec* coarse, const ddamg_hip_vec* fine) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
   DDAMG_REQUIRE(fine && fine->level >= 0 && fine->level + 1 < c->par.num_levels, "restrict: no coarser level below this vector");
-  check_vec(c, coarse, fine->level + 1); check_vec(c, fine, fine->level);
-  if (c->mg32) c->mg32->restrict_to(fine->level, (float*)coarse->data.get(), (const float*)fine->data.get());
-  else c->mg64->restrict_to(fine->level, (double*)coarse->data.get(), (const double*)fine->data.get());
+  with_mg(c, [&](auto& mg) { mg.restrict_to(fine->level, check_vec(mg, coarse, fine->level + 1), check_vec(mg, fine, fine->level)); });
   DDAMG_API_END
 }
 
 int ddamg_hip_interpolate(ddamg_hip_ctx* c, ddamg_hip_vec* fine, const ddamg_hip_vec* coarse, int add) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
   DDAMG_REQUIRE(fine && fine->level >= 0 && fine->level + 1 < c->par.num_levels, "interpolate: no coarser level below this vector");
-  check_vec(c, coarse, fine->level + 1); check_vec(c, fine, fine->level);
-  if (c->mg32) c->mg32->interpolate(fine->level, (float*)fine->data.get(), (const float*)coarse->data.get(), add != 0);
-  else c->mg64->interpolate(fine->level, (double*)fine->data.get(), (const double*)coarse->data.get(), add != 0);
+  with_mg(c, [&](auto& mg) { mg.interpolate(fine->level, check_vec(mg, fine, fine->level), check_vec(mg, coarse, fine->level + 1), add != 0); });
   DDAMG_API_END
 }
 
 int ddamg_hip_coarse_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  DDAMG_REQUIRE(out && in && out->level >= 1 && out->level == in->level, "coarse vectors of one level expected");
-  check_vec(c, out, out->level); check_vec(c, in, in->level);
-  if (c->mg32) c->mg32->apply_op(out->level, (float*)out->data.get(), (const float*)in->data.get());
-  else c->mg64->apply_op(out->level, (double*)out->data.get(), (const double*)in->data.get());
+  enter(c);
+  with_mg(c, [&](auto& mg) {
+    DDAMG_REQUIRE(out && in && out->level >= 1 && out->level == in->level, "coarse vectors of one level expected");
+    mg.apply_op(out->level, check_vec(mg, out, out->level), check_vec(mg, in, in->level));
+  }, "no coarse operator");
   DDAMG_API_END
 }
 
 int ddamg_hip_coarse_hop(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, double sign, int accumulate) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   const int lc = c->par.num_levels - 1;
-  check_vec(c, out, lc); check_vec(c, in, lc);
-  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place hopping term is not supported");
-  if (c->mg32) c->mg32->coarsest_hop_parity((float*)out->data.get(), (const float*)in->data.get(), parity, sign, accumulate != 0);
-  else c->mg64->coarsest_hop_parity((double*)out->data.get(), (const double*)in->data.get(), parity, sign, accumulate != 0);
+  with_mg(c, [&](auto& mg) {
+    auto* o = check_vec(mg, out, lc); auto* i = check_vec(mg, in, lc);
+    DDAMG_REQUIRE(o != i, "in-place hopping term is not supported");
+    mg.coarsest_hop_parity(o, i, parity, sign, accumulate != 0);
+  }, "no coarse operator");
   DDAMG_API_END
 }
 
 int ddamg_hip_coarse_self_mul(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in, int parity, int inverse) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   const int lc = c->par.num_levels - 1;
-  check_vec(c, out, lc); check_vec(c, in, lc);
-  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place self coupling is not supported");
-  if (c->mg32) c->mg32->coarsest_self_mul_parity((float*)out->data.get(), (const float*)in->data.get(), parity, inverse != 0);
-  else c->mg64->coarsest_self_mul_parity((double*)out->data.get(), (const double*)in->data.get(), parity, inverse != 0);
+  with_mg(c, [&](auto& mg) {
+    auto* o = check_vec(mg, out, lc); auto* i = check_vec(mg, in, lc);
+    DDAMG_REQUIRE(o != i, "in-place self coupling is not supported");
+    mg.coarsest_self_mul_parity(o, i, parity, inverse != 0);
+  }, "no coarse operator");
   DDAMG_API_END
 }
 
 int ddamg_hip_coarse_solve(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, int* iterations) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && (c->mg32 || c->mg64), "no coarse operator");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
+  enter(c);
   const int lc = c->par.num_levels - 1;   // the coarsest level
-  check_vec(c, x, lc); check_vec(c, b, lc);
-  int it;
-  if (c->mg32) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->coarse_b(), b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-    it = c->mg32->coarse_solve();
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg32->coarse_x(), x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->coarse_b(), b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-    it = c->mg64->coarse_solve();
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg64->coarse_x(), x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (iterations) *iterations = it;
+  with_mg(c, [&](auto& mg) {
+    check_vec(mg, x, lc);
+    copy_bytes(c, mg.coarse_b(), check_vec(mg, b, lc), b);
+    const int it = mg.coarse_solve();
+    copy_bytes(c, x->data.get(), mg.coarse_x(), x);
+    if (iterations) *iterations = it;
+  }, "no coarse operator");
   DDAMG_API_END
 }
 
+int ddamg_hip_vcycle(ddamg_hip_ctx* c, ddamg_hip_vec* phi, const ddamg_hip_vec* eta) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done, "setup has not been run");
+  DDAMG_REQUIRE(phi && phi->level >= 0 && phi->level + 1 < c->par.num_levels, "vcycle: the coarsest level has none");
+  const int lvl = phi->level;
+  with_mg(c, [&](auto& mg) { mg.vcycle(lvl, check_vec(mg, phi, lvl), nullptr, check_vec(mg, eta, lvl), NO_RES); });
+  DDAMG_API_END
+}
+
+int ddamg_hip_kcycle(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, int* iterations) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(c->setup_done && x && b, "setup has not been run");
+  const int lvl = x->level;
+  DDAMG_REQUIRE(lvl >= 1 && lvl + 1 < c->par.num_levels, "kcycle: an intermediate level");
+  with_mg(c, [&](auto& mg) {
+    check_vec(mg, x, lvl);
+    copy_bytes(c, mg.level(lvl).gm.b, check_vec(mg, b, lvl), b);
+    const int it = mg.kcycle_solve(lvl);
+    copy_bytes(c, x->data.get(), mg.level(lvl).gm.x, x);
+    if (iterations) *iterations = it;
+  });
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+// kept apart from many_call: a column comes back only where its solve converged (iterations[k] >= 0), and the level is the coarsest
 int ddamg_hip_coarse_solve_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* x, const ddamg_hip_vec* const* b, int* iterations) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->mg32 && x && b && iterations, "coarse_solve_many needs the fp32 hierarchy (mixed_precision >= 1)");
+  enter(c);
+  DDAMG_REQUIRE(c->mg32 && x && b && iterations, "coarse_solve_many needs the fp32 hierarchy (mixed_precision >= 1)");
   DDAMG_REQUIRE(ncols >= 2 && ncols <= 32, "2 <= ncols <= 32");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   const int lc = c->par.num_levels - 1;
-  for (int k = 0; k < ncols; k++) { check_vec(c, x[k], lc); check_vec(c, b[k], lc); DDAMG_REQUIRE(x[k]->precision == 32 && b[k]->precision == 32, "fp32 vectors expected"); }
-  // columns next to each other in one buffer, as the bootstrap holds them
+  for (int k = 0; k < ncols; k++) { check_vec(*c->mg32, x[k], lc); check_vec(*c->mg32, b[k], lc); }
   const size_t cs = b[0]->data.bytes() / sizeof(float);
   Columns B(cs, ncols), X(cs, ncols);     // freed on every path out of here
   pack(c, B, b, ncols);
@@ -527,96 +557,40 @@ int ddamg_hip_coarse_solve_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* cons
   DDAMG_API_END
 }
 
-int ddamg_hip_vcycle(ddamg_hip_ctx* c, ddamg_hip_vec* phi, const ddamg_hip_vec* eta) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  DDAMG_REQUIRE(phi && phi->level >= 0 && phi->level + 1 < c->par.num_levels, "vcycle: the coarsest level has none");
-  const int lvl = phi->level;
-  check_vec(c, phi, lvl); check_vec(c, eta, lvl);
-  if (c->mg32) c->mg32->vcycle(lvl, (float*)phi->data.get(), nullptr, (const float*)eta->data.get(), NO_RES);
-  else c->mg64->vcycle(lvl, (double*)phi->data.get(), nullptr, (const double*)eta->data.get(), NO_RES);
-  DDAMG_API_END
-}
-
-int ddamg_hip_kcycle(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, int* iterations) {
-  DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && c->setup_done && x && b, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int lvl = x->level;
-  DDAMG_REQUIRE(lvl >= 1 && lvl + 1 < c->par.num_levels, "kcycle: an intermediate level");
-  check_vec(c, x, lvl); check_vec(c, b, lvl);
-  int it;
-  if (c->mg32) {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg32->level(lvl).gm.b, b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-    it = c->mg32->kcycle_solve(lvl);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg32->level(lvl).gm.x, x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    DDAMG_HIP_CHECK(hipMemcpyAsync(c->mg64->level(lvl).gm.b, b->data.get(), b->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-    it = c->mg64->kcycle_solve(lvl);
-    DDAMG_HIP_CHECK(hipMemcpyAsync(x->data.get(), c->mg64->level(lvl).gm.x, x->data.bytes(), hipMemcpyDeviceToDevice, c->stream));
-  }
-  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (iterations) *iterations = it;
-  DDAMG_API_END
-}
-
-// ---- many right-hand sides on a coarse level: the kernels of the batched setup through the boundary (tests, measurements) ----
 int ddamg_hip_coarse_apply_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* out, const ddamg_hip_vec* const* in) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && out && in, "null context or null vector array");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int lvl = many_level(c, ncols, out, in);
-  Columns I(in[0]->data.bytes() / sizeof(float), ncols), O(in[0]->data.bytes() / sizeof(float), ncols);
-  pack(c, I, in, ncols);
-  const bool ok = lvl == c->par.num_levels - 1 ? c->mg32->coarsest_apply_many(O.p, O.cs, I.p, I.cs, ncols) : c->mg32->multi_apply_many(lvl, O.p, O.cs, I.p, I.cs, ncols);
-  if (ok) unpack(c, out, O, ncols);
-  c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "coarse_apply_many: shape not covered (fp32, single process; the coarsest level, or an intermediate level of three or four levels)");
+  enter(c);
+  many_call(c, ncols, out, in, false, "coarse_apply_many: shape not covered (fp32, single process; the coarsest level, or an intermediate level of three or four levels)",
+            [&](Multigrid<float>& mg, int lvl, Columns& O, Columns& I) {
+              return lvl == c->par.num_levels - 1 ? mg.coarsest_apply_many(O.p, O.cs, I.p, I.cs, ncols) : mg.multi_apply_many(lvl, O.p, O.cs, I.p, I.cs, ncols);
+            });
   DDAMG_API_END
 }
 
 int ddamg_hip_smoother_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta, int cycles, int initial_guess_zero) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && phi && eta, "null context or null vector array");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int lvl = many_level(c, ncols, phi, eta);
-  Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
-  pack(c, E, eta, ncols); pack(c, P, phi, ncols);
-  const bool ok = c->mg32->multi_smooth_many(lvl, P.p, P.cs, E.p, E.cs, ncols, cycles, initial_guess_zero ? NO_RES : RES);
-  if (ok) unpack(c, phi, P, ncols);
-  c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "smoother_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)");
+  enter(c);
+  many_call(c, ncols, phi, eta, true, "smoother_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)",
+            [&](Multigrid<float>& mg, int lvl, Columns& P, Columns& E) { return mg.multi_smooth_many(lvl, P.p, P.cs, E.p, E.cs, ncols, cycles, initial_guess_zero ? NO_RES : RES); });
   DDAMG_API_END
 }
 
 int ddamg_hip_vcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* phi, const ddamg_hip_vec* const* eta) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && phi && eta, "null context or null vector array");
+  enter(c);
   DDAMG_REQUIRE(c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int lvl = many_level(c, ncols, phi, eta);
-  Columns E(eta[0]->data.bytes() / sizeof(float), ncols), P(eta[0]->data.bytes() / sizeof(float), ncols);
-  pack(c, E, eta, ncols);
-  const bool ok = c->mg32->multi_vcycle_many(lvl, P.p, P.cs, E.p, E.cs, ncols);
-  if (ok) unpack(c, phi, P, ncols);
-  c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "vcycle_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)");
+  many_call(c, ncols, phi, eta, false, "vcycle_many: shape not covered (an intermediate level of three or four levels, red-black Schwarz, fp32, single process)",
+            [&](Multigrid<float>& mg, int lvl, Columns& P, Columns& E) { return mg.multi_vcycle_many(lvl, P.p, P.cs, E.p, E.cs, ncols); });
   DDAMG_API_END
 }
 
 int ddamg_hip_kcycle_many(ddamg_hip_ctx* c, int ncols, ddamg_hip_vec* const* x, const ddamg_hip_vec* const* b, int* iterations) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && x && b && iterations, "null context, null vector array or null iteration counts");
+  enter(c);
+  DDAMG_REQUIRE(iterations, "null context, null vector array or null iteration counts");
   DDAMG_REQUIRE(c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int lvl = many_level(c, ncols, x, b);
-  Columns B(b[0]->data.bytes() / sizeof(float), ncols), X(b[0]->data.bytes() / sizeof(float), ncols);
-  pack(c, B, b, ncols);
-  const bool ok = c->mg32->multi_kcycle_many(lvl, X.p, X.cs, B.p, B.cs, ncols, iterations);
-  if (ok) unpack(c, x, X, ncols);
-  c->mg32->release_many_workspace();
-  DDAMG_REQUIRE(ok, "kcycle_many: shape not covered (an intermediate level of three or four levels with the K-cycle, red-black Schwarz, fp32, single process)");
+  many_call(c, ncols, x, b, false, "kcycle_many: shape not covered (an intermediate level of three or four levels with the K-cycle, red-black Schwarz, fp32, single process)",
+            [&](Multigrid<float>& mg, int lvl, Columns& X, Columns& B) { return mg.multi_kcycle_many(lvl, X.p, X.cs, B.p, B.cs, ncols, iterations); });
   DDAMG_API_END
 }
 
@@ -628,11 +602,9 @@ template <typename LoadB, typename StoreX>
 static void solve_core(ddamg_hip_ctx* c, double tol, LoadB load_b, StoreX store_x, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_REQUIRE(c->have_operator, "no operator set");
   DDAMG_REQUIRE(c->par.method <= 0 || c->par.method == 5 || c->setup_done, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   int it; double rr = 0;
   if (c->bicg_ready) { c->bicg32.total_iter = 0; c->bicg64.total_iter = 0; }
-  if (c->mg32) c->mg32->coarse_iter_count = 0;
-  if (c->mg64) c->mg64->coarse_iter_count = 0;
+  reset_coarse_iterations(c);
   if (c->par.method == -1) {
     ensure_outer(c);
     load_b(c->outer.b);
@@ -656,60 +628,77 @@ static void solve_core(ddamg_hip_ctx* c, double tol, LoadB load_b, StoreX store_
   }
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   c->last_iter = it;
-  c->last_coarse_iter = c->mg32 ? c->mg32->coarse_iter_count : (c->mg64 ? c->mg64->coarse_iter_count : 0);
-  if (c->par.method == 5) c->last_coarse_iter = c->bicg32.total_iter + c->bicg64.total_iter;   // inner BiCGstab iterations
+  c->last_coarse_iter = c->par.method == 5 ? c->bicg32.total_iter + c->bicg64.total_iter   // inner BiCGstab iterations
+                                           : coarse_iterations_of(c);
   c->last_relres = rr;
   if (iterations) *iterations = it;
   if (coarse_iterations) *coarse_iterations = c->last_coarse_iter;
   if (relres) *relres = rr;
 }
 
+// the multigrid preconditioner on one vector, with the callbacks of solve_core
+template <typename Load, typename Store>
+static void precondition_core(ddamg_hip_ctx* c, Load load, Store store) {
+  ensure_outer(c);
+  load(c->outer.b);
+  reset_coarse_iterations(c);
+  c->outer.prec(c->outer.x, nullptr, c->outer.b, NO_RES);
+  store(c->outer.x);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->last_coarse_iter = coarse_iterations_of(c);
+}
+
+// load / store callbacks for a fine vector `lex` in lattice order: in device memory, or (st given) in host memory through that staging buffer
+static auto load_lex(ddamg_hip_ctx* c, const double* lex, double* st = nullptr) {
+  return [=](double* dst) {
+    const int V = c->levels[0]->geom.V;
+    if (st) DDAMG_HIP_CHECK(hipMemcpyAsync(st, lex, sizeof(double) * 24 * V, hipMemcpyHostToDevice, c->stream));
+    vec_from_lex<double>(dst, st ? st : lex, c->levels[0]->d_lex_of_site, V, 12, c->stream);
+  };
+}
+static auto store_lex(ddamg_hip_ctx* c, double* lex, double* st = nullptr) {
+  return [=](const double* src) {
+    const int V = c->levels[0]->geom.V;
+    vec_to_lex<double>(st ? st : lex, src, c->levels[0]->d_lex_of_site, V, 12, c->stream);
+    if (st) DDAMG_HIP_CHECK(hipMemcpyAsync(lex, st, sizeof(double) * 24 * V, hipMemcpyDeviceToHost, c->stream));
+  };
+}
+// the two arrays of a *_device entry point: in the memory of the context's device, and apart
+static void require_device_pair(ddamg_hip_ctx* c, double* out, const double* in, const char* name) {
+  const size_t nb = sizeof(double) * 24 * c->levels[0]->geom.V;
+  ddamg_require_device_array(c, out, nb, name);
+  ddamg_require_device_array(c, in, nb, name);
+  ddamg_require_disjoint(out, in, nb, name);
+}
+
 extern "C" {
 
 int ddamg_hip_solve(ddamg_hip_ctx* c, double* x_lex, const double* b_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && x_lex && b_lex, "null argument");
-  const int V = c->levels[0]->geom.V;
-  const size_t nb = sizeof(double) * 24 * V;
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  double* st = c->stage(nb);
-  solve_core(c, tol,
-             [&](double* dst) {
-               DDAMG_HIP_CHECK(hipMemcpyAsync(st, b_lex, nb, hipMemcpyHostToDevice, c->stream));
-               vec_from_lex<double>(dst, st, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-             },
-             [&](const double* src) {
-               vec_to_lex<double>(st, src, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-               DDAMG_HIP_CHECK(hipMemcpyAsync(x_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
-             },
-             iterations, coarse_iterations, relres);
+  enter(c);
+  DDAMG_REQUIRE(x_lex && b_lex, "null argument");
+  double* st = c->stage(sizeof(double) * 24 * c->levels[0]->geom.V);
+  solve_core(c, tol, load_lex(c, b_lex, st), store_lex(c, x_lex, st), iterations, coarse_iterations, relres);
   DDAMG_API_END
 }
 
 int ddamg_hip_solve_device(ddamg_hip_ctx* c, double* x_dev_lex, const double* b_dev_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null argument");
-  const int V = c->levels[0]->geom.V;
-  const size_t nb = sizeof(double) * 24 * V;
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  ddamg_require_device_array(c, x_dev_lex, nb, "ddamg_hip_solve_device");
-  ddamg_require_device_array(c, b_dev_lex, nb, "ddamg_hip_solve_device");
-  ddamg_require_disjoint(x_dev_lex, b_dev_lex, nb, "ddamg_hip_solve_device");
-  solve_core(c, tol,
-             [&](double* dst) { vec_from_lex<double>(dst, b_dev_lex, c->levels[0]->d_lex_of_site, V, 12, c->stream); },
-             [&](const double* src) { vec_to_lex<double>(x_dev_lex, src, c->levels[0]->d_lex_of_site, V, 12, c->stream); },
-             iterations, coarse_iterations, relres);
+  enter(c);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_device");
+  solve_core(c, tol, load_lex(c, b_dev_lex), store_lex(c, x_dev_lex), iterations, coarse_iterations, relres);
   DDAMG_API_END
 }
 
 int ddamg_hip_solve_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && x && b, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(x && b, "null argument");
   DDAMG_REQUIRE(x->level == 0 && b->level == 0 && x->precision == 64 && b->precision == 64, "solve_vec needs fine-level fp64 vectors");
   const size_t n = (size_t)24 * c->levels[0]->geom.V;
   solve_core(c, tol,
-             [&](double* dst) { vec_copy<double>(dst, (const double*)b->data.get(), whole(n), c->stream); },
-             [&](const double* src) { vec_copy<double>((double*)x->data.get(), src, whole(n), c->stream); },
+             [&](double* dst) { vec_copy<double>(dst, vec_data<double>(b), whole(n), c->stream); },
+             [&](const double* src) { vec_copy<double>(vec_data<double>(x), src, whole(n), c->stream); },
              iterations, coarse_iterations, relres);
   DDAMG_API_END
 }
@@ -719,34 +708,30 @@ static ddamg::ReduceWork& blas_rw(ddamg_hip_ctx* c) {
   if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
   return c->rw_blas;
 }
-static size_t vec_len(const ddamg_hip_vec* v) { return (size_t)v->V * v->ndof * 2; }
 static void same_shape(const ddamg_hip_vec* a, const ddamg_hip_vec* b) {
   DDAMG_REQUIRE(a && b && a->level == b->level && a->precision == b->precision, "vectors differ in level or precision");
 }
 
 int ddamg_hip_vec_copy(ddamg_hip_ctx* c, ddamg_hip_vec* dst, const ddamg_hip_vec* src) {
   DDAMG_API_BEGIN
+  enter(c);
   same_shape(dst, src);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (dst->precision == 32) vec_copy<float>((float*)dst->data.get(), (const float*)src->data.get(), whole(vec_len(dst)), c->stream);
-  else vec_copy<double>((double*)dst->data.get(), (const double*)src->data.get(), whole(vec_len(dst)), c->stream);
+  with_vec(dst, [&](auto* d) { using T = pointee<decltype(d)>; vec_copy<T>(d, vec_data<T>(src), whole(vec_len(dst)), c->stream); });
   DDAMG_API_END
 }
 int ddamg_hip_vec_axpy(ddamg_hip_ctx* c, ddamg_hip_vec* z, const ddamg_hip_vec* x, const ddamg_hip_vec* y, double alpha_re, double alpha_im) {
   DDAMG_API_BEGIN
+  enter(c);
   same_shape(z, x); same_shape(z, y);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  if (z->precision == 32) vec_axpy<float>((float*)z->data.get(), (const float*)x->data.get(), (const float*)y->data.get(), alpha_re, alpha_im, whole(vec_len(z)), c->stream);
-  else vec_axpy<double>((double*)z->data.get(), (const double*)x->data.get(), (const double*)y->data.get(), alpha_re, alpha_im, whole(vec_len(z)), c->stream);
+  with_vec(z, [&](auto* d) { using T = pointee<decltype(d)>; vec_axpy<T>(d, vec_data<T>(x), vec_data<T>(y), alpha_re, alpha_im, whole(vec_len(z)), c->stream); });
   DDAMG_API_END
 }
 int ddamg_hip_vec_dot(ddamg_hip_ctx* c, const ddamg_hip_vec* x, const ddamg_hip_vec* y, double* re, double* im, double* norm_x) {
   DDAMG_API_BEGIN
+  enter(c);
   same_shape(x, y);
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
   ReduceWork& rw = blas_rw(c);
-  if (x->precision == 32) vec_dot_and_norm2<float>((const float*)x->data.get(), (const float*)y->data.get(), whole(vec_len(x)), rw, rw.d_result, c->stream);
-  else vec_dot_and_norm2<double>((const double*)x->data.get(), (const double*)y->data.get(), whole(vec_len(x)), rw, rw.d_result, c->stream);
+  with_vec(x, [&](auto* p) { using T = pointee<decltype(p)>; vec_dot_and_norm2<T>(p, vec_data<T>(y), whole(vec_len(x)), rw, rw.d_result, c->stream); });
   DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (re) *re = rw.h_result[0];
@@ -757,49 +742,27 @@ int ddamg_hip_vec_dot(ddamg_hip_ctx* c, const ddamg_hip_vec* x, const ddamg_hip_
 
 int ddamg_hip_preconditioner(ddamg_hip_ctx* c, double* out_lex, const double* in_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && out_lex && in_lex, "null argument");
+  enter(c);
+  DDAMG_REQUIRE(out_lex && in_lex, "null argument");
   DDAMG_REQUIRE(c->setup_done && c->par.method > 0, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  ensure_outer(c);
-  const int V = c->levels[0]->geom.V;
-  const size_t nb = sizeof(double) * 24 * V;
-  double* st = c->stage(nb);
-  DDAMG_HIP_CHECK(hipMemcpyAsync(st, in_lex, nb, hipMemcpyHostToDevice, c->stream));
-  vec_from_lex<double>(c->outer.b, st, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-  if (c->mg32) c->mg32->coarse_iter_count = 0;
-  if (c->mg64) c->mg64->coarse_iter_count = 0;
-  c->outer.prec(c->outer.x, nullptr, c->outer.b, NO_RES);
-  vec_to_lex<double>(st, c->outer.x, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-  DDAMG_HIP_CHECK(hipMemcpyAsync(out_lex, st, nb, hipMemcpyDeviceToHost, c->stream));
-  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  c->last_coarse_iter = c->mg32 ? c->mg32->coarse_iter_count : c->mg64->coarse_iter_count;
+  double* st = c->stage(sizeof(double) * 24 * c->levels[0]->geom.V);
+  precondition_core(c, load_lex(c, in_lex, st), store_lex(c, out_lex, st));
   DDAMG_API_END
 }
 
 int ddamg_hip_preconditioner_device(ddamg_hip_ctx* c, double* out_dev_lex, const double* in_dev_lex) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c, "null argument");
+  enter(c);
   DDAMG_REQUIRE(c->setup_done && c->par.method > 0, "setup has not been run");
-  DDAMG_HIP_CHECK(hipSetDevice(c->device));
-  const int V = c->levels[0]->geom.V;
-  const size_t nb = sizeof(double) * 24 * V;
-  ddamg_require_device_array(c, out_dev_lex, nb, "ddamg_hip_preconditioner_device");
-  ddamg_require_device_array(c, in_dev_lex, nb, "ddamg_hip_preconditioner_device");
-  ddamg_require_disjoint(out_dev_lex, in_dev_lex, nb, "ddamg_hip_preconditioner_device");
-  ensure_outer(c);
-  vec_from_lex<double>(c->outer.b, in_dev_lex, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-  if (c->mg32) c->mg32->coarse_iter_count = 0;
-  if (c->mg64) c->mg64->coarse_iter_count = 0;
-  c->outer.prec(c->outer.x, nullptr, c->outer.b, NO_RES);
-  vec_to_lex<double>(out_dev_lex, c->outer.x, c->levels[0]->d_lex_of_site, V, 12, c->stream);
-  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
-  c->last_coarse_iter = c->mg32 ? c->mg32->coarse_iter_count : c->mg64->coarse_iter_count;
+  require_device_pair(c, out_dev_lex, in_dev_lex, "ddamg_hip_preconditioner_device");
+  precondition_core(c, load_lex(c, in_dev_lex), store_lex(c, out_dev_lex));
   DDAMG_API_END
 }
 
 int ddamg_hip_residual_history(ddamg_hip_ctx* c, double* history, int max_len, int* len) {
   DDAMG_API_BEGIN
-  DDAMG_REQUIRE(c && len, "null argument");
+  DDAMG_REQUIRE(c, "null context");   // host numbers only: no device is selected
+  DDAMG_REQUIRE(len && (history || max_len <= 0), "null argument");
   const int n = (int)c->last_history.size();
   *len = n;
   for (int i = 0; i < n && i < max_len; i++) history[i] = c->last_history[i];

@@ -291,6 +291,56 @@ def test_refusals(gold4, hip):
     grid.close()
 
 
+def test_null_and_mismatched_vectors_are_refused_and_the_context_still_solves():
+    """a null vector in any slot, a null column, a vector of the wrong level or precision, and a null context next to valid vectors:
+    each an error with a message from the host-side checks, none reaches a kernel, and the solve afterwards is the one before"""
+    q = two_level_4()
+    q.post_smooth_iter[0] = 2; q.block_iter[0] = 4
+    q.restart, q.max_restart, q.tol = 30, 20, 1e-10
+    q.coarse_iter, q.coarse_restart, q.coarse_tol = 100, 5, 5e-2
+    ctx = dd.Context(q)
+    ctx.set_gauge(synth_field([4] * 4, 2), anti_pbc=True)
+    ctx.setup(2)
+    b = np.zeros((256, 12, 2)); b[..., 0] = 1.0
+    x0, it0, cit0, rr0 = ctx.solve(b, 1e-10)
+    assert rr0 < 1e-10
+    lib, c = ctx._lib, ctx._h
+    v = {(l, p): ctx.vector(l, p) for l in (0, 1) for p in (32, 64)}
+    f32, c32, f64 = v[0, 32]._h, v[1, 32]._h, v[0, 64]._h   # fine and coarse in the V-cycle's precision, fine in the outer solver's
+
+    def refused(status):
+        assert status != 0 and lib.ddamg_hip_last_error()
+
+    # (entry point, valid vector arguments, the arguments after them)
+    calls = [(lib.ddamg_hip_vec_copy, [f32, f32], []), (lib.ddamg_hip_vec_axpy, [f32, f32, f32], [1.0, 0.0]),
+             (lib.ddamg_hip_vec_dot, [f32, f32], [None, None, None]), (lib.ddamg_hip_dirac_apply, [f32, f32], []),
+             (lib.ddamg_hip_smoother, [f32, f32], [1, 1]), (lib.ddamg_hip_restrict, [c32, f32], []),
+             (lib.ddamg_hip_interpolate, [f32, c32], [0]), (lib.ddamg_hip_coarse_apply, [c32, c32], []),
+             (lib.ddamg_hip_coarse_hop, [c32, c32], [0, 1.0, 0]), (lib.ddamg_hip_coarse_self_mul, [c32, c32], [0, 0]),
+             (lib.ddamg_hip_coarse_solve, [c32, c32], [None]), (lib.ddamg_hip_vcycle, [f32, f32], []),
+             (lib.ddamg_hip_solve_vec, [f64, f64], [1e-10, None, None, None])]
+    for entry, vecs, rest in calls:
+        for slot in range(len(vecs)):
+            refused(entry(c, *[None if k == slot else h for k, h in enumerate(vecs)], *rest))
+    cols = (ctypes.c_void_p * 2)
+    refused(lib.ddamg_hip_coarse_apply_many(c, 2, cols(c32.value, None), cols(c32.value, c32.value)))
+    refused(lib.ddamg_hip_coarse_apply_many(c, 2, cols(c32.value, c32.value), cols(None, c32.value)))
+    refused(lib.ddamg_hip_smoother(c, f32, c32, 1, 1))   # the wrong level
+    refused(lib.ddamg_hip_smoother(c, f32, f64, 1, 1))   # the wrong precision
+    refused(lib.ddamg_hip_smoother(c, f64, f64, 1, 1))
+    # no context: refused before anything is done with the vectors
+    refused(lib.ddamg_hip_vec_copy(None, f32, f32))
+    refused(lib.ddamg_hip_vec_axpy(None, f32, f32, f32, 1.0, 0.0))
+    refused(lib.ddamg_hip_vec_dot(None, f32, f32, None, None, None))
+    refused(lib.ddamg_hip_vec_destroy(None, f32))
+    assert lib.ddamg_hip_vec_destroy(c, None) == 0
+    x1, it1, cit1, rr1 = ctx.solve(b, 1e-10)
+    assert (it1, cit1, rr1) == (it0, cit0, rr0) and np.array_equal(x1, x0)
+    for w in v.values():
+        w.free()
+    ctx.close()
+
+
 # 9 ------------------------------------------------------------------------------------------------------------------------
 def test_memory(gold8, hip):
     gb = load_golden("ref_8x8_b4.npz")
