@@ -109,6 +109,8 @@ def load_library():
         "ddamg_hip_vec_upload": [vp, vp, dp],
         "ddamg_hip_vec_download": [vp, vp, dp],
         "ddamg_hip_dirac_apply": [vp, vp, vp],
+        "ddamg_hip_dirac_apply_dagger": [vp, vp, vp],
+        "ddamg_hip_gamma5": [vp, vp, vp],
         "ddamg_hip_vec_copy": [vp, vp, vp],
         "ddamg_hip_vec_axpy": [vp, vp, vp, vp, ctypes.c_double, ctypes.c_double],
         "ddamg_hip_vec_dot": [vp, vp, vp, dp, dp, dp],
@@ -141,6 +143,12 @@ def load_library():
         "ddamg_hip_vcycle": [vp, vp, vp],
         "ddamg_hip_solve": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
         "ddamg_hip_solve_vec": [vp, vp, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_dagger": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_dagger_vec": [vp, vp, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_dagger_device": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_squared": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_squared_vec": [vp, vp, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_squared_device": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -536,6 +544,14 @@ class Context:
     def dirac_apply(self, out, inp):
         _check(self._lib.ddamg_hip_dirac_apply(self._h, out._h, inp._h))
 
+    def dirac_apply_dagger(self, out, inp):
+        """out = D^dagger inp = gamma5 D gamma5 inp in one pass (fine-level Vectors of one precision, out is not inp)"""
+        _check(self._lib.ddamg_hip_dirac_apply_dagger(self._h, out._h, inp._h))
+
+    def gamma5(self, out, inp):
+        """out = gamma5 inp: spin components 0 and 1 change sign (fine-level Vectors of one precision; out may be inp)"""
+        _check(self._lib.ddamg_hip_gamma5(self._h, out._h, inp._h))
+
     # ---- BLAS-1 ----
     def vec_copy(self, dst, src):
         _check(self._lib.ddamg_hip_vec_copy(self._h, dst._h, src._h))
@@ -679,24 +695,57 @@ class Context:
     def vcycle(self, phi, eta):
         _check(self._lib.ddamg_hip_vcycle(self._h, phi._h, eta._h))
 
+    def _solve_host(self, name, b_lex, tol, out, squared=False):
+        """a host-array solve entry point `ddamg_hip_<name>`; squared: two iteration counts each, returned as pairs"""
+        b = np.ascontiguousarray(b_lex, dtype=np.float64)
+        if b.size != self.volume(0) * 24:
+            raise DDAMGError(f"{name}: right-hand side must hold V*12 complex numbers")
+        x = out if out is not None else np.empty((self.volume(0), 12, 2))
+        if x.dtype != np.float64 or not x.flags.c_contiguous or x.size != b.size:
+            raise DDAMGError(f"{name}: `out` must be a C-contiguous float64 array of V*12 complex numbers")
+        return (x,) + self._solve_call(name, _dp(x), _dp(b), tol, squared)
+
+    def _solve_call(self, name, x, b, tol, squared=False):
+        it = (ctypes.c_int * 2)(); ci = (ctypes.c_int * 2)(); rr = ctypes.c_double(0)
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, x, b, float(tol), it, ci, ctypes.byref(rr)))
+        if squared:
+            return (it[0], it[1]), (ci[0], ci[1]), rr.value
+        return it[0], ci[0], rr.value
+
+    def _solve_dev(self, name, x_dev_lex, b_dev_lex, tol, squared=False):
+        n = self.volume(0) * 24
+        return self._solve_call(name, _dev(x_dev_lex, n, name), _dev(b_dev_lex, n, name), tol, squared)
+
     def solve(self, b_lex, tol=0.0, out=None):
         """returns (x_lex, iterations, coarse_iterations, true relative residual); `out` reuses a solution array (a fresh
         one is first touched page by page while the device writes into it, which costs more than the solve at 32^4)"""
-        b = np.ascontiguousarray(b_lex, dtype=np.float64)
-        if b.size != self.volume(0) * 24:
-            raise DDAMGError("solve: right-hand side must hold V*12 complex numbers")
-        x = out if out is not None else np.empty((self.volume(0), 12, 2))
-        if x.dtype != np.float64 or not x.flags.c_contiguous or x.size != b.size:
-            raise DDAMGError("solve: `out` must be a C-contiguous float64 array of V*12 complex numbers")
-        it = ctypes.c_int(0); ci = ctypes.c_int(0); rr = ctypes.c_double(0)
-        _check(self._lib.ddamg_hip_solve(self._h, _dp(x), _dp(b), float(tol), ctypes.byref(it), ctypes.byref(ci), ctypes.byref(rr)))
-        return x, it.value, ci.value, rr.value
+        return self._solve_host("solve", b_lex, tol, out)
 
     def solve_vec(self, x, b, tol=0.0):
         """device-resident solve: x, b fine-level fp64 Vectors; returns (iterations, coarse_iterations, relres)"""
-        it = ctypes.c_int(0); ci = ctypes.c_int(0); rr = ctypes.c_double(0)
-        _check(self._lib.ddamg_hip_solve_vec(self._h, x._h, b._h, float(tol), ctypes.byref(it), ctypes.byref(ci), ctypes.byref(rr)))
-        return it.value, ci.value, rr.value
+        return self._solve_call("solve_vec", x._h, b._h, tol)
+
+    # ---- HMC solves: D^dagger x = b as x = gamma5 D^-1 gamma5 b, and D^dagger D x = b as the two solves back to back ----
+    def solve_dagger(self, b_lex, tol=0.0, out=None):
+        """D^dagger x = b; returns as solve() does (the numbers are those of the solve of D on gamma5 b)"""
+        return self._solve_host("solve_dagger", b_lex, tol, out)
+
+    def solve_dagger_vec(self, x, b, tol=0.0):
+        return self._solve_call("solve_dagger_vec", x._h, b._h, tol)
+
+    def solve_dagger_device(self, x_dev_lex, b_dev_lex, tol=0.0):
+        return self._solve_dev("solve_dagger_device", x_dev_lex, b_dev_lex, tol)
+
+    def solve_squared(self, b_lex, tol=0.0, out=None):
+        """D^dagger D x = b; returns (x_lex, (iterations of the D^dagger solve, of the D solve), the same pair of coarse iterations,
+        ||b - D^dagger D x|| / ||b||): that residual carries the condition of D^dagger and is not promised to be below tol"""
+        return self._solve_host("solve_squared", b_lex, tol, out, squared=True)
+
+    def solve_squared_vec(self, x, b, tol=0.0):
+        return self._solve_call("solve_squared_vec", x._h, b._h, tol, squared=True)
+
+    def solve_squared_device(self, x_dev_lex, b_dev_lex, tol=0.0):
+        return self._solve_dev("solve_squared_device", x_dev_lex, b_dev_lex, tol, squared=True)
 
     def preconditioner(self, in_lex):
         a = np.ascontiguousarray(in_lex, dtype=np.float64)
@@ -707,11 +756,7 @@ class Context:
     def solve_device(self, x_dev_lex, b_dev_lex, tol=0.0):
         """solve with the right-hand side and the solution in device memory ([V][12] complex float64, lexicographic; integer
         addresses or objects with data_ptr()); returns (iterations, coarse_iterations, true relative residual)"""
-        n = self.volume(0) * 24
-        it = ctypes.c_int(0); ci = ctypes.c_int(0); rr = ctypes.c_double(0)
-        _check(self._lib.ddamg_hip_solve_device(self._h, _dev(x_dev_lex, n, "solve_device"), _dev(b_dev_lex, n, "solve_device"), float(tol),
-                                                ctypes.byref(it), ctypes.byref(ci), ctypes.byref(rr)))
-        return it.value, ci.value, rr.value
+        return self._solve_dev("solve_device", x_dev_lex, b_dev_lex, tol)
 
     def preconditioner_device(self, out_dev_lex, in_dev_lex):
         """one V-cycle from / into arrays in device memory; returns out_dev_lex"""

@@ -64,6 +64,9 @@ template <typename T> void vec_zero(T* x, View v, hipStream_t st);
 // x[i] = uniform(-0.5, 0.5) from a counter-based generator (splitmix64 of seed, stream, i); n reals
 template <typename T> void vec_random(T* x, size_t n, unsigned long long seed, unsigned long long stream, hipStream_t st);
 template <typename T> void vec_copy(T* y, const T* x, View v, hipStream_t st);
+// y = gamma5 x (gamma5_PRECISION, src/dirac_generic.c:288-297: spin components 0 and 1 negated) for a fine vector or a site range
+// of one: the first half of the view's chunk rows changes sign.  One launch; y == x allowed.
+template <typename T> void vec_gamma5(T* y, const T* x, View v, hipStream_t st);
 // precision conversion between the float and double chunked-SoA layouts (V sites, nreal reals/site)
 template <typename TO, typename TI> void vec_convert(TO* y, const TI* x, size_t V, int nreal, hipStream_t st);
 // z = x + a*y  (a complex, by value)

@@ -89,7 +89,7 @@ __device__ __forceinline__ void unpack(const float4& v, double (&re)[2], double 
 __device__ __forceinline__ void unpack(const double2& v, double (&re)[1], double (&im)[1]) { re[0] = v.x; im[0] = v.y; }
 
 // ---- elementwise kernels -------------------------------------------------------------------
-enum { OP_ZERO, OP_COPY, OP_AXPY, OP_SCALE, OP_MINUS, OP_PLUS, OP_SCALE_INV_DEV };
+enum { OP_ZERO, OP_COPY, OP_AXPY, OP_SCALE, OP_MINUS, OP_PLUS, OP_SCALE_INV_DEV, OP_GAMMA5 };
 
 template <typename T, int OP>
 __global__ __launch_bounds__(BLK) void ew_kernel(T* __restrict__ z, const T* __restrict__ x, const T* __restrict__ y,
@@ -109,6 +109,12 @@ __global__ __launch_bounds__(BLK) void ew_kernel(T* __restrict__ z, const T* __r
       if constexpr (CH == 4) o = make_float4(0, 0, 0, 0); else o = make_double2(0, 0);
     } else if constexpr (OP == OP_COPY) {
       o = ldv<T>(x + a);
+    } else if constexpr (OP == OP_GAMMA5) {
+      // component-major fine vector: the chunk rows of spin 0 and 1 are the first half of the view
+      o = ldv<T>(x + a);
+      if (c < nchunks / 2) {
+        if constexpr (CH == 4) o = make_float4(-o.x, -o.y, -o.z, -o.w); else o = make_double2(-o.x, -o.y);
+      }
     } else if constexpr (OP == OP_SCALE_INV_DEV) {
       vec xv = ldv<T>(x + a);
       if constexpr (CH == 4) o = make_float4(xv.x * inv, xv.y * inv, xv.z * inv, xv.w * inv);
@@ -143,6 +149,10 @@ static void launch_ew(T* z, const T* x, const T* y, double ar, double ai, const 
 
 template <typename T> void vec_zero(T* x, View v, hipStream_t st) { launch_ew<T, OP_ZERO>(x, nullptr, nullptr, 0, 0, nullptr, v, st); }
 template <typename T> void vec_copy(T* y, const T* x, View v, hipStream_t st) { launch_ew<T, OP_COPY>(y, x, nullptr, 0, 0, nullptr, v, st); }
+template <typename T> void vec_gamma5(T* y, const T* x, View v, hipStream_t st) {
+  DDAMG_REQUIRE((v.total() / Chunk<T>::CH) % 2 == 0, "vec_gamma5: the view must hold whole spinors");
+  launch_ew<T, OP_GAMMA5>(y, x, nullptr, 0, 0, nullptr, v, st);
+}
 __global__ void arnoldi_norm_kernel(double* __restrict__ h, int m) {
   double s = h[2 * m];
   for (int i = 0; i < m; i++) s -= h[2 * i] * h[2 * i] + h[2 * i + 1] * h[2 * i + 1];
@@ -527,6 +537,7 @@ template void vec_random<double>(double*, size_t, unsigned long long, unsigned l
 #define INST(T)                                                                                         \
   template void vec_zero<T>(T*, View, hipStream_t);                                                      \
   template void vec_copy<T>(T*, const T*, View, hipStream_t);                                            \
+  template void vec_gamma5<T>(T*, const T*, View, hipStream_t);                                          \
   template void vec_axpy<T>(T*, const T*, const T*, double, double, View, hipStream_t);                  \
   template void vec_scale<T>(T*, const T*, double, double, View, hipStream_t);                           \
   template void vec_scale_inv_dev<T>(T*, const T*, const double*, View, hipStream_t);                    \

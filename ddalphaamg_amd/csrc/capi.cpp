@@ -647,6 +647,29 @@ int ddamg_hip_dirac_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_
   DDAMG_API_END
 }
 
+int ddamg_hip_dirac_apply_dagger(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(out && in, "null argument");
+  DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
+  DDAMG_REQUIRE(out->level == 0 && in->level == 0, "fine-level vectors expected");
+  DDAMG_REQUIRE(out->precision == in->precision, "precision mismatch");
+  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place apply is not supported");
+  if (in->precision == 32) c->fop32.apply_dagger(vec_data<float>(out), vec_data<float>(in), c->stream);
+  else c->fop64.apply_dagger(vec_data<double>(out), vec_data<double>(in), c->stream);
+  DDAMG_API_END
+}
+
+int ddamg_hip_gamma5(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(out && in, "null argument");
+  DDAMG_REQUIRE(out->level == 0 && in->level == 0, "fine-level vectors expected");
+  DDAMG_REQUIRE(out->precision == in->precision, "precision mismatch");
+  with_vec(out, [&](auto* d) { using T = pointee<decltype(d)>; vec_gamma5<T>(d, vec_data<T>(in), whole(vec_len(out)), c->stream); });
+  DDAMG_API_END
+}
+
 int ddamg_hip_get_site_order(ddamg_hip_ctx* c, int level, int* lex_of_site) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c, "null context");   // host tables only: no device is selected

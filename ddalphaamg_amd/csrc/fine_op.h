@@ -83,6 +83,10 @@ class FineOp {
   void scale_clover(const double* base64, double scale_even, double scale_odd, hipStream_t st);
   // eta = D_W phi; with a process grid: pack -> exchange (overlapped with the interior tiles) -> boundary tiles
   void apply(T* eta, const T* phi, hipStream_t st) const;
+  // eta = D_W^dagger phi = gamma5 D_W gamma5 phi in the launches of apply(): the kernels negate spin components 0 and 1 of what they
+  // read from phi and of eta in front of its store (d_plus_clover_dagger_PRECISION, src/dirac_generic.c:281-285, takes three
+  // passes); the bits are those of vec_gamma5, apply, vec_gamma5.  eta != phi.
+  void apply_dagger(T* eta, const T* phi, hipStream_t st) const;
   FineOpDev<T> dev() const { return FineOpDev<T>{D_, clover_, clover_inv_, nb_, V_, halo_.recv(), halo_.dev(), tile_nb_, tnb_, parity_, Dc_, Dsgn_, Cc_, Dp_, Dpb_}; }
   bool links_compressed() const { return Dc_ != nullptr; }
   // reals per link that apply() reads: 18, 12 (two-row form) or 10 (pivot form, fp32 only)
@@ -111,6 +115,8 @@ class FineOp {
   void parity_select(T* out, const T* a, const T* b, int keep, hipStream_t st) const;
 
  private:
+  template <bool DAG>
+  void apply_impl(T* eta, const T* phi, hipStream_t st) const;
   void ensure_storage(const Geometry& g, hipStream_t st);   // the fields and the site tables, at the first upload
   void layout_staged(const Geometry& g, const double* dD, const double* dC, const Knobs& knobs, hipStream_t st);
   DeviceBuffer<T> D_, clover_, clover_inv_;
@@ -207,11 +213,12 @@ __device__ __forceinline__ void halo_backward(const FineOpDev<T>& op, int slot, 
 
 // layout converters between the reference's lexicographic AoS fp64 vectors
 // ([V][ndof] complex, src/main_pre_def_generic.h:25-27) and device chunked-SoA vectors.
-// `lex_of_site` is a device table.  ndof = complex dof per site.
+// `lex_of_site` is a device table.  ndof = complex dof per site.  gamma5 (fine vectors, ndof = 12): the destination is gamma5 times
+// the source, at no extra pass (the D^dagger solves: x = gamma5 D^-1 gamma5 b)
 template <typename T>
-void vec_from_lex(T* dst, const double* src_lex_dev, const int* lex_of_site, int V, int ndof, hipStream_t st);
+void vec_from_lex(T* dst, const double* src_lex_dev, const int* lex_of_site, int V, int ndof, hipStream_t st, bool gamma5 = false);
 template <typename T>
-void vec_to_lex(double* dst_lex_dev, const T* src, const int* lex_of_site, int V, int ndof, hipStream_t st);
+void vec_to_lex(double* dst_lex_dev, const T* src, const int* lex_of_site, int V, int ndof, hipStream_t st, bool gamma5 = false);
 
 // site-major (AoS) coarse vectors <-> lexicographic host layout
 template <typename T>

@@ -66,9 +66,20 @@ __device__ __forceinline__ void load_site_as(const TIN* __restrict__ base, size_
   }
 }
 
+// the dagger form (FineOp::apply_dagger): gamma5 = diag(-1, -1, +1, +1) in spin, so spin components 0 and 1 (reals 0-11 of the 24)
+// change sign on everything read from phi and on eta in front of its store; the arithmetic in between is the one of D, and every
+// intermediate is the one of gamma5, D, gamma5 in three passes (negation is exact), hence the same bits
+template <bool DAG, typename T>
+__device__ __forceinline__ void gamma5_sign(T (&v)[24]) {
+  if constexpr (DAG) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) v[k] = -v[k];
+  }
+}
+
 // CCL is not used here: it gives each kernel its own instantiation (one tile_dir shared by the CCL and the non-CCL kernel is
 // optimised once before it is inlined into both, and both then need 143 VGPRs instead of 120)
-template <typename T, int MU, bool ARITH, LinkForm LF, bool HB2, typename TIN = T, bool CCL = false>
+template <typename T, int MU, bool ARITH, LinkForm LF, bool HB2, typename TIN = T, bool CCL = false, bool DAG = false>
 __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const FineOpDev<T>& op, size_t s, bool live, int tile0, const uint4& q,
                                          const int (&tn)[8], const T (&p)[24], T (&e)[24], T* __restrict__ sp, T* __restrict__ hb) {
   const size_t V = op.V;
@@ -93,6 +104,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
         for (int c = 0; c < 24; c++) pn[c] = sp[c * 256 + (j - tile0)];
       } else {
         load_site_as<T, TIN, 24>(phi, V, j, pn);
+        gamma5_sign<DAG>(pn);
       }
       hop_accumulate<T, MU, true>(U, pn, e);
     } else {
@@ -113,6 +125,7 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
     } else {
       T pn[24], Un[18];
       load_site_as<T, TIN, 24>(phi, V, j, pn);
+      gamma5_sign<DAG>(pn);
       load_link<T, MU, LF>(op, V, (size_t)j, Un);
       hop_accumulate<T, MU, false>(Un, pn, e);
     }
@@ -127,8 +140,8 @@ __device__ __forceinline__ void tile_dir(const TIN* __restrict__ phi, const Fine
 // the list, so results change by rounding with it (docs/design/04_kernels.md has what was measured for the other orders).
 constexpr int kDirOrder[4] = {3, 2, 0, 1};
 
-// CCL: the clover term from its 56-real form (FineOpDev::cloverc, fp32 only)
-template <typename T, bool ARITH, LinkForm LF = LinkForm::Full, typename TIN = T, bool CCL = false>
+// CCL: the clover term from its 56-real form (FineOpDev::cloverc, fp32 only); DAG: eta = D^dagger phi = gamma5 D gamma5 phi (gamma5_sign)
+template <typename T, bool ARITH, LinkForm LF = LinkForm::Full, typename TIN = T, bool CCL = false, bool DAG = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds_kernel(T* __restrict__ eta, const TIN* __restrict__ phi, FineOpDev<T> op, int ntiles,
                                                                   const int* __restrict__ tile_list) {
   // fp32: two buffers for the backward products, used in turn, so that one barrier per direction is enough (48 KB of LDS,
@@ -155,8 +168,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
 #pragma unroll
     for (int d = 0; d < 8; d++) tn[d] = op.tile_nb[(size_t)d * (V >> 8) + tile];
   }
-  if (live) load_site_as<T, TIN, 24>(phi, V, s, p);
-  else {
+  if (live) {
+    load_site_as<T, TIN, 24>(phi, V, s, p);
+    gamma5_sign<DAG>(p);
+  } else {
 #pragma unroll
     for (int k = 0; k < 24; k++) p[k] = 0;
   }
@@ -179,11 +194,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_apply_lds
   }
   __syncthreads();
   // the two hb buffers alternate with the position in the list, whichever direction stands there
-  tile_dir<T, kDirOrder[0], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
-  tile_dir<T, kDirOrder[1], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
-  tile_dir<T, kDirOrder[2], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
-  tile_dir<T, kDirOrder[3], ARITH, LF, HB2, TIN, CCL>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
-  if (live) store_site<T, 24, DDAMG_NT_STORE>(eta, V, s, e);
+  tile_dir<T, kDirOrder[0], ARITH, LF, HB2, TIN, CCL, DAG>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
+  tile_dir<T, kDirOrder[1], ARITH, LF, HB2, TIN, CCL, DAG>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
+  tile_dir<T, kDirOrder[2], ARITH, LF, HB2, TIN, CCL, DAG>(phi, op, s, live, tile0, q, tn, p, e, sp, hb);
+  tile_dir<T, kDirOrder[3], ARITH, LF, HB2, TIN, CCL, DAG>(phi, op, s, live, tile0, q, tn, p, e, sp, hb1);
+  if (live) {
+    gamma5_sign<DAG>(e);
+    store_site<T, 24, DDAMG_NT_STORE>(eta, V, s, e);
+  }
 }
 
 // ---- hopping term onto one parity (global odd-even: GMRES smoother) -----------------------------------------------
@@ -293,26 +311,28 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) void dirac_hop_parit
   }
 }
 
-template <typename T, bool CCL>
+template <typename T, bool CCL, bool DAG>
 static void launch_dirac_apply(T* eta, const T* phi, const FineOpDev<T>& op, int ntiles, const int* tile_list, hipStream_t st) {
   if constexpr (sizeof(T) == 4) {
     if (op.tnb && op.Dp) {
-      hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Pivot, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+      hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Pivot, T, CCL, DAG>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
       return;
     }
   }
-  if (op.tnb && op.Dc) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::TwoRow, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
-  else if (op.tnb) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Full, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
-  else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, LinkForm::Full, T, CCL>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  if (op.tnb && op.Dc) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::TwoRow, T, CCL, DAG>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  else if (op.tnb) hipLaunchKernelGGL((dirac_apply_lds_kernel<T, true, LinkForm::Full, T, CCL, DAG>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
+  else hipLaunchKernelGGL((dirac_apply_lds_kernel<T, false, LinkForm::Full, T, CCL, DAG>), dim3(ntiles), dim3(256), 0, st, eta, phi, op, ntiles, tile_list);
 }
 
+// apply() and apply_dagger(): the same launches, the kernels with and without the gamma5 signs
 template <typename T>
-void FineOp<T>::apply(T* eta, const T* phi, hipStream_t st) const {
+template <bool DAG>
+void FineOp<T>::apply_impl(T* eta, const T* phi, hipStream_t st) const {
   DDAMG_REQUIRE(D_ != nullptr, "fine operator not uploaded");
   auto launch = [&](int ntiles, const int* tile_list) {
     if (ntiles == 0) return;
-    if (Cc_) launch_dirac_apply<T, sizeof(T) == 4>(eta, phi, dev(), ntiles, tile_list, st);
-    else launch_dirac_apply<T, false>(eta, phi, dev(), ntiles, tile_list, st);
+    if (Cc_) launch_dirac_apply<T, sizeof(T) == 4, DAG>(eta, phi, dev(), ntiles, tile_list, st);
+    else launch_dirac_apply<T, false, DAG>(eta, phi, dev(), ntiles, tile_list, st);
     DDAMG_HIP_CHECK(hipGetLastError());
   };
   if (!halo_.active()) {
@@ -321,11 +341,19 @@ void FineOp<T>::apply(T* eta, const T* phi, hipStream_t st) const {
   }
   // reference order of events: src/dirac_generic.c:178-262 (project+send, interior work, wait, boundary): tiles without an
   // off-process neighbour during the exchange, the others after it
-  halo_.pack(phi, D_, V_, st);
+  halo_.pack(phi, D_, V_, st, DAG);
   halo_.exchange_begin(comm_, st);
   launch(halo_.n_interior(), halo_.interior_tiles());
   halo_.exchange_finish(comm_, st);
   launch(halo_.n_boundary(), halo_.boundary_tiles());
+}
+template <typename T>
+void FineOp<T>::apply(T* eta, const T* phi, hipStream_t st) const { apply_impl<false>(eta, phi, st); }
+// d_plus_clover_dagger_PRECISION (src/dirac_generic.c:281-285: gamma5, D, gamma5 in three passes) in one
+template <typename T>
+void FineOp<T>::apply_dagger(T* eta, const T* phi, hipStream_t st) const {
+  DDAMG_REQUIRE(eta != phi, "apply_dagger: in place");
+  apply_impl<true>(eta, phi, st);
 }
 
 // eta = D phi with phi an fp32 vector (its own layout): the fp64 operator of the outer solver on the iterates that come out of the
@@ -898,7 +926,8 @@ void FineOp<T>::parity_select(T* out, const T* a, const T* b, int keep, hipStrea
 }
 
 // ---- layout converters ---------------------------------------------------------------------
-template <typename T>
+// G5: the vector times gamma5 on the way (the reals of spin components 0 and 1, the first half of a site's, change sign)
+template <typename T, bool G5>
 __global__ void vec_from_lex_kernel(T* __restrict__ dst, const double* __restrict__ src, const int* __restrict__ lex_of_site, int V, int nreal) {
   // one thread per (site, real): coalesced on the SoA side
   constexpr int CH = Chunk<T>::CH;
@@ -911,9 +940,10 @@ __global__ void vec_from_lex_kernel(T* __restrict__ dst, const double* __restric
   size_t s = rem / CH;
   int c = rem % CH;
   int r = (int)k * CH + c;
-  dst[i] = (T)src[(size_t)lex_of_site[s] * nreal + r];
+  const T x = (T)src[(size_t)lex_of_site[s] * nreal + r];
+  dst[i] = G5 && 2 * r < nreal ? -x : x;
 }
-template <typename T>
+template <typename T, bool G5>
 __global__ void vec_to_lex_kernel(double* __restrict__ dst, const T* __restrict__ src, const int* __restrict__ lex_of_site, int V, int nreal) {
   constexpr int CH = Chunk<T>::CH;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -924,23 +954,28 @@ __global__ void vec_to_lex_kernel(double* __restrict__ dst, const T* __restrict_
   size_t s = rem / CH;
   int c = rem % CH;
   int r = (int)k * CH + c;
-  dst[(size_t)lex_of_site[s] * nreal + r] = (double)src[i];
+  const double x = (double)src[i];
+  dst[(size_t)lex_of_site[s] * nreal + r] = G5 && 2 * r < nreal ? -x : x;
 }
 
 template <typename T>
-void vec_from_lex(T* dst, const double* src, const int* lex_of_site, int V, int ndof, hipStream_t st) {
+void vec_from_lex(T* dst, const double* src, const int* lex_of_site, int V, int ndof, hipStream_t st, bool gamma5) {
   int nreal = 2 * ndof;
   DDAMG_REQUIRE(nreal % Chunk<T>::CH == 0, "dof per site must fill whole 16-byte chunks");
   size_t total = (size_t)V * nreal;
-  hipLaunchKernelGGL(vec_from_lex_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
+  DDAMG_REQUIRE(!gamma5 || ndof == 12, "gamma5 acts on fine vectors");
+  if (gamma5) hipLaunchKernelGGL((vec_from_lex_kernel<T, true>), dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
+  else hipLaunchKernelGGL((vec_from_lex_kernel<T, false>), dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 template <typename T>
-void vec_to_lex(double* dst, const T* src, const int* lex_of_site, int V, int ndof, hipStream_t st) {
+void vec_to_lex(double* dst, const T* src, const int* lex_of_site, int V, int ndof, hipStream_t st, bool gamma5) {
   int nreal = 2 * ndof;
   DDAMG_REQUIRE(nreal % Chunk<T>::CH == 0, "dof per site must fill whole 16-byte chunks");
   size_t total = (size_t)V * nreal;
-  hipLaunchKernelGGL(vec_to_lex_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
+  DDAMG_REQUIRE(!gamma5 || ndof == 12, "gamma5 acts on fine vectors");
+  if (gamma5) hipLaunchKernelGGL((vec_to_lex_kernel<T, true>), dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
+  else hipLaunchKernelGGL((vec_to_lex_kernel<T, false>), dim3((total + 255) / 256), dim3(256), 0, st, dst, src, lex_of_site, V, nreal);
   DDAMG_HIP_CHECK(hipGetLastError());
 }
 
@@ -971,9 +1006,9 @@ template void aos_to_lex<double>(double*, const double*, const int*, int, int, h
 
 template class FineOp<float>;
 template class FineOp<double>;
-template void vec_from_lex<float>(float*, const double*, const int*, int, int, hipStream_t);
-template void vec_from_lex<double>(double*, const double*, const int*, int, int, hipStream_t);
-template void vec_to_lex<float>(double*, const float*, const int*, int, int, hipStream_t);
-template void vec_to_lex<double>(double*, const double*, const int*, int, int, hipStream_t);
+template void vec_from_lex<float>(float*, const double*, const int*, int, int, hipStream_t, bool);
+template void vec_from_lex<double>(double*, const double*, const int*, int, int, hipStream_t, bool);
+template void vec_to_lex<float>(double*, const float*, const int*, int, int, hipStream_t, bool);
+template void vec_to_lex<double>(double*, const double*, const int*, int, int, hipStream_t, bool);
 
 }  // namespace ddamg

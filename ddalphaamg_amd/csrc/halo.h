@@ -79,8 +79,8 @@ class Halo {
   const int* boundary_tiles() const { return d_boundary_; }
   int n_interior() const { return n_interior_; }
   int n_boundary() const { return n_boundary_; }
-  // pack kernel: fills the send arena from phi (needs the links: D = FineOpDev::D)
-  void pack(const T* phi, const T* D, int V, hipStream_t st);
+  // pack kernel: fills the send arena from phi (needs the links: D = FineOpDev::D); dagger: from gamma5 phi (FineOp::apply_dagger)
+  void pack(const T* phi, const T* D, int V, hipStream_t st, bool dagger = false);
   void pack_f32in(const float* phi, const T* D, int V, hipStream_t st);    // the same from an fp32 vector (converted in the loads)
   void exchange_begin(Comm* c, hipStream_t st) { arena_.exchange_begin(c, st); }
   void exchange_finish(Comm* c, hipStream_t st) { arena_.exchange_finish(c, st); }

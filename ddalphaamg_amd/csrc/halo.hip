@@ -264,7 +264,8 @@ void comm_destroy(Comm* c) {
 }
 
 // ---- pack -----------------------------------------------------------------------------------------
-template <typename T, int MU, typename TIN = T>
+// DAG: the face sites of gamma5 phi (spin components 0 and 1 negated as they are read), for FineOp::apply_dagger
+template <typename T, int MU, typename TIN = T, bool DAG = false>
 __device__ __forceinline__ void pack_site(const TIN* __restrict__ phi, const T* __restrict__ D, size_t V, int s, bool plus, T (&out)[12]) {
   T p[24];
   if constexpr (sizeof(TIN) == sizeof(T)) load_site<T, 24>(reinterpret_cast<const T*>(phi), V, s, p);
@@ -273,6 +274,10 @@ __device__ __forceinline__ void pack_site(const TIN* __restrict__ phi, const T* 
     load_site<TIN, 24>(phi, V, s, q);
 #pragma unroll
     for (int k = 0; k < 24; k++) p[k] = (T)q[k];
+  }
+  if constexpr (DAG) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) p[k] = -p[k];
   }
   if (plus) {
     T U[18], h[12];
@@ -284,7 +289,7 @@ __device__ __forceinline__ void pack_site(const TIN* __restrict__ phi, const T* 
   }
 }
 
-template <typename T, typename TIN = T>
+template <typename T, typename TIN = T, bool DAG = false>
 __global__ __launch_bounds__(256) void halo_pack_kernel(T* __restrict__ send, const TIN* __restrict__ phi, const T* __restrict__ D,
                                                         const int* __restrict__ face_sites, HaloDev hd, int V, int total) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -306,10 +311,10 @@ __global__ __launch_bounds__(256) void halo_pack_kernel(T* __restrict__ send, co
   const int s = face_sites[i];
   T out[12];
   switch (mu) {
-    case 0: pack_site<T, 0, TIN>(phi, D, V, s, plus, out); break;
-    case 1: pack_site<T, 1, TIN>(phi, D, V, s, plus, out); break;
-    case 2: pack_site<T, 2, TIN>(phi, D, V, s, plus, out); break;
-    default: pack_site<T, 3, TIN>(phi, D, V, s, plus, out); break;
+    case 0: pack_site<T, 0, TIN, DAG>(phi, D, V, s, plus, out); break;
+    case 1: pack_site<T, 1, TIN, DAG>(phi, D, V, s, plus, out); break;
+    case 2: pack_site<T, 2, TIN, DAG>(phi, D, V, s, plus, out); break;
+    default: pack_site<T, 3, TIN, DAG>(phi, D, V, s, plus, out); break;
   }
   store_site<T, 12>(send + hd.off[d], (size_t)hd.F[mu], (size_t)slot, out);
 }
@@ -418,10 +423,14 @@ void Halo<T>::init(const Geometry& g) {
 }
 
 template <typename T>
-void Halo<T>::pack(const T* phi, const T* D, int V, hipStream_t st) {
+void Halo<T>::pack(const T* phi, const T* D, int V, hipStream_t st, bool dagger) {
   const int total = arena_.total_sites();
-  hipLaunchKernelGGL(halo_pack_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<T*>(arena_.send()), phi, D,
-                     arena_.d_face_sites(), hd_, V, total);
+  if (dagger)
+    hipLaunchKernelGGL((halo_pack_kernel<T, T, true>), dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<T*>(arena_.send()), phi, D,
+                       arena_.d_face_sites(), hd_, V, total);
+  else
+    hipLaunchKernelGGL(halo_pack_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<T*>(arena_.send()), phi, D,
+                       arena_.d_face_sites(), hd_, V, total);
   DDAMG_HIP_CHECK(hipGetLastError());
   arena_.mark_packed(st);
 }

@@ -88,24 +88,19 @@ static void ensure_outer(ddamg_hip_ctx* c) {
 }
 
 // cgn_double (src/linsolve_generic.c:503-640; method -1, src/top_level.c:82-83): conjugate gradients on the normal
-// equations D^H D x = D^H b with D^H = g5 D g5 (apply_operator_dagger_PRECISION, src/linalg_generic.c / dirac_generic.c);
+// equations D^H D x = D^H b with D^H = g5 D g5 in one pass (FineOp::apply_dagger; d_plus_clover_dagger_PRECISION, src/dirac_generic.c:281-285);
 // once the normal-equation residual has dropped by tol the loop goes on on the true residual of D x = b (CGNR phase).
 // At most restart*max_restart iterations (src/init.c:179).
 static int solve_cgn(ddamg_hip_ctx* c, double tol, double* relres) {
   typedef std::complex<double> cd;
   Gmres<double>& g = c->outer;
   const size_t n = g.vec_elems;
-  const View all = whole(n), upper = View{1, 0, 0, n / 2}, lower = View{1, 0, n / 2, n / 2};
+  const View all = whole(n);
   ReduceWork& rw = c->rw_outer;
   hipStream_t st = c->stream;
-  double *x = g.x, *b = g.b, *r_true = g.r, *p = g.w, *pp = g.V(0), *Dp = g.V(1), *r_old = g.V(2), *r_new = g.V(3), *tmp = g.V(4);
-  // g5: the spin components 0,1 (the first half of the component-major vector) change sign (g5_PRECISION, src/oddeven_generic.c:780-800)
-  auto g5 = [&](double* out, const double* in) {
-    vec_scale<double>(out, in, -1.0, 0.0, upper, st);
-    if (out != in) vec_copy<double>(out, in, lower, st);
-  };
+  double *x = g.x, *b = g.b, *r_true = g.r, *p = g.w, *pp = g.V(0), *Dp = g.V(1), *r_old = g.V(2), *r_new = g.V(3);
   auto D = [&](double* out, const double* in) { c->fop64.apply(out, in, st); };
-  auto Ddag = [&](double* out, const double* in) { g5(tmp, in); D(out, tmp); g5(out, out); };
+  auto Ddag = [&](double* out, const double* in) { c->fop64.apply_dagger(out, in, st); };
   auto dot = [&](const double* a, const double* v) {   // <a, v>, conjugate-linear in a
     vec_multi_dot<double>(a, 0, 1, v, all, rw, rw.d_result, st);
     DDAMG_HIP_CHECK(hipMemcpyAsync(rw.h_result, rw.d_result, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -648,21 +643,72 @@ static void precondition_core(ddamg_hip_ctx* c, Load load, Store store) {
   c->last_coarse_iter = coarse_iterations_of(c);
 }
 
-// load / store callbacks for a fine vector `lex` in lattice order: in device memory, or (st given) in host memory through that staging buffer
-static auto load_lex(ddamg_hip_ctx* c, const double* lex, double* st = nullptr) {
+// load / store callbacks for a fine vector `lex` in lattice order: in device memory, or (st given) in host memory through that staging buffer;
+// g5: gamma5 times the vector arrives (the D^dagger solves)
+static auto load_lex(ddamg_hip_ctx* c, const double* lex, double* st = nullptr, bool g5 = false) {
   return [=](double* dst) {
     const int V = c->levels[0]->geom.V;
     if (st) DDAMG_HIP_CHECK(hipMemcpyAsync(st, lex, sizeof(double) * 24 * V, hipMemcpyHostToDevice, c->stream));
-    vec_from_lex<double>(dst, st ? st : lex, c->levels[0]->d_lex_of_site, V, 12, c->stream);
+    vec_from_lex<double>(dst, st ? st : lex, c->levels[0]->d_lex_of_site, V, 12, c->stream, g5);
   };
 }
-static auto store_lex(ddamg_hip_ctx* c, double* lex, double* st = nullptr) {
+static auto store_lex(ddamg_hip_ctx* c, double* lex, double* st = nullptr, bool g5 = false) {
   return [=](const double* src) {
     const int V = c->levels[0]->geom.V;
-    vec_to_lex<double>(st ? st : lex, src, c->levels[0]->d_lex_of_site, V, 12, c->stream);
+    vec_to_lex<double>(st ? st : lex, src, c->levels[0]->d_lex_of_site, V, 12, c->stream, g5);
     if (st) DDAMG_HIP_CHECK(hipMemcpyAsync(lex, st, sizeof(double) * 24 * V, hipMemcpyDeviceToHost, c->stream));
   };
 }
+static ddamg::ReduceWork& blas_rw(ddamg_hip_ctx* c) {
+  if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
+  return c->rw_blas;
+}
+// the two fine fp64 vectors of a *_vec solve
+static void require_solve_vecs(const ddamg_hip_vec* x, const ddamg_hip_vec* b, const char* msg) {
+  DDAMG_REQUIRE(x && b, "null argument");
+  DDAMG_REQUIRE(x->level == 0 && b->level == 0 && x->precision == 64 && b->precision == 64, msg);
+}
+// load / store callbacks for fine fp64 vectors of the boundary (or of the solver's layout); g5: gamma5 times the vector arrives
+static auto load_dev(ddamg_hip_ctx* c, const double* v, bool g5 = false) {
+  return [=](double* dst) {
+    const View all = whole((size_t)24 * c->levels[0]->geom.V);
+    if (g5) vec_gamma5<double>(dst, v, all, c->stream); else vec_copy<double>(dst, v, all, c->stream);
+  };
+}
+static auto store_dev(ddamg_hip_ctx* c, double* v, bool g5 = false) {
+  return [=](const double* src) {
+    const View all = whole((size_t)24 * c->levels[0]->geom.V);
+    if (g5) vec_gamma5<double>(v, src, all, c->stream); else vec_copy<double>(v, src, all, c->stream);
+  };
+}
+
+// D^dagger D x = b by two solves through the hierarchy of D: y = gamma5 D^-1 gamma5 b (the signs in the callbacks load_g5b and, here,
+// in the store of y), then x = D^-1 y.  y and the residual's workspace live for this call only; load_b(dst) fills the plain b once more
+// for the residual of the system the caller asked for, ||b - D^dagger D x|| / ||b||, in fp64.
+template <typename LoadG5B, typename LoadB, typename StoreX>
+static void solve_squared_core(ddamg_hip_ctx* c, double tol, LoadG5B load_g5b, LoadB load_b, StoreX store_x, int* iterations, int* coarse_iterations,
+                               double* relres) {
+  const size_t n = (size_t)24 * c->levels[0]->geom.V;
+  const View all = whole(n);
+  DeviceBuffer<double> y, t;
+  y.alloc(n);
+  t.alloc(n);
+  solve_core(c, tol, load_g5b, store_dev(c, y, true), iterations, coarse_iterations, nullptr);
+  double rr = 0;
+  solve_core(c, tol, load_dev(c, y), [&](const double* x) {
+    ReduceWork& rw = blas_rw(c);
+    c->fop64.apply(t, x, c->stream);
+    c->fop64.apply_dagger(y, t, c->stream);
+    load_b(t);
+    const double nb = host_norm<double>(t, all, rw, c->stream);
+    vec_minus<double>(t, t, y, all, c->stream);
+    rr = nb > 0 ? host_norm<double>(t, all, rw, c->stream) / nb : 0.0;
+    store_x(x);
+  }, iterations ? iterations + 1 : nullptr, coarse_iterations ? coarse_iterations + 1 : nullptr, nullptr);
+  c->last_relres = rr;
+  if (relres) *relres = rr;
+}
+
 // the two arrays of a *_device entry point: in the memory of the context's device, and apart
 static void require_device_pair(ddamg_hip_ctx* c, double* out, const double* in, const char* name) {
   const size_t nb = sizeof(double) * 24 * c->levels[0]->geom.V;
@@ -693,21 +739,67 @@ int ddamg_hip_solve_device(ddamg_hip_ctx* c, double* x_dev_lex, const double* b_
 int ddamg_hip_solve_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN
   enter(c);
-  DDAMG_REQUIRE(x && b, "null argument");
-  DDAMG_REQUIRE(x->level == 0 && b->level == 0 && x->precision == 64 && b->precision == 64, "solve_vec needs fine-level fp64 vectors");
-  const size_t n = (size_t)24 * c->levels[0]->geom.V;
-  solve_core(c, tol,
-             [&](double* dst) { vec_copy<double>(dst, vec_data<double>(b), whole(n), c->stream); },
-             [&](const double* src) { vec_copy<double>(vec_data<double>(x), src, whole(n), c->stream); },
-             iterations, coarse_iterations, relres);
+  require_solve_vecs(x, b, "solve_vec needs fine-level fp64 vectors");
+  solve_core(c, tol, load_dev(c, vec_data<double>(b)), store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+// ---- D^dagger x = b: x = gamma5 D^-1 gamma5 b, the signs in the load and store callbacks (no pass of their own) ----
+int ddamg_hip_solve_dagger(ddamg_hip_ctx* c, double* x_lex, const double* b_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(x_lex && b_lex, "null argument");
+  double* st = c->stage(sizeof(double) * 24 * c->levels[0]->geom.V);
+  solve_core(c, tol, load_lex(c, b_lex, st, true), store_lex(c, x_lex, st, true), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_dagger_device(ddamg_hip_ctx* c, double* x_dev_lex, const double* b_dev_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_dagger_device");
+  solve_core(c, tol, load_lex(c, b_dev_lex, nullptr, true), store_lex(c, x_dev_lex, nullptr, true), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_dagger_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations, int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_dagger_vec needs fine-level fp64 vectors");
+  solve_core(c, tol, load_dev(c, vec_data<double>(b), true), store_dev(c, vec_data<double>(x), true), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+// ---- D^dagger D x = b (solve_squared_core) ----
+int ddamg_hip_solve_squared(ddamg_hip_ctx* c, double* x_lex, const double* b_lex, double tol, int iterations[2], int coarse_iterations[2], double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(x_lex && b_lex, "null argument");
+  double* st = c->stage(sizeof(double) * 24 * c->levels[0]->geom.V);
+  solve_squared_core(c, tol, load_lex(c, b_lex, st, true), load_lex(c, b_lex, st), store_lex(c, x_lex, st), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_squared_device(ddamg_hip_ctx* c, double* x_dev_lex, const double* b_dev_lex, double tol, int iterations[2], int coarse_iterations[2],
+                                   double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_squared_device");
+  solve_squared_core(c, tol, load_lex(c, b_dev_lex, nullptr, true), load_lex(c, b_dev_lex), store_lex(c, x_dev_lex), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_squared_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int iterations[2], int coarse_iterations[2],
+                                double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_squared_vec needs fine-level fp64 vectors");
+  const double* bd = vec_data<double>(b);
+  solve_squared_core(c, tol, load_dev(c, bd, true), load_dev(c, bd), store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres);
   DDAMG_API_END
 }
 
 // ---- BLAS-1 on device vectors (src/linalg_generic.c:29-353) ---------------------------------------
-static ddamg::ReduceWork& blas_rw(ddamg_hip_ctx* c) {
-  if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
-  return c->rw_blas;
-}
 static void same_shape(const ddamg_hip_vec* a, const ddamg_hip_vec* b) {
   DDAMG_REQUIRE(a && b && a->level == b->level && a->precision == b->precision, "vectors differ in level or precision");
 }

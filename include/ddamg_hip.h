@@ -172,6 +172,13 @@ int ddamg_hip_vec_download_device(ddamg_hip_ctx* ctx, const ddamg_hip_vec* v, do
 
 /* replaces d_plus_clover_float / d_plus_clover_double (src/dirac_generic.c:159-277) */
 int ddamg_hip_dirac_apply(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in);
+/* d_plus_clover_dagger_PRECISION (src/dirac_generic.c:281-285) in one pass: out = D^dagger in = gamma5 D gamma5 in, in the launches
+ * of ddamg_hip_dirac_apply (the signs sit in the kernel's loads and in its store) and with the bits of the three passes.  Fine-level
+ * vectors of equal precision, 32 or 64; out == in is refused, as by ddamg_hip_dirac_apply. */
+int ddamg_hip_dirac_apply_dagger(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in);
+/* gamma5_PRECISION (src/dirac_generic.c:288-297): spin components 0 and 1 change sign.  One launch; fine-level vectors of equal
+ * precision, 32 or 64; out == in allowed */
+int ddamg_hip_gamma5(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in);
 
 /* BLAS-1 on device vectors: replaces vector_PRECISION_copy / vector_PRECISION_saxpy (z = x + alpha*y) and
  * global_inner_product_PRECISION <x,y> = sum conj(x_i) y_i together with global_norm_PRECISION(x)
@@ -321,6 +328,30 @@ int ddamg_hip_preconditioner(ddamg_hip_ctx* ctx, double* out_lex, const double* 
 int ddamg_hip_solve_device(ddamg_hip_ctx* ctx, double* x_dev_lex, const double* b_dev_lex, double tol,
                            int* iterations, int* coarse_iterations, double* relres);
 int ddamg_hip_preconditioner_device(ddamg_hip_ctx* ctx, double* out_dev_lex, const double* in_dev_lex);
+/* D^dagger x = b through the hierarchy of D: x = gamma5 D^-1 gamma5 b.  The reference has the operator (d_plus_clover_dagger_PRECISION,
+ * src/dirac_generic.c:281-285) and no driver for this solve.  gamma5 costs no pass over the vectors: the signs sit in the layout kernels
+ * that load b and store x (in one gamma5 kernel each in place of the copies of the _vec form).  Every `method` and `mixed_precision` of
+ * ddamg_hip_solve, and process grids (gamma5 is local).  relres, the iteration counts and ddamg_hip_residual_history are those of the
+ * inner solve of D on gamma5 b; gamma5 changes signs only, so they are exactly the residuals of D^dagger x = b as well.  Arguments as
+ * for ddamg_hip_solve, ddamg_hip_solve_vec and ddamg_hip_solve_device, refused alike. */
+int ddamg_hip_solve_dagger(ddamg_hip_ctx* ctx, double* x_lex, const double* b_lex, double tol,
+                           int* iterations, int* coarse_iterations, double* relres);
+int ddamg_hip_solve_dagger_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                               int* iterations, int* coarse_iterations, double* relres);
+int ddamg_hip_solve_dagger_device(ddamg_hip_ctx* ctx, double* x_dev_lex, const double* b_dev_lex, double tol,
+                                  int* iterations, int* coarse_iterations, double* relres);
+/* D^dagger D x = b (the pseudofermion heat-bath and force solves of an HMC; no counterpart in the reference):  y = D^-dagger b as above,
+ * then x = D^-1 y; y never leaves the device and lives for the call only.  Both solves run to the same tol, each relative to its own
+ * right-hand side.  iterations[0], coarse_iterations[0]: the D^dagger solve; [1]: the D solve (either array may be null).
+ * relres = ||b - D^dagger D x|| / ||b||, recomputed in fp64 with the fp64 operator and its dagger: the residual of the system the
+ * caller asked for.  It is NOT promised to be below tol: the error of the first solve passes through D^-1, so relres carries the
+ * condition of D^dagger.  ddamg_hip_residual_history is that of the second solve. */
+int ddamg_hip_solve_squared(ddamg_hip_ctx* ctx, double* x_lex, const double* b_lex, double tol,
+                            int iterations[2], int coarse_iterations[2], double* relres);
+int ddamg_hip_solve_squared_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                                int iterations[2], int coarse_iterations[2], double* relres);
+int ddamg_hip_solve_squared_device(ddamg_hip_ctx* ctx, double* x_dev_lex, const double* b_dev_lex, double tol,
+                                   int iterations[2], int coarse_iterations[2], double* relres);
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES) */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
 
