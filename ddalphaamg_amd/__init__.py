@@ -6,7 +6,7 @@ orchestration, sources in ``csrc/``, interface in ``include/ddamg_hip.h`` and th
 for tests and benchmarks.  There is no CPU fallback: loading fails loudly if the library is
 missing, and every compute entry point fails if no HIP device is visible.
 """
-from .api import (Params, Context, Vector, DDAMGError, load_library, library_path,
+from .api import (Params, Context, Vector, Chrono, DDAMGError, load_library, library_path,
                   declared_symbols)
 
-__all__ = ["Params", "Context", "Vector", "DDAMGError", "load_library", "library_path", "declared_symbols"]
+__all__ = ["Params", "Context", "Vector", "Chrono", "DDAMGError", "load_library", "library_path", "declared_symbols"]

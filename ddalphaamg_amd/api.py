@@ -79,6 +79,7 @@ def load_library():
     lib = ctypes.CDLL(_LIBNAME)
     vp = ctypes.c_void_p
     dp = ctypes.POINTER(ctypes.c_double)
+    ip = ctypes.POINTER(ctypes.c_int)
     lib.ddamg_hip_last_error.restype = ctypes.c_char_p
     lib.ddamg_hip_comm_stats.restype = ctypes.c_char_p
     lib.ddamg_hip_comm_stats.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -149,6 +150,19 @@ def load_library():
         "ddamg_hip_solve_squared": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
         "ddamg_hip_solve_squared_vec": [vp, vp, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
         "ddamg_hip_solve_squared_device": [vp, dp, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), dp],
+        "ddamg_hip_solve_guess": [vp, ctypes.c_int, dp, dp, ctypes.c_double, ip, ip, dp, dp],
+        "ddamg_hip_solve_guess_vec": [vp, ctypes.c_int, vp, vp, ctypes.c_double, ip, ip, dp, dp],
+        "ddamg_hip_solve_guess_device": [vp, ctypes.c_int, dp, dp, ctypes.c_double, ip, ip, dp, dp],
+        "ddamg_hip_chrono_create": [vp, ctypes.c_int, ctypes.POINTER(vp)],
+        "ddamg_hip_chrono_destroy": [vp, vp],
+        "ddamg_hip_chrono_reset": [vp, vp],
+        "ddamg_hip_chrono_count": [vp, vp, ip],
+        "ddamg_hip_chrono_push_vec": [vp, vp, vp],
+        "ddamg_hip_chrono_guess_vec": [vp, vp, ctypes.c_int, vp, vp, ip, dp],
+        "ddamg_hip_solve_chrono_vec": [vp, vp, ctypes.c_int, vp, vp, ctypes.c_double, ip, ip, dp, dp],
+        "ddamg_hip_solve_chrono_device": [vp, vp, ctypes.c_int, dp, dp, ctypes.c_double, ip, ip, dp, dp],
+        "ddamg_hip_solve_squared_chrono_vec": [vp, vp, vp, vp, vp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_solve_squared_chrono_device": [vp, vp, vp, dp, dp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -429,6 +443,32 @@ class Vector:
     def free(self):
         if self._h:
             self.ctx._lib.ddamg_hip_vec_destroy(self.ctx._h, self._h)
+            self._h = ctypes.c_void_p()
+
+
+class Chrono:
+    """Mirror of ddamg_hip_chrono: the last `depth` solutions of a context, for the guess of the next solve; freed before the context"""
+
+    def __init__(self, ctx, depth):
+        self.ctx, self.depth = ctx, depth
+        self._h = ctypes.c_void_p()
+        _check(ctx._lib.ddamg_hip_chrono_create(ctx._h, int(depth), ctypes.byref(self._h)))
+
+    def push(self, x):
+        self.ctx.chrono_push_vec(self, x)
+
+    def guess(self, x0, b, system=0):
+        return self.ctx.chrono_guess_vec(self, x0, b, system)
+
+    def reset(self):
+        self.ctx.chrono_reset(self)
+
+    def count(self):
+        return self.ctx.chrono_count(self)
+
+    def free(self):
+        if self._h:
+            _check(self.ctx._lib.ddamg_hip_chrono_destroy(self.ctx._h, self._h))
             self._h = ctypes.c_void_p()
 
 
@@ -746,6 +786,82 @@ class Context:
 
     def solve_squared_device(self, x_dev_lex, b_dev_lex, tol=0.0):
         return self._solve_dev("solve_squared_device", x_dev_lex, b_dev_lex, tol, squared=True)
+
+    # ---- solves from a starting vector; the guess extrapolated from past solutions (Chrono) ----
+    # system: 0 solves D x = b, 1 solves D^dagger x = b
+    def _guess_call(self, name, head, x, b, tol):
+        """`ddamg_hip_<name>`(ctx, *head, x, b, tol, ...); returns (iterations, coarse_iterations, relres, guess_relres)"""
+        it = ctypes.c_int(0); ci = ctypes.c_int(0); rr = ctypes.c_double(0); gr = ctypes.c_double(0)
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, *head, x, b, float(tol), ctypes.byref(it), ctypes.byref(ci), ctypes.byref(rr),
+                                                       ctypes.byref(gr)))
+        return it.value, ci.value, rr.value, gr.value
+
+    def solve_guess(self, x0_lex, b_lex, tol=0.0, system=0):
+        """the solve from the guess x0_lex (not written); returns (x_lex, iterations, coarse_iterations, relres = ||b - A x|| / ||b||,
+        guess_relres = ||b - A x0|| / ||b||)"""
+        b = np.ascontiguousarray(b_lex, dtype=np.float64)
+        x = np.array(x0_lex, dtype=np.float64, order="C")
+        if b.size != self.volume(0) * 24 or x.size != b.size:
+            raise DDAMGError("solve_guess: guess and right-hand side must hold V*12 complex numbers")
+        return (x,) + self._guess_call("solve_guess", (int(system),), _dp(x), _dp(b), tol)
+
+    def solve_guess_vec(self, x, b, tol=0.0, system=0):
+        """x: the guess on entry, the solution on return"""
+        return self._guess_call("solve_guess_vec", (int(system),), x._h, b._h, tol)
+
+    def solve_guess_device(self, x_dev_lex, b_dev_lex, tol=0.0, system=0):
+        n = self.volume(0) * 24
+        return self._guess_call("solve_guess_device", (int(system),), _dev(x_dev_lex, n, "solve_guess_device"), _dev(b_dev_lex, n, "solve_guess_device"), tol)
+
+    def chrono_create(self, depth):
+        """a store of the last `depth` solutions (1..8): a Chrono"""
+        return Chrono(self, depth)
+
+    def chrono_destroy(self, h):
+        h.free()
+
+    def chrono_reset(self, h):
+        _check(self._lib.ddamg_hip_chrono_reset(self._h, h._h))
+
+    def chrono_count(self, h):
+        n = ctypes.c_int(0)
+        _check(self._lib.ddamg_hip_chrono_count(self._h, h._h, ctypes.byref(n)))
+        return n.value
+
+    def chrono_push_vec(self, h, x):
+        _check(self._lib.ddamg_hip_chrono_push_vec(self._h, h._h, x._h))
+
+    def chrono_guess_vec(self, h, x0, b, system=0):
+        """x0 = the combination of the stored vectors with the least residual for the operator that is set now; returns (vectors
+        that entered it, predicted ||b - A x0|| / ||b||)"""
+        kept = ctypes.c_int(0); pr = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_chrono_guess_vec(self._h, h._h, int(system), x0._h, b._h, ctypes.byref(kept), ctypes.byref(pr)))
+        return kept.value, pr.value
+
+    def solve_chrono_vec(self, h, x, b, tol=0.0, system=0):
+        """guess from the store, solve from it, push the solution; returns as solve_guess_vec"""
+        return self._guess_call("solve_chrono_vec", (h._h, int(system)), x._h, b._h, tol)
+
+    def solve_chrono_device(self, h, x_dev_lex, b_dev_lex, tol=0.0, system=0):
+        n = self.volume(0) * 24
+        return self._guess_call("solve_chrono_device", (h._h, int(system)), _dev(x_dev_lex, n, "solve_chrono_device"),
+                                _dev(b_dev_lex, n, "solve_chrono_device"), tol)
+
+    def _squared_chrono_call(self, name, hy, hx, x, b, tol):
+        it = (ctypes.c_int * 2)(); ci = (ctypes.c_int * 2)(); rr = ctypes.c_double(0)
+        stores = [h._h if h is not None else None for h in (hy, hx)]
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, *stores, x, b, float(tol), it, ci, ctypes.byref(rr)))
+        return (it[0], it[1]), (ci[0], ci[1]), rr.value
+
+    def solve_squared_chrono_vec(self, hy, hx, x, b, tol=0.0):
+        """D^dagger D x = b, the D^dagger solve from the store hy, the D solve from hx (either may be None: a zero guess); returns as
+        solve_squared_vec"""
+        return self._squared_chrono_call("solve_squared_chrono_vec", hy, hx, x._h, b._h, tol)
+
+    def solve_squared_chrono_device(self, hy, hx, x_dev_lex, b_dev_lex, tol=0.0):
+        n = self.volume(0) * 24
+        return self._squared_chrono_call("solve_squared_chrono_device", hy, hx, _dev(x_dev_lex, n, "solve_squared_chrono_device"),
+                                         _dev(b_dev_lex, n, "solve_squared_chrono_device"), tol)
 
     def preconditioner(self, in_lex):
         a = np.ascontiguousarray(in_lex, dtype=np.float64)

@@ -1,18 +1,8 @@
 // blas.hip -- see blas.h.  Bandwidth-bound streaming kernels: 16-byte accesses, grid-stride,
 // fp64 accumulation, wave64 shuffles + LDS for the block reduction, two-stage deterministic sums.
-#include "blas.h"
+#include "blas_device.h"
 
 namespace ddamg {
-
-static constexpr int BLK = 256;
-static constexpr int MAX_GRID = 2048;  // 256 CUs x 8 blocks (guide: cap memory-bound grids, grid-stride the rest)
-
-static inline int grid_for(size_t nchunks) {
-  size_t g = (nchunks + BLK - 1) / BLK;
-  if (g < 1) g = 1;
-  if (g > (size_t)MAX_GRID) g = MAX_GRID;
-  return (int)g;
-}
 
 void ReduceWork::init(int max_m_) {
   max_m = max_m_; max_blocks = MAX_GRID;
@@ -56,33 +46,6 @@ void wait_published(ReduceWork& rw, hipStream_t st) {
     }
   }
 }
-
-// ---- chunk addressing --------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ size_t chunk_addr(const View& v, size_t c) {
-  constexpr int CH = Chunk<T>::CH;
-  if (v.rows == 1) return v.off + c * CH;
-  const size_t cpr = v.len / CH;
-  const size_t r = c / cpr;
-  return v.off + r * v.stride + (c - r * cpr) * CH;
-}
-template <typename T> __device__ __forceinline__ typename Chunk<T>::vec ldv(const T* p) { return *reinterpret_cast<const typename Chunk<T>::vec*>(p); }
-// read-once stream (Krylov basis vectors of the fine level): non-temporal, so that it does not displace reusable lines
-template <typename T, bool NT> __device__ __forceinline__ typename Chunk<T>::vec ldv_stream(const T* p) {
-  if constexpr (!NT) return ldv<T>(p);
-  else {
-    constexpr int CH = Chunk<T>::CH;
-    typedef T vecn __attribute__((ext_vector_type(CH)));
-    vecn w = __builtin_nontemporal_load(reinterpret_cast<const vecn*>(p));
-    typename Chunk<T>::vec v;
-    v.x = w[0]; v.y = w[1];
-    if constexpr (CH == 4) { v.z = w[2]; v.w = w[3]; }
-    return v;
-  }
-}
-// vectors above this size cannot live in the caches anyway
-static inline bool stream_sized(const View& v, size_t elem) { return v.total() * elem > ((size_t)32 << 20); }
-template <typename T> __device__ __forceinline__ void stv(T* p, typename Chunk<T>::vec x) { *reinterpret_cast<typename Chunk<T>::vec*>(p) = x; }
 
 // complex pair views of a chunk
 __device__ __forceinline__ void unpack(const float4& v, double (&re)[2], double (&im)[2]) { re[0] = v.x; im[0] = v.y; re[1] = v.z; im[1] = v.w; }
@@ -252,28 +215,6 @@ void vec_multi_axpy_f32basis(double* w, const float* X, size_t xstride, int m, c
 }
 
 // ---- reductions -----------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-  return x;
-}
-// block sum of NV values per thread; result valid in thread 0
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&val)[NV], double* lds /* [NV*4] */) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    double s = wave_sum(val[k]);
-    if (lane == 0) lds[k * 4 + wv] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; k++) val[k] = lds[k * 4] + lds[k * 4 + 1] + lds[k * 4 + 2] + lds[k * 4 + 3];
-  }
-  __syncthreads();
-}
-
 static constexpr int DOT_TILE = 4;
 // partial[(blockIdx.x)*(2*mtot) + 2*i..] for i in tile blockIdx.y
 template <typename T, bool NT>
@@ -322,6 +263,12 @@ __global__ __launch_bounds__(BLK) void final_sum_kernel(const double* __restrict
   for (int b = threadIdx.x; b < nblocks; b += BLK) s[0] += partial[(size_t)b * nval + k];
   block_sum<1>(s, lds);
   if (threadIdx.x == 0) out[k] = (sqrt_first && k == 0) ? sqrt(s[0]) : s[0];
+}
+
+void sum_partials(ReduceWork& rw, int nblocks, int nval, double* d_out, hipStream_t st) {
+  hipLaunchKernelGGL(final_sum_kernel, dim3(nval), dim3(BLK), 0, st, rw.d_partial, nblocks, nval, d_out, 0);
+  DDAMG_HIP_CHECK(hipGetLastError());
+  if (rw.comm) comm_allreduce(rw.comm, d_out, nval, st);
 }
 
 __global__ void sqrt_inplace_kernel(double* x) { x[0] = sqrt(x[0]); }

@@ -20,6 +20,18 @@ struct ddamg_hip_vec {
   ddamg::DeviceBuffer<char> data;
 };
 
+// a store of past solutions (ddamg_hip_chrono_*, solver.cpp): fine fp64 vectors in the solver's layout, n reals each
+struct ddamg_hip_chrono {
+  const ddamg_hip_ctx* owner = nullptr;
+  int depth = 0, count = 0, next = 0;      // a ring: slot `next` takes the next push, the newest vector is in slot next - 1
+  size_t n = 0;
+  ddamg::DeviceBuffer<double> V;           // [depth][n]
+  // workspace of a guess, from the first one on: the orthonormalised images Q = A V, their companions W (the same operations on
+  // V), and the predicted residual
+  ddamg::DeviceBuffer<double> Q, W, r;
+  double* slot(int age) const { return V + (size_t)((next - 1 - age + 2 * depth) % depth) * n; }   // age 0: the newest
+};
+
 namespace ddamg {
 
 struct Level {

@@ -3,6 +3,7 @@
 // fgmres_double + preconditioner (mixed precision 1) src/linsolve_generic.c:219-413, src/preconditioner.c:25-69.
 #include <chrono>
 #include "capi_common.h"
+#include "chrono.h"
 #include <cstring>
 #include <cstdio>
 
@@ -682,6 +683,19 @@ static auto store_dev(ddamg_hip_ctx* c, double* v, bool g5 = false) {
   };
 }
 
+// ||b - D^dagger D x|| / ||b|| in fp64: load_b(dst) fills the plain b; y and t are workspace
+template <typename LoadB>
+static double squared_residual(ddamg_hip_ctx* c, const double* x, LoadB load_b, double* y, double* t) {
+  const View all = whole((size_t)24 * c->levels[0]->geom.V);
+  ReduceWork& rw = blas_rw(c);
+  c->fop64.apply(t, x, c->stream);
+  c->fop64.apply_dagger(y, t, c->stream);
+  load_b(t);
+  const double nb = host_norm<double>(t, all, rw, c->stream);
+  vec_minus<double>(t, t, y, all, c->stream);
+  return nb > 0 ? host_norm<double>(t, all, rw, c->stream) / nb : 0.0;
+}
+
 // D^dagger D x = b by two solves through the hierarchy of D: y = gamma5 D^-1 gamma5 b (the signs in the callbacks load_g5b and, here,
 // in the store of y), then x = D^-1 y.  y and the residual's workspace live for this call only; load_b(dst) fills the plain b once more
 // for the residual of the system the caller asked for, ||b - D^dagger D x|| / ||b||, in fp64.
@@ -689,20 +703,13 @@ template <typename LoadG5B, typename LoadB, typename StoreX>
 static void solve_squared_core(ddamg_hip_ctx* c, double tol, LoadG5B load_g5b, LoadB load_b, StoreX store_x, int* iterations, int* coarse_iterations,
                                double* relres) {
   const size_t n = (size_t)24 * c->levels[0]->geom.V;
-  const View all = whole(n);
   DeviceBuffer<double> y, t;
   y.alloc(n);
   t.alloc(n);
   solve_core(c, tol, load_g5b, store_dev(c, y, true), iterations, coarse_iterations, nullptr);
   double rr = 0;
   solve_core(c, tol, load_dev(c, y), [&](const double* x) {
-    ReduceWork& rw = blas_rw(c);
-    c->fop64.apply(t, x, c->stream);
-    c->fop64.apply_dagger(y, t, c->stream);
-    load_b(t);
-    const double nb = host_norm<double>(t, all, rw, c->stream);
-    vec_minus<double>(t, t, y, all, c->stream);
-    rr = nb > 0 ? host_norm<double>(t, all, rw, c->stream) / nb : 0.0;
+    rr = squared_residual(c, x, load_b, y, t);
     store_x(x);
   }, iterations ? iterations + 1 : nullptr, coarse_iterations ? coarse_iterations + 1 : nullptr, nullptr);
   c->last_relres = rr;
@@ -717,7 +724,312 @@ static void require_device_pair(ddamg_hip_ctx* c, double* out, const double* in,
   ddamg_require_disjoint(out, in, nb, name);
 }
 
+// ---- solves from a starting vector, and the guess extrapolated from past solutions (chrono.h) -----------------------------------
+static void require_system(int system) {
+  DDAMG_REQUIRE(system == DDAMG_HIP_SYSTEM_D || system == DDAMG_HIP_SYSTEM_DDAGGER, "system: 0 (D x = b) or 1 (D^dagger x = b)");
+}
+static void apply_system(ddamg_hip_ctx* c, int system, double* out, const double* in) {
+  if (system == DDAMG_HIP_SYSTEM_DDAGGER) c->fop64.apply_dagger(out, in, c->stream); else c->fop64.apply(out, in, c->stream);
+}
+// r = b - y (r == b allowed); returns (||b||, ||r||), both from the one reduction of chrono_residual
+static std::pair<double, double> residual_norms(ddamg_hip_ctx* c, double* r, const double* b, const double* y) {
+  ReduceWork& rw = blas_rw(c);
+  chrono_residual(r, b, y, whole((size_t)24 * c->levels[0]->geom.V), rw, rw.d_result, c->stream);
+  publish_to_host(rw.d_result, 2, rw, c->stream);
+  wait_published(rw, c->stream);
+  return {std::sqrt(rw.h_result[0]), std::sqrt(rw.h_result[1])};
+}
+
+// A x = b from a guess, A = D or D^dagger by `system`, in residual-correction form through solve_core: r0 = b - A x0, A e = r0 from
+// zero to tol ||b|| / ||r0||, x = x0 + e.  load_x(dst) fills the guess, load_b(dst) the right-hand side (twice: once more for the
+// residual of the x that is returned), store_x(src) takes the solution; all three in the solver's layout.  zero_fallback: a guess
+// that is no better than zero is replaced by zero.
+template <typename LoadX, typename LoadB, typename StoreX>
+static void solve_guess_core(ddamg_hip_ctx* c, int system, double tol, LoadX load_x, LoadB load_b, StoreX store_x, bool zero_fallback, int* iterations,
+                             int* coarse_iterations, double* relres, double* guess_relres) {
+  require_system(system);
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
+  DDAMG_REQUIRE(c->par.method <= 0 || c->par.method == 5 || c->setup_done, "setup has not been run");
+  const size_t n = (size_t)24 * c->levels[0]->geom.V;
+  const View all = whole(n);
+  const bool g5 = system == DDAMG_HIP_SYSTEM_DDAGGER;
+  if (!(tol > 0)) tol = c->par.tol;
+  DeviceBuffer<double> x, r, t;
+  for (DeviceBuffer<double>* p : {&x, &r, &t}) p->alloc(n);
+  load_x(x);
+  apply_system(c, system, t, x);
+  load_b(r);
+  auto [nb, nr] = residual_norms(c, r, r, t);
+  if (zero_fallback && nb > 0 && !(nr < nb)) {
+    vec_zero<double>(x, all, c->stream);
+    load_b(r);
+    nr = nb;
+  }
+  int it = 0, cit = 0;
+  double rr = 0, gr = 0;
+  c->last_history.clear();
+  if (!(nb > 0)) {
+    vec_zero<double>(x, all, c->stream);
+  } else {
+    gr = nr / nb;
+    if (nr <= tol * nb) {
+      rr = gr;
+    } else {
+      // the correction of D^dagger through the gamma5 signs of the D^dagger solves; nb / nr first: a zero guess gives tol * 1
+      solve_core(c, tol * (nb / nr), load_dev(c, r, g5), store_dev(c, t, g5), &it, &cit, nullptr);
+      vec_plus<double>(x, x, t, all, c->stream);
+      apply_system(c, system, t, x);
+      load_b(r);
+      const auto [nb1, nr1] = residual_norms(c, r, r, t);
+      rr = nr1 / nb1;
+    }
+  }
+  store_x(x);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->last_iter = it; c->last_coarse_iter = cit; c->last_relres = rr;
+  if (iterations) *iterations = it;
+  if (coarse_iterations) *coarse_iterations = cit;
+  if (relres) *relres = rr;
+  if (guess_relres) *guess_relres = gr;
+}
+
+static void require_store(const ddamg_hip_ctx* c, const ddamg_hip_chrono* h) {
+  DDAMG_REQUIRE(h, "null argument");
+  DDAMG_REQUIRE(h->owner == c, "the store belongs to another context");
+}
+static void chrono_push(ddamg_hip_ctx* c, ddamg_hip_chrono* h, const double* x) {
+  vec_copy<double>(h->V + (size_t)h->next * h->n, x, whole(h->n), c->stream);
+  h->next = (h->next + 1) % h->depth;
+  h->count = std::min(h->count + 1, h->depth);
+}
+
+// x0 = the combination of the stored vectors that minimises ||b - A x0|| (x0 and b in the solver's layout, apart): the images
+// q = A v_j, newest first, orthonormalised by classical Gram-Schmidt applied twice, the same operations carried on the v_j; an image
+// that the projection takes below 1e-12 of its norm (rounding noise is k 2^-53, the smallest ratio of a useful history about 1e-7) is
+// dropped.  Then c = Q^H b, x0 = W c, r = b - Q c.  One read-back per column.
+static void chrono_guess(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int system, double* x0, const double* b, int* kept, double* predicted_relres) {
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
+  const size_t n = h->n;
+  const View all = whole(n);
+  hipStream_t st = c->stream;
+  ReduceWork& rw = blas_rw(c);
+  double* norms = rw.d_result + 2 * CHRONO_MAX;     // behind the coefficients of vec_multi_dot
+  auto read_norms = [&] { publish_to_host(norms, 2, rw, st); wait_published(rw, st); };
+  if (h->count && !h->Q.get()) {
+    h->Q.alloc((size_t)h->depth * n);
+    h->W.alloc((size_t)h->depth * n);
+    h->r.alloc(n);
+  }
+  int m = 0;
+  for (int age = 0; age < h->count; age++) {
+    double *q = h->Q + (size_t)m * n, *w = h->W + (size_t)m * n;
+    apply_system(c, system, q, h->slot(age));
+    vec_copy<double>(w, h->slot(age), all, st);
+    vec_norm<double>(q, all, rw, norms, st);
+    for (int pass = 0; pass < 2 && m > 0; pass++) {
+      vec_multi_dot<double>(h->Q, n, m, q, all, rw, rw.d_result, st);
+      chrono_project_pair(q, h->Q, w, h->W, n, m, rw.d_result, all, st);
+    }
+    vec_norm<double>(q, all, rw, norms + 1, st);
+    read_norms();
+    const double before = rw.h_result[0], after = rw.h_result[1];
+    if (!(after > 1e-12 * before)) continue;        // a duplicate, a zero vector, or not a number
+    vec_scale<double>(q, q, 1.0 / after, 0.0, all, st);
+    vec_scale<double>(w, w, 1.0 / after, 0.0, all, st);
+    m++;
+  }
+  double predicted = 1.0;
+  if (m == 0) {
+    vec_zero<double>(x0, all, st);
+  } else {
+    vec_multi_dot<double>(h->Q, n, m, b, all, rw, rw.d_result, st);
+    chrono_combine(x0, h->W, h->r, b, h->Q, n, m, rw.d_result, all, st);
+    vec_norm<double>(h->r, all, rw, norms, st);
+    vec_norm<double>(b, all, rw, norms + 1, st);
+    read_norms();
+    predicted = rw.h_result[1] > 0 ? rw.h_result[0] / rw.h_result[1] : 0.0;
+  }
+  DDAMG_HIP_CHECK(hipStreamSynchronize(st));
+  if (kept) *kept = m;
+  if (predicted_relres) *predicted_relres = predicted;
+}
+
+// the guess from the store h (null: zero), the solve from it, the solution pushed
+template <typename LoadB, typename StoreX>
+static void solve_chrono_core(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int system, double tol, LoadB load_b, StoreX store_x, int* iterations,
+                              int* coarse_iterations, double* relres, double* guess_relres) {
+  require_system(system);
+  if (h) require_store(c, h);
+  const size_t n = (size_t)24 * c->levels[0]->geom.V;
+  solve_guess_core(c, system, tol, [&](double* x) {
+    if (!h || h->count == 0) { vec_zero<double>(x, whole(n), c->stream); return; }
+    DeviceBuffer<double> b;
+    b.alloc(n);
+    load_b(b);
+    chrono_guess(c, h, system, x, b, nullptr, nullptr);
+  }, load_b, [&](const double* x) {
+    store_x(x);
+    if (h) chrono_push(c, h, x);
+  }, true, iterations, coarse_iterations, relres, guess_relres);
+}
+
+// D^dagger D x = b as solve_squared_core, each of the two solves from the guess of its own store
+template <typename LoadB, typename StoreX>
+static void solve_squared_chrono_core(ddamg_hip_ctx* c, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, double tol, LoadB load_b, StoreX store_x,
+                                      int* iterations, int* coarse_iterations, double* relres) {
+  const size_t n = (size_t)24 * c->levels[0]->geom.V;
+  for (const ddamg_hip_chrono* h : {hy, hx})
+    if (h) require_store(c, h);
+  DeviceBuffer<double> y, t, u;
+  for (DeviceBuffer<double>* p : {&y, &t, &u}) p->alloc(n);
+  solve_chrono_core(c, hy, DDAMG_HIP_SYSTEM_DDAGGER, tol, load_b, store_dev(c, y), iterations, coarse_iterations, nullptr, nullptr);
+  double rr = 0;
+  solve_chrono_core(c, hx, DDAMG_HIP_SYSTEM_D, tol, load_dev(c, y), [&](const double* x) {
+    rr = squared_residual(c, x, load_b, u, t);
+    store_x(x);
+  }, iterations ? iterations + 1 : nullptr, coarse_iterations ? coarse_iterations + 1 : nullptr, nullptr, nullptr);
+  c->last_relres = rr;
+  if (relres) *relres = rr;
+}
+
 extern "C" {
+
+int ddamg_hip_solve_guess(ddamg_hip_ctx* c, int system, double* x_lex, const double* b_lex, double tol, int* iterations, int* coarse_iterations,
+                          double* relres, double* guess_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(x_lex && b_lex, "null argument");
+  double* st = c->stage(sizeof(double) * 24 * c->levels[0]->geom.V);
+  solve_guess_core(c, system, tol, load_lex(c, x_lex, st), load_lex(c, b_lex, st), store_lex(c, x_lex, st), false, iterations, coarse_iterations, relres,
+                   guess_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_guess_device(ddamg_hip_ctx* c, int system, double* x_dev_lex, const double* b_dev_lex, double tol, int* iterations,
+                                 int* coarse_iterations, double* relres, double* guess_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_guess_device");
+  solve_guess_core(c, system, tol, load_lex(c, x_dev_lex), load_lex(c, b_dev_lex), store_lex(c, x_dev_lex), false, iterations, coarse_iterations, relres,
+                   guess_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_guess_vec(ddamg_hip_ctx* c, int system, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations,
+                              int* coarse_iterations, double* relres, double* guess_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_guess_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x != b, "solve_guess_vec: the guess and the right-hand side must be two vectors");
+  solve_guess_core(c, system, tol, load_dev(c, vec_data<double>(x)), load_dev(c, vec_data<double>(b)), store_dev(c, vec_data<double>(x)), false,
+                   iterations, coarse_iterations, relres, guess_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_create(ddamg_hip_ctx* c, int depth, ddamg_hip_chrono** h) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(h, "null argument");
+  DDAMG_REQUIRE(depth >= 1 && depth <= CHRONO_MAX, "chrono_create: 1 <= depth <= 8");
+  std::unique_ptr<ddamg_hip_chrono> s(new ddamg_hip_chrono);
+  s->owner = c; s->depth = depth;
+  s->n = (size_t)24 * c->levels[0]->geom.V;
+  s->V.alloc((size_t)depth * s->n);
+  *h = s.release();
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_destroy(ddamg_hip_ctx* c, ddamg_hip_chrono* h) {
+  DDAMG_API_BEGIN
+  enter(c);
+  if (!h) return 0;
+  require_store(c, h);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  delete h;
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_reset(ddamg_hip_ctx* c, ddamg_hip_chrono* h) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  h->count = h->next = 0;
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_count(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int* n) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  DDAMG_REQUIRE(n, "null argument");
+  *n = h->count;
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_push_vec(ddamg_hip_ctx* c, ddamg_hip_chrono* h, const ddamg_hip_vec* x) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  DDAMG_REQUIRE(x, "null argument");
+  DDAMG_REQUIRE(x->level == 0 && x->precision == 64, "chrono_push_vec needs a fine-level fp64 vector");
+  chrono_push(c, h, vec_data<double>(x));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_chrono_guess_vec(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int system, ddamg_hip_vec* x0, const ddamg_hip_vec* b, int* kept,
+                               double* predicted_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  require_system(system);
+  require_solve_vecs(x0, b, "chrono_guess_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x0 != b, "chrono_guess_vec: the guess and the right-hand side must be two vectors");
+  chrono_guess(c, h, system, vec_data<double>(x0), vec_data<double>(b), kept, predicted_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_chrono_vec(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int system, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations,
+                               int* coarse_iterations, double* relres, double* guess_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  require_solve_vecs(x, b, "solve_chrono_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x != b, "solve_chrono_vec: the solution and the right-hand side must be two vectors");
+  solve_chrono_core(c, h, system, tol, load_dev(c, vec_data<double>(b)), store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres,
+                    guess_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_chrono_device(ddamg_hip_ctx* c, ddamg_hip_chrono* h, int system, double* x_dev_lex, const double* b_dev_lex, double tol,
+                                  int* iterations, int* coarse_iterations, double* relres, double* guess_relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_store(c, h);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_chrono_device");
+  solve_chrono_core(c, h, system, tol, load_lex(c, b_dev_lex), store_lex(c, x_dev_lex), iterations, coarse_iterations, relres, guess_relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_squared_chrono_vec(ddamg_hip_ctx* c, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, ddamg_hip_vec* x, const ddamg_hip_vec* b,
+                                       double tol, int iterations[2], int coarse_iterations[2], double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_squared_chrono_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x != b, "solve_squared_chrono_vec: the solution and the right-hand side must be two vectors");
+  solve_squared_chrono_core(c, hy, hx, tol, load_dev(c, vec_data<double>(b)), store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_squared_chrono_device(ddamg_hip_ctx* c, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, double* x_dev_lex, const double* b_dev_lex,
+                                          double tol, int iterations[2], int coarse_iterations[2], double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_pair(c, x_dev_lex, b_dev_lex, "ddamg_hip_solve_squared_chrono_device");
+  solve_squared_chrono_core(c, hy, hx, tol, load_lex(c, b_dev_lex), store_lex(c, x_dev_lex), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
 
 int ddamg_hip_solve(ddamg_hip_ctx* c, double* x_lex, const double* b_lex, double tol, int* iterations, int* coarse_iterations, double* relres) {
   DDAMG_API_BEGIN

@@ -28,6 +28,7 @@ extern "C" {
 
 typedef struct ddamg_hip_ctx ddamg_hip_ctx;
 typedef struct ddamg_hip_vec ddamg_hip_vec;
+typedef struct ddamg_hip_chrono ddamg_hip_chrono;   /* a store of past solutions (ddamg_hip_chrono_create) */
 
 /* Mirrors the parameters the reference reads from its .ini / dd_alpha_amg_parameters
  * (src/init.c:778-953, src/dd_alpha_amg_parameters.h:26-51).  Lattices in T,Z,Y,X order. */
@@ -352,7 +353,59 @@ int ddamg_hip_solve_squared_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddam
                                 int iterations[2], int coarse_iterations[2], double* relres);
 int ddamg_hip_solve_squared_device(ddamg_hip_ctx* ctx, double* x_dev_lex, const double* b_dev_lex, double tol,
                                    int iterations[2], int coarse_iterations[2], double* relres);
-/* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES) */
+enum { DDAMG_HIP_SYSTEM_D = 0, DDAMG_HIP_SYSTEM_DDAGGER = 1 };   /* `system` of the solves below */
+/* A solve that starts from the caller's vector (no counterpart in the reference, whose interface starts every solve from zero): x
+ * holds the guess x0 on entry and the solution on return.  system: DDAMG_HIP_SYSTEM_D solves D x = b, DDAMG_HIP_SYSTEM_DDAGGER solves
+ * D^dagger x = b; with A that operator, the call forms r0 = b - A x0 with the fp64 operator, solves A e = r0 from zero by the solver of
+ * ddamg_hip_solve (ddamg_hip_solve_dagger) to the tolerance tol ||b|| / ||r0||, and returns x = x0 + e: every `method`, every
+ * `mixed_precision` and process grids.  tol <= 0: params.tol.  Where ||r0|| <= tol ||b|| already, x stays as it is and the counts are 0.
+ * relres = ||b - A x|| / ||b|| recomputed in fp64 from the x that is returned: relative to b, not to r0.
+ * guess_relres = ||r0|| / ||b||; both norms come out of one reduction, so a zero guess gives exactly 1 and the bits of the plain solve.
+ * b = 0 gives x = 0, zero counts and zero residuals.  ddamg_hip_residual_history is that of the correction solve and so relative to
+ * ||r0||, not to ||b||.  Arguments as for ddamg_hip_solve, ddamg_hip_solve_vec and ddamg_hip_solve_device, refused alike, as is a
+ * system other than the two. */
+int ddamg_hip_solve_guess(ddamg_hip_ctx* ctx, int system, double* x_lex, const double* b_lex, double tol,
+                          int* iterations, int* coarse_iterations, double* relres, double* guess_relres);
+int ddamg_hip_solve_guess_vec(ddamg_hip_ctx* ctx, int system, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                              int* iterations, int* coarse_iterations, double* relres, double* guess_relres);
+int ddamg_hip_solve_guess_device(ddamg_hip_ctx* ctx, int system, double* x_dev_lex, const double* b_dev_lex, double tol,
+                                 int* iterations, int* coarse_iterations, double* relres, double* guess_relres);
+/* A store of the last `depth` solutions (1 <= depth <= 8) and the chronological guess from them: the combination of the stored
+ * vectors that minimises the residual of the system posed NOW (minimal residual extrapolation, Brower et al., Nucl. Phys. B 484
+ * (1997) 353; no counterpart in the reference).  The solves of a molecular-dynamics trajectory, of a Hasenbusch chain or of a mass
+ * scan are nearby systems: the operator may change between a push and a guess (ddamg_hip_shift_mass, ddamg_hip_set_gauge*), that is
+ * the point.  The store owns depth fine fp64 vectors and, from its first guess on, the workspace of a guess (2 depth + 1 more); it
+ * belongs to the context that created it, is refused by any other, and is destroyed before that context.
+ *   create / destroy / reset (forget the vectors, keep the memory) / count (vectors held);  destroy with a null store is a no-op;
+ *   push_vec: a ring, the oldest vector falls out;
+ *   guess_vec: x0 = the guess for A x = b (system as above), kept = the vectors that entered it, predicted_relres = the residual
+ *     ||b - A x0|| / ||b|| as the orthogonalisation predicts it (a prediction: the truth is guess_relres of the solve that follows).
+ *     One fp64 operator application per stored vector, newest first; the images are orthonormalised by classical Gram-Schmidt applied
+ *     twice with the same operations carried on the vectors -- the Gram matrix of the images is numerically singular exactly when the
+ *     history is good, so no normal equations -- and a vector whose image loses all but 1e-12 of its norm in the projection (a
+ *     duplicate) is left out.  An empty store gives x0 = 0, kept = 0 and predicted_relres = 1.
+ *   solve_chrono_*: the guess, ddamg_hip_solve_guess from it, and the solution pushed.  x is output only.  Where the measured
+ *     guess_relres is not finite or not below 1 the solve starts from zero instead and guess_relres is returned as 1.
+ *   solve_squared_chrono_*: D^dagger D x = b as ddamg_hip_solve_squared, the D^dagger solve with the store hy (of the intermediate
+ *     vectors y, which stay inside), the D solve with hx; either store may be null, which is a zero guess for that solve.  relres and
+ *     the two pairs of counts as for ddamg_hip_solve_squared. */
+int ddamg_hip_chrono_create(ddamg_hip_ctx* ctx, int depth, ddamg_hip_chrono** h);
+int ddamg_hip_chrono_destroy(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h);
+int ddamg_hip_chrono_reset(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h);
+int ddamg_hip_chrono_count(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h, int* n);
+int ddamg_hip_chrono_push_vec(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h, const ddamg_hip_vec* x);
+int ddamg_hip_chrono_guess_vec(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h, int system, ddamg_hip_vec* x0, const ddamg_hip_vec* b,
+                               int* kept, double* predicted_relres);
+int ddamg_hip_solve_chrono_vec(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h, int system, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                               int* iterations, int* coarse_iterations, double* relres, double* guess_relres);
+int ddamg_hip_solve_chrono_device(ddamg_hip_ctx* ctx, ddamg_hip_chrono* h, int system, double* x_dev_lex, const double* b_dev_lex, double tol,
+                                  int* iterations, int* coarse_iterations, double* relres, double* guess_relres);
+int ddamg_hip_solve_squared_chrono_vec(ddamg_hip_ctx* ctx, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, ddamg_hip_vec* x, const ddamg_hip_vec* b,
+                                       double tol, int iterations[2], int coarse_iterations[2], double* relres);
+int ddamg_hip_solve_squared_chrono_device(ddamg_hip_ctx* ctx, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, double* x_dev_lex,
+                                          const double* b_dev_lex, double tol, int iterations[2], int coarse_iterations[2], double* relres);
+/* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
+ * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
 
 /* device site ordering of a level: lex_of_site[s] = lexicographic index of device site s (the role of the
