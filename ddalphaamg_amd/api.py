@@ -92,6 +92,8 @@ def load_library():
         "ddamg_hip_set_gauge2": [vp, dp, dp, ctypes.c_int, dp],
         "ddamg_hip_set_gauge_device": [vp, dp, ctypes.c_int, dp],
         "ddamg_hip_set_gauge2_device": [vp, dp, dp, ctypes.c_int, dp],
+        "ddamg_hip_set_gauge_device_grid": [vp, dp, ctypes.c_int, dp],
+        "ddamg_hip_set_gauge2_device_grid": [vp, dp, dp, ctypes.c_int, dp],
         "ddamg_hip_ildg_to_links_device": [vp, vp, ctypes.c_int, ctypes.c_longlong, dp],
         "ddamg_hip_links_to_ildg_device": [vp, dp, ctypes.c_int, ctypes.c_longlong, vp],
         "ddamg_hip_load_ildg_conf": [vp, ctypes.c_char_p, ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_int)],
@@ -520,9 +522,27 @@ class Context:
                                                      _dev(clover_gauge_dev_lex, n, "set_gauge2_device"), int(bool(anti_pbc)), ctypes.byref(plaq)))
         return plaq.value
 
+    def set_gauge_device_grid(self, gauge_dev_lex, anti_pbc=True):
+        """set_gauge_device on any process grid: this process's links in device memory, the neighbours' one-site shell exchanged
+        device to device over the installed transport.  Collective: every process of the grid calls it.  Returns the global
+        plaquette.  On an undivided context it is set_gauge_device."""
+        plaq = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_set_gauge_device_grid(self._h, _dev(gauge_dev_lex, self.volume(0) * 72, "set_gauge_device_grid"), int(bool(anti_pbc)),
+                                                         ctypes.byref(plaq)))
+        return plaq.value
+
+    def set_gauge2_device_grid(self, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc=False):
+        """set_gauge2_device on any process grid (collective); only the clover field's shell travels"""
+        plaq = ctypes.c_double(0)
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_set_gauge2_device_grid(self._h, _dev(hopp_gauge_dev_lex, n, "set_gauge2_device_grid"),
+                                                          _dev(clover_gauge_dev_lex, n, "set_gauge2_device_grid"), int(bool(anti_pbc)), ctypes.byref(plaq)))
+        return plaq.value
+
     def load_ildg_conf(self, path, anti_pbc=True):
-        """the configuration of an ILDG file becomes the operator (file -> pinned staging -> device links -> operator on a single
-        process; read_ildg_conf + set_gauge on a process grid).  Returns (plaquette computed from the links, the file's plaquette
+        """the configuration of an ILDG file becomes the operator (file -> pinned staging -> device links -> operator; on a process
+        grid every process reads its own part that way and the neighbours' shell of links travels device to device, as in
+        set_gauge_device_grid: collective, a transport must be installed).  Returns (plaquette computed from the links, the file's plaquette
         times three or None if it has none), both in [0,3]"""
         plaq = ctypes.c_double(0); fplaq = ctypes.c_double(0); has = ctypes.c_int(0)
         _check(self._lib.ddamg_hip_load_ildg_conf(self._h, os.fsencode(path), int(bool(anti_pbc)), ctypes.byref(plaq), ctypes.byref(fplaq),
@@ -543,8 +563,9 @@ class Context:
         return raw_dev
 
     def clover_kernel_time(self, gauge_dev_lex, which, reps=10):
-        """(milliseconds per launch, plaquette) of the field-strength kernel (which = 0), the host path's clover kernel (1) or
-        the field-strength, assembly and plaquette-sum kernels together (2) on links in device memory; a measurement"""
+        """(milliseconds per launch, plaquette) of the field-strength kernel (which = 0), the host path's clover kernel (1), the
+        field-strength, assembly and plaquette-sum kernels together (2) or, on a process grid, the field-strength kernel on the
+        extended lattice (3) on links in device memory; a measurement"""
         ms = ctypes.c_float(0); plaq = ctypes.c_double(0)
         _check(self._lib.ddamg_hip_clover_kernel_time(self._h, _dev(gauge_dev_lex, self.volume(0) * 72, "clover_kernel_time"), int(which), int(reps),
                                                       ctypes.byref(ms), ctypes.byref(plaq)))

@@ -4,6 +4,7 @@
 #include "storage_refusal.h"
 #include "ildg_device.h"
 #include "io_common.h"
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <fcntl.h>
@@ -229,14 +230,19 @@ static void ensure_host_mirror(ddamg_hip_ctx* c) {
 }
 
 // links in device memory -> both fine operators, nothing through the host: what ddamg_hip_set_gauge_device / _set_gauge2_device
-// run on the caller's arrays and ddamg_hip_load_ildg_conf on its own
-static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette) {
+// and their _grid forms run on the caller's arrays and ddamg_hip_load_ildg_conf on its own.  On a process grid the neighbours'
+// shell of links travels device to device over the transport (collective) and the plaquette is the global one.
+static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
   const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed() || c->comm != nullptr, (std::string(name) + " on a process grid fetches the neighbours' links: install a transport first "
+                                                         "(ddamg_hip_comm_init_rccl / ddamg_hip_comm_init_host / ddamg_hip_comm_init_mpi)").c_str());
   const size_t V = g.V;
   DeviceBuffer<double> dD, dC;   // the staging arrays of FineOp::upload, filled on the device
   dD.alloc(72 * V);
   dC.alloc(84 * V);
-  const double pl = gauge_to_operator_resident(g.L, hopp_dev, clover_dev, anti_pbc, c->par.m0, c->par.csw, dD, dC, c->stream);
+  const double pl = g.distributed()
+                        ? gauge_to_operator_resident_grid(g, c->comm, hopp_dev, clover_dev, anti_pbc, c->par.m0, c->par.csw, dD, dC, c->stream)
+                        : gauge_to_operator_resident(g.L, hopp_dev, clover_dev, anti_pbc, c->par.m0, c->par.csw, dD, dC, c->stream);
   if (plaquette) *plaquette = pl;
   drop_clover_base(c);      // a new operator is unscaled
   c->fop64.upload_staged(g, dD, dC, c->knobs, c->stream);
@@ -249,15 +255,17 @@ static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const do
   operator_replaced(c);
 }
 
-static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name) {
+// grid: the _grid entry points, which take any context; the others refuse a process grid, where the call would be collective
+static void set_gauge_resident(ddamg_hip_ctx* c, const double* hopp_dev, const double* clover_dev, int anti_pbc, double* plaquette, const char* name, bool grid) {
   enter(c);
   const Geometry& g = c->levels[0]->geom;
-  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": links in device memory are taken on a single process only, because the clover term on a "
-                                   "process grid needs the neighbours' links: use ddamg_hip_set_gauge there").c_str());
+  DDAMG_REQUIRE(grid || !g.distributed(), (std::string(name) + ": this entry point takes links in device memory on a single process only, because the clover "
+                                           "term on a process grid needs the neighbours' links: use ddamg_hip_set_gauge_device_grid / "
+                                           "ddamg_hip_set_gauge2_device_grid there (collective; device to device), or ddamg_hip_set_gauge").c_str());
   const size_t V = g.V;
   ddamg_require_device_array(c, hopp_dev, sizeof(double) * 72 * V, name);
   if (clover_dev != hopp_dev) ddamg_require_device_array(c, clover_dev, sizeof(double) * 72 * V, name);
-  links_to_operator(c, hopp_dev, clover_dev, anti_pbc, plaquette);
+  links_to_operator(c, hopp_dev, clover_dev, anti_pbc, plaquette, name);
 }
 
 // gauge field -> operator fields in the reference's storage (dirac_setup, src/dirac.c:60-168), no upload
@@ -291,14 +299,26 @@ int ddamg_hip_set_gauge(ddamg_hip_ctx* c, const double* gauge_lex, int anti_pbc,
 
 int ddamg_hip_set_gauge_device(ddamg_hip_ctx* c, const double* gauge_dev_lex, int anti_pbc, double* plaquette) {
   DDAMG_API_BEGIN
-  set_gauge_resident(c, gauge_dev_lex, gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge_device");
+  set_gauge_resident(c, gauge_dev_lex, gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge_device", false);
   DDAMG_API_END
 }
 
 int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* c, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette) {
   // D from the first field, clover term and plaquette from the second, one layout pass
   DDAMG_API_BEGIN
-  set_gauge_resident(c, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge2_device");
+  set_gauge_resident(c, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge2_device", false);
+  DDAMG_API_END
+}
+
+int ddamg_hip_set_gauge_device_grid(ddamg_hip_ctx* c, const double* gauge_dev_lex, int anti_pbc, double* plaquette) {
+  DDAMG_API_BEGIN
+  set_gauge_resident(c, gauge_dev_lex, gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge_device_grid", true);
+  DDAMG_API_END
+}
+
+int ddamg_hip_set_gauge2_device_grid(ddamg_hip_ctx* c, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette) {
+  DDAMG_API_BEGIN
+  set_gauge_resident(c, hopp_gauge_dev_lex, clover_gauge_dev_lex, anti_pbc, plaquette, "ddamg_hip_set_gauge2_device_grid", true);
   DDAMG_API_END
 }
 
@@ -351,8 +371,12 @@ struct File {
 
 // file -> pinned staging -> device: the record of `info` as links [V][4][9] complex fp64 in `links`.  The pread of chunk k + 1
 // runs while the copy and the kernel of chunk k are on the stream; a pinned chunk is read into again once the copy out of it
-// (its event) is done, the one raw chunk on the device is reused in stream order.
-static void ildg_record_to_links(ddamg_hip_ctx* c, const char* path, const struct ddamg_hip_lime_info& info, size_t V, double* links) {
+// (its event) is done, the one raw chunk on the device is reused in stream order.  `part`: this process's part of the file's
+// lattice (V = part.Vloc); on a process grid a chunk is gathered from the runs of L[3] sites that ddamg_hip_read_ildg_conf reads as
+// rows, in its order, so that the chunk holds local lexicographic order.
+static void ildg_record_to_links(ddamg_hip_ctx* c, const char* path, const struct ddamg_hip_lime_info& info, const ddamg_io::Part& part, double* links) {
+  const size_t V = part.Vloc;
+  const bool whole = part.Vloc == part.Vglob;
   const size_t site_bytes = (size_t)72 * (info.precision / 8);
   size_t chunk_sites = ((size_t)64 << 20) / site_bytes;
   if (c->knobs.ildg_chunk_sites.set && c->knobs.ildg_chunk_sites.value > 0) chunk_sites = (size_t)c->knobs.ildg_chunk_sites.value;
@@ -372,8 +396,18 @@ static void ildg_record_to_links(ddamg_hip_ctx* c, const char* path, const struc
       const size_t n = V - first < chunk_sites ? V - first : chunk_sites;
       const int b = (int)(k & 1);
       if (in_flight[b]) DDAMG_HIP_CHECK(hipEventSynchronize(copied[b].e));
-      if (ddamg_io::pread_all(file.fd, pinned[b].get(), n * site_bytes, (off_t)(info.data_offset + (long long)(first * site_bytes))))
-        throw std::runtime_error(std::string("LIME file '") + path + "' ends early");
+      int rc = 0;
+      if (whole) rc = ddamg_io::pread_all(file.fd, pinned[b].get(), n * site_bytes, (off_t)(info.data_offset + (long long)(first * site_bytes)));
+      else
+        for (size_t s = first; s < first + n && !rc;) {   // the pieces of rows inside this chunk
+          const size_t row = s / part.L[3], x = s - row * part.L[3];
+          const size_t len = std::min((size_t)part.L[3] - x, first + n - s);
+          const size_t y = row % part.L[2], z = (row / part.L[2]) % part.L[1], t = row / ((size_t)part.L[2] * part.L[1]);
+          const size_t gsite = (((part.O[0] + t) * part.G[1] + (part.O[1] + z)) * part.G[2] + (part.O[2] + y)) * part.G[3] + part.O[3] + x;
+          rc = ddamg_io::pread_all(file.fd, pinned[b].get() + (s - first) * site_bytes, len * site_bytes, (off_t)(info.data_offset + (long long)(gsite * site_bytes)));
+          s += len;
+        }
+      if (rc) throw std::runtime_error(std::string("LIME file '") + path + "' ends early");
       DDAMG_HIP_CHECK(hipMemcpyAsync(raw.get(), pinned[b].get(), n * site_bytes, hipMemcpyHostToDevice, c->stream));
       DDAMG_HIP_CHECK(hipEventRecord(copied[b].e, c->stream));
       in_flight[b] = true;
@@ -393,21 +427,18 @@ int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* c, const char* path, int anti_pbc, d
   const Geometry& g = c->levels[0]->geom;
   int G[4];
   for (int mu = 0; mu < 4; mu++) G[mu] = g.L[mu] * g.P[mu];
-  double file_plaq = 0; int has_plaq = 0;
-  if (g.distributed()) {
-    // this process's part through the host, then the path that fetches the neighbours' links
-    std::vector<double> U((size_t)g.V * 72);
-    if (ddamg_hip_read_ildg_conf(path, G, g.P, g.pc, U.data(), &file_plaq, &has_plaq)) throw std::runtime_error(ddamg_hip_io_last_error());
-    if (ddamg_hip_set_gauge(c, U.data(), anti_pbc, plaquette_out)) return 1;   // the message is set
-  } else {
-    struct ddamg_hip_lime_info info;
-    if (ddamg_io::ildg_checked_info(path, G, &info)) throw std::runtime_error(ddamg_hip_io_last_error());
-    file_plaq = 3.0 * info.plaquette; has_plaq = info.has_plaquette;
-    DeviceBuffer<double> links;
-    links.alloc((size_t)g.V * 72);
-    ildg_record_to_links(c, path, info, (size_t)g.V, links);
-    links_to_operator(c, links, links, anti_pbc, plaquette_out);
-  }
+  // on a process grid: this process's part of the record, then the path that fetches the neighbours' links device to device
+  DDAMG_REQUIRE(!g.distributed() || c->comm != nullptr, "ddamg_hip_load_ildg_conf on a process grid fetches the neighbours' links: install a transport first "
+                                                        "(ddamg_hip_comm_init_rccl / ddamg_hip_comm_init_host / ddamg_hip_comm_init_mpi)");
+  ddamg_io::Part part;
+  DDAMG_REQUIRE(ddamg_io::make_part(G, g.P, g.pc, part) && part.Vloc == (size_t)g.V, "load_ildg_conf: the process grid does not divide the lattice");
+  struct ddamg_hip_lime_info info;
+  if (ddamg_io::ildg_checked_info(path, G, &info)) throw std::runtime_error(ddamg_hip_io_last_error());
+  const double file_plaq = 3.0 * info.plaquette; const int has_plaq = info.has_plaquette;
+  DeviceBuffer<double> links;
+  links.alloc((size_t)g.V * 72);
+  ildg_record_to_links(c, path, info, part, links);
+  links_to_operator(c, links, links, anti_pbc, plaquette_out, "ddamg_hip_load_ildg_conf");
   if (file_plaquette_out) *file_plaquette_out = file_plaq;
   if (has_file_plaquette_out) *has_file_plaquette_out = has_plaq;
   DDAMG_API_END
@@ -418,9 +449,12 @@ int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* c, const double* gauge_dev_lex, 
   enter(c);
   DDAMG_REQUIRE(milliseconds, "null argument");
   const Geometry& g = c->levels[0]->geom;
-  DDAMG_REQUIRE(!g.distributed(), "ddamg_hip_clover_kernel_time: single process only");
+  DDAMG_REQUIRE(which == 3 ? (g.distributed() && c->comm != nullptr) : !g.distributed(),
+                "ddamg_hip_clover_kernel_time: which = 0, 1, 2 on a single process only; which = 3 (the field-strength kernel on the extended lattice) on "
+                "a process grid with a transport only");
   ddamg_require_device_array(c, gauge_dev_lex, sizeof(double) * 72 * g.V, "ddamg_hip_clover_kernel_time");
-  const double pl = clover_kernels_timed(g.L, gauge_dev_lex, c->par.m0, c->par.csw, which, reps, c->ev0, c->ev1, c->stream, milliseconds);
+  const double pl = which == 3 ? extended_field_strength_timed(g, c->comm, gauge_dev_lex, reps, c->ev0, c->ev1, c->stream, milliseconds)
+                               : clover_kernels_timed(g.L, gauge_dev_lex, c->par.m0, c->par.csw, which, reps, c->ev0, c->ev1, c->stream, milliseconds);
   if (plaquette) *plaquette = pl;
   DDAMG_API_END
 }

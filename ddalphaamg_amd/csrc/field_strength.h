@@ -9,7 +9,11 @@
 // Q_{nu mu} = Q_{mu nu}^dagger, so the plane's contribution to the clover term is F = (Q - Q^dagger) / 16: anti-Hermitian,
 // kept as 9 reals per site and plane.  The plaquette is the trace of the first leaf.
 //
-// The bodies are plain functions of (workgroup, thread) so that a host program can run them thread by thread.
+// On a process grid the same kernel reads the lattice extended by the neighbours' links (Shell below): the tiles still cover
+// own sites only, and only the offsets of the staged neighbourhood differ (stage_offsets<true>).
+//
+// The bodies are plain functions of (workgroup, thread) so that a host program can run them thread by thread
+// (tests/native/link_shell_check.cpp does, for the extended lattice).
 #pragma once
 #include <cstddef>
 
@@ -103,16 +107,121 @@ DDAMG_FS_HD Tile tile_of(const Planes& g, int p, int block) {
   return t;
 }
 
+// ---- the lattice extended by the neighbours' links on a process grid --------------------------------------------------------
+// The own lattice plus a shell one site deep in every split direction (h[d] = 1; an unsplit direction has h[d] = 0 and keeps
+// wrapping periodically inside the process): extents E[d] = L[d] + 2 h[d], own coordinate c in [-h, L + h) stored at c + h,
+// lexicographic as the own lattice.  Same shell as gauge.cpp builds on the host.
+struct Shell {
+  int L[4], h[4], E[4];
+  size_t stride[4];      // site strides of the extended array
+  size_t V, Ve;          // own sites, sites of the extended array
+};
+inline Shell make_shell(const int L[4], const bool split[4]) {
+  Shell s;
+  s.V = 1; s.Ve = 1;
+  for (int d = 0; d < 4; d++) { s.L[d] = L[d]; s.h[d] = split[d] ? 1 : 0; s.E[d] = L[d] + 2 * s.h[d]; s.V *= (size_t)L[d]; s.Ve *= (size_t)s.E[d]; }
+  s.stride[3] = 1; s.stride[2] = (size_t)s.E[3]; s.stride[1] = s.stride[2] * s.E[2]; s.stride[0] = s.stride[1] * s.E[1];
+  return s;
+}
+
+// W doubles moved by one thread: 2 (one 16-byte access) where every array involved is 16-byte aligned, 1 otherwise
+template <int W> struct Reals;
+template <> struct alignas(16) Reals<2> { double v[2]; };
+template <> struct alignas(8) Reals<1> { double v[1]; };
+
+// links_extend_kernel, thread i of V * 72 / W: W consecutive reals of the caller's links U [V][4][18] into the interior of the
+// extended array Ue [Ve][4][18].  negate_last_t != 0: the T-links of the local slice L[0] - 1 change sign on the way (the
+// anti-periodic boundary; set on the processes that hold the last global time slice and nowhere else, so that the neighbours
+// receive signed links and nobody flips afterwards).  U is read, never written.
+template <int W>
+DDAMG_FS_HD void extend_links(const Shell& s, const double* __restrict__ U, double* __restrict__ Ue, size_t i, int negate_last_t) {
+  constexpr size_t PER_SITE = 72 / W;
+  if (i >= s.V * PER_SITE) return;
+  const size_t lx = i / PER_SITE; const int k = (int)(i - lx * PER_SITE) * W;   // first real inside the site
+  size_t r = lx;
+  const int x3 = (int)(r % s.L[3]); r /= s.L[3];
+  const int x2 = (int)(r % s.L[2]); r /= s.L[2];
+  const int x1 = (int)(r % s.L[1]); r /= s.L[1];
+  const int x0 = (int)r;
+  const size_t e = (size_t)(x0 + s.h[0]) * s.stride[0] + (size_t)(x1 + s.h[1]) * s.stride[1] + (size_t)(x2 + s.h[2]) * s.stride[2] + (size_t)(x3 + s.h[3]);
+  Reals<W> v = *reinterpret_cast<const Reals<W>*>(U + lx * 72 + k);
+  if (negate_last_t && k < 18 && x0 == s.L[0] - 1) {
+#pragma unroll
+    for (int w = 0; w < W; w++) v.v[w] = -v.v[w];
+  }
+  *reinterpret_cast<Reals<W>*>(Ue + e * 72 + k) = v;
+}
+
+// One slab of the extended array: the sites with coordinate `plane` (as stored: own coordinate + h) in direction mu.  Directions
+// are exchanged in the order 0, 1, 2, 3; the slab spans the full extended range of the split directions before mu, so that what
+// was received there (the corners) travels along, and the own range of the directions after mu.
+struct Slab {
+  int mu;
+  int n[4];          // sites per direction (n[mu] = 1)
+  int first[4];      // stored coordinate of the first one (first[mu]: set by the caller, see slab_at)
+  size_t sites;
+};
+inline Slab make_slab(const Shell& s, int mu) {
+  Slab b; b.mu = mu; b.sites = 1;
+  for (int d = 0; d < 4; d++) {
+    if (d == mu) { b.n[d] = 1; b.first[d] = 0; }
+    else if (d < mu) { b.n[d] = s.E[d]; b.first[d] = 0; }
+    else { b.n[d] = s.L[d]; b.first[d] = s.h[d]; }
+    b.sites *= (size_t)b.n[d];
+  }
+  return b;
+}
+// the slab at own coordinate c of direction mu: c = L - 1 and 0 are packed, -1 and L are filled from what arrived
+inline Slab slab_at(const Shell& s, Slab b, int c) { b.first[b.mu] = c + s.h[b.mu]; return b; }
+
+// link_slab_pack_kernel (to_buffer) / link_slab_unpack_kernel, thread i of sites * 36: 16 bytes, consecutive threads consecutive
+// reals of a site; buf [sites][72] in the slab's own lexicographic order, the same on the sender and the receiver
+DDAMG_FS_HD void slab_copy(const Shell& s, const Slab& b, double* __restrict__ Ue, double* __restrict__ buf, size_t i, bool to_buffer) {
+  if (i >= b.sites * 36) return;
+  const size_t site = i / 36; const int k = (int)(i - site * 36) * 2;
+  size_t r = site, e = 0;
+#pragma unroll
+  for (int d = 3; d >= 0; d--) { e += (size_t)(b.first[d] + (int)(r % b.n[d])) * s.stride[d]; r /= b.n[d]; }
+  Reals<2>* in_array = reinterpret_cast<Reals<2>*>(Ue + e * 72 + k);
+  Reals<2>* in_buffer = reinterpret_cast<Reals<2>*>(buf + site * 72 + k);
+  if (to_buffer) *in_buffer = *in_array; else *in_array = *in_buffer;
+}
+
+// where the staged neighbourhood of tile t lies in the extended array: the tile with the extended array's strides and the offset
+// of the two outside coordinates there.  Used for the loads only; F and the plaquette keep the own lattice's tile.
+DDAMG_FS_HD Tile extended_tile(const Planes& g, const Shell& s, const Tile& t, int block) {
+  Tile x = t;
+  x.smu = s.stride[t.mu]; x.snu = s.stride[t.nu];
+  int r = block / (((g.L[t.nu] + TILE - 1) / TILE) * ((g.L[t.mu] + TILE - 1) / TILE));
+  x.outside = 0;
+  for (int d = 3; d >= 0; d--)
+    if (d != t.mu && d != t.nu) { x.outside += (size_t)(r % g.L[d] + s.h[d]) * s.stride[d]; r /= g.L[d]; }
+  return x;
+}
+
 // step 1, threads 0 .. 2 EXT - 1: site offset of every mu row (entries 0 .. EXT-1) and nu column (EXT .. 2 EXT - 1) of the
-// staged neighbourhood, periodic; flip[i] != 0: the mu links of row i carry the anti-periodic sign (mu = T, last time slice)
-DDAMG_FS_HD void stage_offsets(const Planes& g, const Tile& t, int anti_pbc, int tid, size_t* off, int* flip) {
+// staged neighbourhood, periodic; flip[i] != 0: the mu links of row i carry the anti-periodic sign (mu = T, last time slice).
+// EXTENDED (t: extended_tile, s: its shell): offsets into the extended array.  A split direction is addressed without wrap,
+// coordinate c in [-1, L] at c + 1 (rows of a tile tail beyond L, which no site of the lattice reads, stay at L); the others wrap
+// as on a single process.  The sign is in the extended array already: nothing is flipped.
+template <bool EXTENDED = false>
+DDAMG_FS_HD void stage_offsets(const Planes& g, const Tile& t, int anti_pbc, int tid, size_t* off, int* flip, const Shell* s = nullptr) {
   if (tid >= 2 * EXT) return;
   const bool row = tid < EXT;
   const int i = row ? tid : tid - EXT;
   const int Ld = g.L[row ? t.mu : t.nu];
-  const int c = ((row ? t.a0 : t.b0) + i - 1 + Ld) % Ld;
-  off[tid] = (size_t)c * (row ? t.smu : t.snu);
-  if (row) flip[i] = (anti_pbc && t.mu == 0 && c == g.L[0] - 1) ? 1 : 0;
+  if constexpr (EXTENDED) {
+    const int h = s->h[row ? t.mu : t.nu];
+    int c = (row ? t.a0 : t.b0) + i - 1;
+    if (h) c = (c > Ld ? Ld : c) + 1;
+    else c = (c + Ld) % Ld;
+    off[tid] = (size_t)c * (row ? t.smu : t.snu);
+    if (row) flip[i] = 0;
+  } else {
+    const int c = ((row ? t.a0 : t.b0) + i - 1 + Ld) % Ld;
+    off[tid] = (size_t)c * (row ? t.smu : t.snu);
+    if (row) flip[i] = (anti_pbc && t.mu == 0 && c == g.L[0] - 1) ? 1 : 0;
+  }
 }
 
 // step 2, all threads: the links of both directions into LDS, lds[(w * NEXT + i * EXT + j) * PITCH + k], w = 0: U_mu, 1: U_nu;

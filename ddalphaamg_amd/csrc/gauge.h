@@ -27,6 +27,16 @@ double clover_kernels_timed(const int L[4], const double* dU, double m0, double 
                             float* ms);
 struct Geometry;
 struct Comm;
+// gauge_to_operator_resident on a process grid (ddamg_hip_set_gauge_device_grid): the process's own links in device memory, read
+// in place and never written.  The clover field's links are copied into the local lattice extended by one site in every split
+// direction, the neighbours' shell (corners included) is exchanged device to device over the transport, and the field-strength
+// kernel runs on the extended array; D comes from the own hopping links alone.  Collective; returns the global average plaquette
+// (one all-reduce).  Waits for the stream; the extended array and the slab buffers live for the call only.
+double gauge_to_operator_resident_grid(const Geometry& g, Comm* comm, const double* dU_hopp, const double* dU_clover, int anti_pbc, double m0, double csw,
+                                       double* dD, double* dC, hipStream_t st);
+// measurement (ddamg_hip_clover_kernel_time, which = 3): the field-strength kernel on the extended array of the links dU, built
+// once as above; *ms = milliseconds per launch; returns this process's average plaquette
+double extended_field_strength_timed(const Geometry& g, Comm* comm, const double* dU, int reps, hipEvent_t e0, hipEvent_t e1, hipStream_t st, float* ms);
 double gauge_to_operator_dist(const Geometry& g, Comm* comm, const double* gauge_in, int anti_pbc, double m0, double csw,
                               double* D_out, double* clover_out, hipStream_t st);
 }

@@ -1,10 +1,15 @@
 // gauge_device.hip -- clover term and plaquette on the device, for the own lattice of a single process and for the
-// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them).
+// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them for links in host memory, ExtendedLinks
+// below for links in device memory).
 // Reference: compute_clover_term src/dirac.c:24-58, Q / Qdiff / set_clover :304-402, calc_plaq :568-622.
 // One thread per lexicographic site; links are read straight from the reference layout [V][4][3x3] complex fp64.
 #include "gauge.h"
 #include "common.h"
 #include "field_strength.h"
+#include "geometry.h"
+#include "halo.h"
+#include <algorithm>
+#include <cstdint>
 #include <vector>
 
 namespace ddamg {
@@ -188,12 +193,15 @@ double clover_and_plaquette_extended_device(const int L[4], const int halo[4], c
 }
 
 
-// ---- links that the caller keeps in device memory (ddamg_hip_set_gauge_device) ----------------------------------------------
-// The links are read in place and never written: the anti-periodic sign is applied in the loads.  Kernel bodies: field_strength.h.
+// ---- links that the caller keeps in device memory (ddamg_hip_set_gauge_device, _set_gauge_device_grid) -----------------------
+// The links are read in place and never written: the anti-periodic sign is applied in the loads (on a process grid: in the copy
+// into the extended array).  Kernel bodies: field_strength.h.
 namespace {
-// F of one plane for an 8 x 8 tile of its sites (grid: x = tiles, y = the six planes) and the tile's sum of plaquette traces
+// F of one plane for an 8 x 8 tile of its sites (grid: x = tiles, y = the six planes) and the tile's sum of plaquette traces.
+// EXTENDED: U is the lattice extended by the neighbours' links (shell); tiles, F and the sums stay those of the own lattice
+template <bool EXTENDED>
 __global__ __launch_bounds__(fs::THREADS) void field_strength_kernel(double* __restrict__ F, double* __restrict__ plaq_block, const double* __restrict__ U,
-                                                                      fs::Planes g, size_t V, int anti_pbc) {
+                                                                      fs::Planes g, size_t V, int anti_pbc, fs::Shell shell) {
   __shared__ double lds[fs::LDS_DOUBLES];
   __shared__ size_t off[2 * fs::EXT];
   __shared__ int flip[fs::EXT];
@@ -204,9 +212,16 @@ __global__ __launch_bounds__(fs::THREADS) void field_strength_kernel(double* __r
     return;
   }
   const fs::Tile t = fs::tile_of(g, p, block);
-  fs::stage_offsets(g, t, anti_pbc, tid, off, flip);
-  __syncthreads();
-  fs::stage_links(U, t, tid, off, flip, lds);
+  if constexpr (EXTENDED) {
+    const fs::Tile te = fs::extended_tile(g, shell, t, block);
+    fs::stage_offsets<true>(g, te, 0, tid, off, flip, &shell);
+    __syncthreads();
+    fs::stage_links(U, te, tid, off, flip, lds);
+  } else {
+    fs::stage_offsets(g, t, anti_pbc, tid, off, flip);
+    __syncthreads();
+    fs::stage_links(U, t, tid, off, flip, lds);
+  }
   __syncthreads();
   size_t lex = 0; double f[9]; double pl = 0.0;
   if (fs::site_field_strength(g, t, tid, lds, &lex, f, &pl)) {
@@ -218,6 +233,19 @@ __global__ __launch_bounds__(fs::THREADS) void field_strength_kernel(double* __r
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pl += __shfl_down(pl, o, 64);   // the workgroup is one wave
   if (tid == 0) plaq_block[slot] = pl;
+}
+
+// the caller's links into the interior of the extended array, W reals per thread (fs::extend_links)
+template <int W>
+__global__ __launch_bounds__(256) void links_extend_kernel(double* __restrict__ Ue, const double* __restrict__ U, fs::Shell shell, int negate_last_t) {
+  fs::extend_links<W>(shell, U, Ue, (size_t)blockIdx.x * 256 + threadIdx.x, negate_last_t);
+}
+// one slab of the extended array into a contiguous buffer, and a received buffer into the slab one site further out (fs::slab_copy)
+__global__ __launch_bounds__(256) void link_slab_pack_kernel(double* __restrict__ buf, double* __restrict__ Ue, fs::Shell shell, fs::Slab slab) {
+  fs::slab_copy(shell, slab, Ue, buf, (size_t)blockIdx.x * 256 + threadIdx.x, true);
+}
+__global__ __launch_bounds__(256) void link_slab_unpack_kernel(double* __restrict__ Ue, double* __restrict__ buf, fs::Shell shell, fs::Slab slab) {
+  fs::slab_copy(shell, slab, Ue, buf, (size_t)blockIdx.x * 256 + threadIdx.x, false);
 }
 
 __global__ __launch_bounds__(128) void clover_assemble_kernel(double* __restrict__ clover, const double* __restrict__ F, size_t V, double m0, double csw,
@@ -267,7 +295,12 @@ struct ResidentWork {
   }
   double* total() { return part + 6 * (size_t)planes.max_blocks; }
   void field_strength(const double* dU, int anti_pbc, hipStream_t st) {
-    hipLaunchKernelGGL(field_strength_kernel, dim3((unsigned)planes.max_blocks, 6), dim3(fs::THREADS), 0, st, F, part, dU, planes, V, anti_pbc);
+    hipLaunchKernelGGL(field_strength_kernel<false>, dim3((unsigned)planes.max_blocks, 6), dim3(fs::THREADS), 0, st, F, part, dU, planes, V, anti_pbc,
+                       fs::Shell{});
+    DDAMG_HIP_CHECK(hipGetLastError());
+  }
+  void field_strength_extended(const double* dUe, const fs::Shell& shell, hipStream_t st) {   // the sign is in dUe
+    hipLaunchKernelGGL(field_strength_kernel<true>, dim3((unsigned)planes.max_blocks, 6), dim3(fs::THREADS), 0, st, F, part, dUe, planes, V, 0, shell);
     DDAMG_HIP_CHECK(hipGetLastError());
   }
   void assemble(double* dC, double m0, double csw, hipStream_t st) {
@@ -276,11 +309,54 @@ struct ResidentWork {
     hipLaunchKernelGGL(plaquette_sum_kernel, dim3(1), dim3(256), 0, st, total(), part, 6 * (size_t)planes.max_blocks);
     DDAMG_HIP_CHECK(hipGetLastError());
   }
-  double plaquette(hipStream_t st) {   // average over sites and planes; waits for the stream
+  double plaquette_sum(hipStream_t st) {   // over the own sites and the planes; waits for the stream
     double sum = 0;
     DDAMG_HIP_CHECK(hipMemcpyAsync(&sum, total(), sizeof(double), hipMemcpyDeviceToHost, st));
     DDAMG_HIP_CHECK(hipStreamSynchronize(st));
-    return sum / ((double)V * 6.0);
+    return sum;
+  }
+  double plaquette(hipStream_t st) { return plaquette_sum(st) / ((double)V * 6.0); }   // the average
+};
+
+// The lattice extended by the neighbours' links, on the device: the caller's links go into the interior (with the anti-periodic
+// sign, on the processes that hold the last global time slice), then the shell arrives direction by direction, device to device
+// (comm_sendrecv_device), each slab spanning what the directions before it brought so that the corners travel along -- a corner
+// of a (T, Z) plane comes from the diagonal process in two hops.  A full extended copy, not a compact shell next to the caller's
+// array: it costs one streaming pass and (E/L)^4 of the field for the duration of the call, and keeps the staging of
+// field_strength_kernel a sum of a row and a column offset.  All four links of a shell site travel (72 doubles), though the
+// leaves never read U_mu at x + mu: trimming the slab at L would save a quarter of half the messages and cost a second layout.
+struct ExtendedLinks {
+  fs::Shell shell;
+  DeviceBuffer<double> Ue, sbuf, rbuf;
+  explicit ExtendedLinks(const Geometry& g) : shell(fs::make_shell(g.L, g.split)) {
+    Ue.alloc(72 * shell.Ve);
+    size_t most = 0;
+    for (int mu = 0; mu < 4; mu++) if (shell.h[mu]) most = std::max(most, fs::make_slab(shell, mu).sites);
+    if (most) { sbuf.alloc(72 * most); rbuf.alloc(72 * most); }
+  }
+  // enqueued on st; collective over the process grid.  dU is read, never written.
+  void fill(const Geometry& g, Comm* comm, const double* dU, int anti_pbc, hipStream_t st) {
+    const int negate_last_t = (anti_pbc && g.pc[0] == g.P[0] - 1) ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(dU) % 16 == 0)
+      hipLaunchKernelGGL(links_extend_kernel<2>, dim3((unsigned)((shell.V * 36 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
+    else
+      hipLaunchKernelGGL(links_extend_kernel<1>, dim3((unsigned)((shell.V * 72 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
+    DDAMG_HIP_CHECK(hipGetLastError());
+    for (int mu = 0; mu < 4; mu++) {
+      if (!shell.h[mu]) continue;
+      const fs::Slab slab = fs::make_slab(shell, mu);
+      const unsigned blocks = (unsigned)((slab.sites * 36 + 255) / 256);
+      for (int side = 0; side < 2; side++) {
+        // side 0: my slice x_mu = L-1 goes to the +mu neighbour (its x_mu = -1); side 1: x_mu = 0 to the -mu neighbour (its x_mu = L)
+        const int src_c = side == 0 ? shell.L[mu] - 1 : 0, dst_c = side == 0 ? -1 : shell.L[mu];
+        hipLaunchKernelGGL(link_slab_pack_kernel, dim3(blocks), dim3(256), 0, st, sbuf, Ue, shell, fs::slab_at(shell, slab, src_c));
+        DDAMG_HIP_CHECK(hipGetLastError());
+        comm_sendrecv_device(comm, sbuf, g.neighbor_rank[side == 0 ? mu : 4 + mu], rbuf, g.neighbor_rank[side == 0 ? 4 + mu : mu],
+                             sizeof(double) * 72 * slab.sites, 100 + 2 * mu + side, st);
+        hipLaunchKernelGGL(link_slab_unpack_kernel, dim3(blocks), dim3(256), 0, st, Ue, rbuf, shell, fs::slab_at(shell, slab, dst_c));
+        DDAMG_HIP_CHECK(hipGetLastError());
+      }
+    }
   }
 };
 }  // namespace
@@ -294,6 +370,46 @@ double gauge_to_operator_resident(const int L[4], const double* dU_hopp, const d
   w.field_strength(dU_clover, anti_pbc, st);
   w.assemble(dC, m0, csw, st);
   return w.plaquette(st);
+}
+
+double gauge_to_operator_resident_grid(const Geometry& g, Comm* comm, const double* dU_hopp, const double* dU_clover, int anti_pbc, double m0, double csw,
+                                       double* dD, double* dC, hipStream_t st) {
+  DDAMG_REQUIRE(comm != nullptr, "process grid > 1 but no transport: call ddamg_hip_comm_init_rccl or ddamg_hip_comm_init_host first");
+  ResidentWork w(g.L);
+  // D needs the own links only; the last global time slice lives on the processes at the end of the T direction of the grid
+  const int negate_last_t = (anti_pbc && g.pc[0] == g.P[0] - 1) ? 1 : 0;
+  const size_t n = 72 * w.V, vol3 = (size_t)g.L[1] * g.L[2] * g.L[3];
+  hipLaunchKernelGGL(links_to_D_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dD, dU_hopp, n, negate_last_t, (size_t)(g.L[0] - 1) * vol3 * 72);
+  DDAMG_HIP_CHECK(hipGetLastError());
+  ExtendedLinks x(g);
+  x.fill(g, comm, dU_clover, anti_pbc, st);
+  w.field_strength_extended(x.Ue, x.shell, st);
+  w.assemble(dC, m0, csw, st);
+  double acc[2] = {w.plaquette_sum(st), (double)w.V * 6.0};   // the stream is idle now: x may go
+  comm_allreduce_host(comm, acc, 2);
+  comm_release_device_staging(comm);
+  return acc[0] / acc[1];
+}
+
+double extended_field_strength_timed(const Geometry& g, Comm* comm, const double* dU, int reps, hipEvent_t e0, hipEvent_t e1, hipStream_t st, float* ms) {
+  DDAMG_REQUIRE(comm != nullptr && reps >= 1, "extended_field_strength_timed: a transport and reps >= 1");
+  ResidentWork w(g.L);
+  ExtendedLinks x(g);
+  x.fill(g, comm, dU, 0, st);
+  for (int r = -1; r < reps; r++) {   // r = -1: untimed first launch
+    if (r == 0) DDAMG_HIP_CHECK(hipEventRecord(e0, st));
+    w.field_strength_extended(x.Ue, x.shell, st);
+  }
+  DDAMG_HIP_CHECK(hipEventRecord(e1, st));
+  DDAMG_HIP_CHECK(hipEventSynchronize(e1));
+  DDAMG_HIP_CHECK(hipEventElapsedTime(ms, e0, e1));
+  *ms /= (float)reps;
+  DeviceBuffer<double> dC;
+  dC.alloc(84 * w.V);
+  w.assemble(dC, 0.0, 0.0, st);
+  const double pl = w.plaquette(st);
+  comm_release_device_staging(comm);
+  return pl;
 }
 
 double clover_kernels_timed(const int L[4], const double* dU, double m0, double csw, int which, int reps, hipEvent_t e0, hipEvent_t e1, hipStream_t st,

@@ -32,6 +32,15 @@ void rccl_unique_id(void* id128);
 // host-buffer primitives over either transport (setup-time exchanges such as the gauge-field halo): blocking
 void comm_sendrecv_host(Comm* c, const void* send, int send_peer, void* recv, int recv_peer, size_t bytes, int tag);
 void comm_allreduce_host(Comm* c, double* buf, int n);
+// device-buffer send / receive over either transport (the shell of links of ddamg_hip_set_gauge_device_grid): `bytes` from d_send
+// to send_peer and as many from recv_peer into d_recv, one message each way, sent and received together so that a process that is
+// its own neighbour does not wait for itself.  Ordered behind the work already on `st`, and `st` waits for it: what is enqueued
+// on `st` afterwards sees d_recv complete and may overwrite d_send.  The call itself may return before anything has moved (RCCL:
+// the transfer runs on the transport stream, nothing is staged), so both buffers must stay allocated until `st` has passed this
+// point.  Host transport: device -> pinned, the callback with one message, pinned -> device; the pinned staging is kept for the
+// next call until comm_release_device_staging.
+void comm_sendrecv_device(Comm* c, const void* d_send, int send_peer, void* d_recv, int recv_peer, size_t bytes, int tag, hipStream_t st);
+void comm_release_device_staging(Comm* c);
 // d_recv[r*bytes .. (r+1)*bytes) <- d_send of process r, for every process r (device buffers; enqueued behind st, which waits for it)
 void comm_allgather(Comm* c, const void* d_send, void* d_recv, size_t bytes, hipStream_t st);
 // what travelled since the last reset: halo exchanges by payload (bytes per face site), reductions, all-gathers (JSON object)

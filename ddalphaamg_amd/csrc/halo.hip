@@ -58,6 +58,8 @@ struct Comm {
     void reset() { collect_all(); calls = 0; bytes = 0; ms = 0; }
     void destroy() { for (int i = 0; i < NEV; i++) { if (a[i]) (void)hipEventDestroy(a[i]); if (b[i]) (void)hipEventDestroy(b[i]); a[i] = b[i] = nullptr; } }
   } allreduce_stats, allgather_stats;
+  PinnedBuffer<char> h_dev_send, h_dev_recv;     // staging for the host transport's device-buffer messages
+  Payload link_shell_stats;                     // comm_sendrecv_device: calls (exchanges), messages sent, bytes sent
   std::string stats_json;
 };
 
@@ -78,15 +80,19 @@ const char* comm_stats_json(Comm* c) {
   snprintf(buf, sizeof buf, "], \"allreduce\": {\"calls\": %llu, \"bytes\": %llu, \"milliseconds_on_the_transport_stream\": %s%.3f}", c->allreduce_stats.calls,
            c->allreduce_stats.bytes, c->kind == 1 ? "" : "null, \"host_note_ms\": ", c->allreduce_stats.ms);
   s += buf;
-  snprintf(buf, sizeof buf, ", \"allgather\": {\"calls\": %llu, \"bytes_sent\": %llu, \"milliseconds_on_the_transport_stream\": %s%.3f}}", c->allgather_stats.calls,
+  snprintf(buf, sizeof buf, ", \"allgather\": {\"calls\": %llu, \"bytes_sent\": %llu, \"milliseconds_on_the_transport_stream\": %s%.3f}", c->allgather_stats.calls,
            c->allgather_stats.bytes, c->kind == 1 ? "" : "null, \"host_note_ms\": ", c->allgather_stats.ms);
+  s += buf;
+  // device-buffer messages (the shell of links of a configuration): a payload class of their own, not a halo exchange
+  snprintf(buf, sizeof buf, ", \"device_sendrecv\": {\"calls\": %llu, \"messages\": %llu, \"bytes_sent\": %llu}}", c->link_shell_stats.exchanges,
+           c->link_shell_stats.messages, c->link_shell_stats.bytes);
   s += buf;
   c->stats_json = s;
   return c->stats_json.c_str();
 }
 void comm_stats_reset(Comm* c) {
   if (!c) return;
-  c->halo_stats.clear(); c->allreduce_stats.reset(); c->allgather_stats.reset();
+  c->halo_stats.clear(); c->allreduce_stats.reset(); c->allgather_stats.reset(); c->link_shell_stats = Comm::Payload{};
 }
 
 int comm_rank(const Comm* c) { return c ? c->rank : 0; }
@@ -203,6 +209,33 @@ void comm_sendrecv_host(Comm* c, const void* send, int send_peer, void* recv, in
   DDAMG_NCCL_CHECK(ncclGroupEnd());
   DDAMG_HIP_CHECK(hipMemcpyAsync(recv, dr, bytes, hipMemcpyDeviceToHost, c->stream));
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+void comm_sendrecv_device(Comm* c, const void* d_send, int send_peer, void* d_recv, int recv_peer, size_t bytes, int tag, hipStream_t st) {
+  DDAMG_REQUIRE(c != nullptr, "process grid > 1 but no transport: call ddamg_hip_comm_init_rccl or ddamg_hip_comm_init_host first");
+  c->link_shell_stats.exchanges++; c->link_shell_stats.messages++; c->link_shell_stats.bytes += bytes;
+  if (c->kind == 1) {
+    DDAMG_HIP_CHECK(hipEventRecord(c->ev_a, st));
+    DDAMG_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_a, 0));
+    DDAMG_NCCL_CHECK(ncclGroupStart());
+    DDAMG_NCCL_CHECK(ncclSend(d_send, bytes, ncclChar, send_peer, c->nccl, c->stream));
+    DDAMG_NCCL_CHECK(ncclRecv(d_recv, bytes, ncclChar, recv_peer, c->nccl, c->stream));
+    DDAMG_NCCL_CHECK(ncclGroupEnd());
+    DDAMG_HIP_CHECK(hipEventRecord(c->ev_b, c->stream));
+    DDAMG_HIP_CHECK(hipStreamWaitEvent(st, c->ev_b, 0));
+    return;
+  }
+  if (bytes > c->h_dev_send.bytes()) { c->h_dev_send.alloc(bytes); c->h_dev_recv.alloc(bytes); }
+  DDAMG_HIP_CHECK(hipMemcpyAsync(c->h_dev_send, d_send, bytes, hipMemcpyDeviceToHost, st));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(st));
+  ddamg_hip_halo_msg m{send_peer, recv_peer, tag, c->h_dev_send.get(), c->h_dev_recv.get(), (unsigned long long)bytes};
+  c->fn(c->user, 1, &m);
+  DDAMG_HIP_CHECK(hipMemcpyAsync(d_recv, c->h_dev_recv, bytes, hipMemcpyHostToDevice, st));
+  DDAMG_HIP_CHECK(hipStreamSynchronize(st));   // the staging is reused by the next call
+}
+void comm_release_device_staging(Comm* c) {
+  if (!c) return;
+  c->h_dev_send.reset(); c->h_dev_recv.reset();
 }
 
 void comm_allreduce_host(Comm* c, double* buf, int n) {

@@ -108,16 +108,29 @@ int ddamg_hip_set_gauge2(ddamg_hip_ctx* ctx, const double* hopp_gauge_lex, const
  * into the links, src/io.c:536-541, is applied in the loads), the plaquette is summed on the device, and both precisions'
  * operators are laid out from the staging arrays.  Same effect on the context as ddamg_hip_set_gauge, except that the host copy
  * behind ddamg_hip_get_operator is not filled: it is rebuilt from the fp64 operator when it is asked for.  Refused, with a message
- * that names ddamg_hip_set_gauge, on a context whose fine level is divided over processes (process_grid entries > 1 or -1),
- * because the clover term then needs the neighbours' links. */
+ * that names ddamg_hip_set_gauge_device_grid and ddamg_hip_set_gauge, on a context whose fine level is divided over processes
+ * (process_grid entries > 1 or -1), because the clover term then needs the neighbours' links and the call becomes collective. */
 int ddamg_hip_set_gauge_device(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int anti_pbc, double* plaquette);
 /* ddamg_hip_set_gauge2 (dirac_setup( hopp, clover ), src/dirac.c:60-168) from two fields in device memory: D from the first, the
  * clover term and the plaquette from the second, one layout pass.  Equal pointers behave as ddamg_hip_set_gauge_device. */
 int ddamg_hip_set_gauge2_device(ddamg_hip_ctx* ctx, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette);
+/* The same two on any process grid (the reference exchanges the ghost shell of the gauge field in dirac_setup, src/dirac.c:88-120).
+ * Arguments and layout as above: this process's links [V][4][9] complex fp64, lexicographic T,Z,Y,X in the local lattice, never
+ * written.  COLLECTIVE: every process of the grid calls it, with a transport installed (ddamg_hip_comm_init_rccl / _host / _mpi).
+ * The links of the clover field are copied into the local lattice extended by one site in every split direction (the anti-periodic
+ * sign goes in there, on the processes that hold the last global time slice), and the neighbours' shell, corners included, arrives
+ * device to device: 72 doubles per shell site, two messages per split direction, one direction after the other; RCCL moves the
+ * device buffers themselves, the host transport stages them through pinned memory.  The hopping field needs no shell.  The
+ * extended array lives for the call only.  *plaquette is the global average (one all-reduce).  On a context that is not divided
+ * they are ddamg_hip_set_gauge_device / _set_gauge2_device. */
+int ddamg_hip_set_gauge_device_grid(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int anti_pbc, double* plaquette);
+int ddamg_hip_set_gauge2_device_grid(ddamg_hip_ctx* ctx, const double* hopp_gauge_dev_lex, const double* clover_gauge_dev_lex, int anti_pbc, double* plaquette);
 /* Milliseconds per launch of the kernels that turn links in device memory into the clover term, between the context's timer events
  * (as ddamg_hip_timer_begin / _end) after one untimed launch: which = 0 the field-strength kernel of ddamg_hip_set_gauge_device,
- * 1 the clover kernel of ddamg_hip_set_gauge, 2 the field-strength, assembly and plaquette-sum kernels together.  *plaquette: the
- * average plaquette the kernels give.  The context is not changed.  For measurements (tools/device_interface_bench.py).  No
+ * 1 the clover kernel of ddamg_hip_set_gauge, 2 the field-strength, assembly and plaquette-sum kernels together (0, 1, 2: single
+ * process), 3 the field-strength kernel of ddamg_hip_set_gauge_device_grid on the extended lattice, which is built once before the
+ * timed launches (a process grid with a transport; collective).  *plaquette: the average plaquette the kernels give (3: over this
+ * process's sites).  The context is not changed.  For measurements (tools/device_interface_bench.py).  No
  * counterpart in the reference. */
 int ddamg_hip_clover_kernel_time(ddamg_hip_ctx* ctx, const double* gauge_dev_lex, int which, int reps, float* milliseconds, double* plaquette);
 
@@ -134,11 +147,12 @@ int ddamg_hip_links_to_ildg_device(ddamg_hip_ctx* ctx, const double* links_dev, 
 /* lime_read_conf + dirac_setup (src/lime_io.c:222-337, src/dirac.c:60-168): the configuration of an ILDG file becomes the
  * operator.  Single process: the binary record is read in chunks (64 MiB of file data) into two pinned staging buffers, the read
  * of one chunk overlapping the copy and the conversion kernel of the one before, and the links land in a device array from which
- * the operator is built as ddamg_hip_set_gauge_device builds it; no host code touches a link.  On a process grid: this process's
- * part through ddamg_hip_read_ildg_conf and ddamg_hip_set_gauge (a transport must be installed).  The file's lattice must be the
- * context's global lattice.  *plaquette_out: the plaquette computed from the links, in [0,3]; *file_plaquette_out: three times the
- * number of the file's "xlf-info" record if *has_file_plaquette_out (all three may be NULL).  A failure leaves the operator that
- * was set before in place. */
+ * the operator is built as ddamg_hip_set_gauge_device builds it; no host code touches a link.  On a process grid (collective, a
+ * transport must be installed): each process reads its own part the same way -- a chunk is gathered from the runs of L[X] sites
+ * that ddamg_hip_read_ildg_conf reads as rows -- and the operator is built as ddamg_hip_set_gauge_device_grid builds it.  The
+ * file's lattice must be the context's global lattice.  *plaquette_out: the plaquette computed from the links, in [0,3];
+ * *file_plaquette_out: three times the number of the file's "xlf-info" record if *has_file_plaquette_out (all three may be
+ * NULL).  A failure leaves the operator that was set before in place. */
 int ddamg_hip_load_ildg_conf(ddamg_hip_ctx* ctx, const char* path, int anti_pbc, double* plaquette_out, double* file_plaquette_out,
                              int* has_file_plaquette_out);
 

@@ -12,6 +12,10 @@ memory, ONE process, ONE seeded field, ONE context per hierarchy.  Run it under 
                      (ddamg_hip_clover_kernel_time); GB/s of the field-strength kernel are the links read once and F written
                      (576 + 432 bytes per site) over its time
   solve              seconds per ddamg_hip_solve and per ddamg_hip_solve_device (rhs = ones, tol 1e-10) after one setup
+  --grid T Z Y X     a process grid with entries 1 and -1 (-1: the process is its own neighbour in that direction, over RCCL;
+                     -1 -1 -1 -1 is the full self-exchange): set_gauge against set_gauge_device_grid on the SAME context and
+                     field, in alternation, then milliseconds per launch of field_strength_kernel on the extended lattice
+                     (ddamg_hip_clover_kernel_time, which = 3); no solve leg
 Every figure is the median over --reps calls after --warmup untimed ones, the two forms in alternation.  Device arrays come from
 the HIP runtime the library is linked to."""
 import argparse, ctypes, json, os, statistics, sys, time
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--kernel-reps", type=int, default=10)
     ap.add_argument("--no-solve", action="store_true")
+    ap.add_argument("--grid", type=int, nargs=4, metavar=("T", "Z", "Y", "X"), help="process-grid entries, 1 or -1")
     ap.add_argument("--out")
     a = ap.parse_args()
     import synth
@@ -66,20 +71,38 @@ def main():
     if n >= 64:
         p.restart, p.max_restart = 10, 100
     U = synth.synth_gauge(L, bench.GAUGE_EPS, bench.GAUGE_SEED)
+    if a.grid:
+        if any(e not in (1, -1) for e in a.grid) or all(e == 1 for e in a.grid):
+            raise SystemExit("--grid takes entries 1 and -1, at least one of them -1 (one process)")
+        for mu in range(4):
+            p.process_grid[mu] = a.grid[mu]
     ctx = dd.Context(p)
     hip = hip_runtime()
     dU = to_device(hip, U)
     res = {"lattice": L, "levels": a.levels}
     plaq = {}
-    med, spread = alternate({"set_gauge": lambda: plaq.__setitem__("host", ctx.set_gauge(U, anti_pbc=True)),
-                             "set_gauge_device": lambda: plaq.__setitem__("device", ctx.set_gauge_device(dU, anti_pbc=True))}, a.warmup, a.reps)
-    res["set_gauge_s"] = med["set_gauge"]; res["set_gauge_device_s"] = med["set_gauge_device"]
-    res["set_gauge_spread_s"] = spread
-    res["plaquette"] = plaq
-    for which, name in ((0, "field_strength_kernel_ms"), (1, "clover_kernel_ms"), (2, "device_path_kernels_ms"), (0, "field_strength_kernel_ms_again"),
-                        (1, "clover_kernel_ms_again")):
-        res[name], _ = ctx.clover_kernel_time(dU, which, a.kernel_reps)
-    res["field_strength_GBps"] = V * (576 + 432) / (res["field_strength_kernel_ms"] * 1e-3) / 1e9
+    if a.grid:
+        ctx.comm_init_rccl(api.rccl_unique_id())
+        res["grid"] = a.grid
+        med, spread = alternate({"set_gauge": lambda: plaq.__setitem__("host", ctx.set_gauge(U, anti_pbc=True)),
+                                 "set_gauge_device_grid": lambda: plaq.__setitem__("device", ctx.set_gauge_device_grid(dU, anti_pbc=True))}, a.warmup, a.reps)
+        res["set_gauge_s"] = med["set_gauge"]; res["set_gauge_device_grid_s"] = med["set_gauge_device_grid"]
+        res["set_gauge_spread_s"] = spread
+        res["plaquette"] = plaq
+        for name in ("field_strength_extended_kernel_ms", "field_strength_extended_kernel_ms_again"):
+            res[name], _ = ctx.clover_kernel_time(dU, 3, a.kernel_reps)
+        res["comm"] = ctx.comm_stats().get("device_sendrecv")
+        a.no_solve = True
+    else:
+        med, spread = alternate({"set_gauge": lambda: plaq.__setitem__("host", ctx.set_gauge(U, anti_pbc=True)),
+                                 "set_gauge_device": lambda: plaq.__setitem__("device", ctx.set_gauge_device(dU, anti_pbc=True))}, a.warmup, a.reps)
+        res["set_gauge_s"] = med["set_gauge"]; res["set_gauge_device_s"] = med["set_gauge_device"]
+        res["set_gauge_spread_s"] = spread
+        res["plaquette"] = plaq
+        for which, name in ((0, "field_strength_kernel_ms"), (1, "clover_kernel_ms"), (2, "device_path_kernels_ms"), (0, "field_strength_kernel_ms_again"),
+                            (1, "clover_kernel_ms_again")):
+            res[name], _ = ctx.clover_kernel_time(dU, which, a.kernel_reps)
+        res["field_strength_GBps"] = V * (576 + 432) / (res["field_strength_kernel_ms"] * 1e-3) / 1e9
     if not a.no_solve:
         ctx.set_gauge_device(dU, anti_pbc=True)
         ctx.setup(p.setup_iter[0])

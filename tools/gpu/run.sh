@@ -102,7 +102,8 @@ selfx)        # fine operator through the RCCL self-exchange: 0, 1, 2, 3 split d
     echo "grid $g: $(python3 bench.py --steps 500 --warmup 100 --no-solve --no-strong --no-cpu-baseline --self-exchange=$g 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["ms_per_step"]*1000,2), "us")')"
   done ;;
 device_interface)  # set_gauge / solve from host memory against the same from device memory, and the clover kernels alone: run.sh device_interface [extent] [levels]
-  timeout -k 10 900 python3 tools/device_interface_bench.py --lattice ${1:-32} --levels ${2:-2} --out $O/device_interface_${1:-32}.json ;;
+  timeout -k 10 900 python3 tools/device_interface_bench.py --lattice ${1:-32} --levels ${2:-2} --out $O/device_interface_${1:-32}.json &&
+  timeout -k 10 600 python3 tools/device_interface_bench.py --lattice ${1:-32} --levels ${2:-2} --grid -1 -1 -1 -1 --out $O/device_interface_grid_${1:-32}.json ;;
 dagger)       # D, the fused D^dagger and gamma5, D, gamma5 through the entry points, fp32 and fp64, in alternation: run.sh dagger [extent]
   timeout -k 10 300 python3 tools/dagger_bench.py --lattice ${1:-32} --out $O/dagger_${1:-32}.json ;;
 rehearse)     # bench.py --full --rehearse N (default 8): the per-GPU problem of the N-GPU point on one GPU; run.sh rehearse "2 4 8" for the curve
