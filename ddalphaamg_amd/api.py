@@ -165,6 +165,15 @@ def load_library():
         "ddamg_hip_solve_chrono_device": [vp, vp, ctypes.c_int, dp, dp, ctypes.c_double, ip, ip, dp, dp],
         "ddamg_hip_solve_squared_chrono_vec": [vp, vp, vp, vp, vp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_solve_squared_chrono_device": [vp, vp, vp, dp, dp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_vec_upload_parity_device": [vp, vp, ctypes.c_int, dp, ctypes.c_int],
+        "ddamg_hip_vec_download_parity_device": [vp, vp, ctypes.c_int, dp],
+        "ddamg_hip_schur_apply": [vp, vp, vp, ctypes.c_int],
+        "ddamg_hip_schur_apply_device": [vp, dp, dp, ctypes.c_int],
+        "ddamg_hip_solve_schur_vec": [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_solve_schur_device": [vp, ctypes.c_int, ctypes.c_int, dp, dp, dp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_solve_schur_squared_vec": [vp, vp, vp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_solve_schur_squared_device": [vp, dp, dp, dp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_clover_logdet": [vp, ctypes.c_int, dp, ip],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -441,6 +450,18 @@ class Vector:
         """download into a lexicographic float64 array in device memory; returns dev_lex"""
         _check(self.ctx._lib.ddamg_hip_vec_download_device(self.ctx._h, self._h, _dev(dev_lex, self.V * self.ndof * 2, "download_device")))
         return dev_lex
+
+    def upload_parity_device(self, parity, half_dev, zero_other=True):
+        """the sites of `parity` (0 even, 1 odd) from a half field in device memory ([V/2][12] complex float64, half index =
+        lexicographic index >> 1); zero_other: the other parity becomes zero, else it is left alone"""
+        _check(self.ctx._lib.ddamg_hip_vec_upload_parity_device(self.ctx._h, self._h, int(parity), _dev(half_dev, self.V * self.ndof, "upload_parity_device"),
+                                                                int(bool(zero_other))))
+        return self
+
+    def download_parity_device(self, parity, half_dev):
+        """the sites of `parity` into a half field in device memory; returns half_dev"""
+        _check(self.ctx._lib.ddamg_hip_vec_download_parity_device(self.ctx._h, self._h, int(parity), _dev(half_dev, self.V * self.ndof, "download_parity_device")))
+        return half_dev
 
     def free(self):
         if self._h:
@@ -883,6 +904,59 @@ class Context:
         n = self.volume(0) * 24
         return self._squared_chrono_call("solve_squared_chrono_device", hy, hx, _dev(x_dev_lex, n, "solve_squared_chrono_device"),
                                          _dev(b_dev_lex, n, "solve_squared_chrono_device"), tol)
+
+    # ---- the even-odd preconditioned system: Dhat = D_ee - D_eo D_oo^-1 D_oe on the even sites (include/ddamg_hip.h) ----
+    def vec_upload_parity_device(self, v, parity, half_dev, zero_other=True):
+        return v.upload_parity_device(parity, half_dev, zero_other)
+
+    def vec_download_parity_device(self, v, parity, half_dev):
+        return v.download_parity_device(parity, half_dev)
+
+    def schur_apply(self, out, inp, dagger=False):
+        """out = Dhat inp (dagger: Dhat^dagger inp) on the even sites, zero on the odd ones; the odd sites of inp are not read"""
+        _check(self._lib.ddamg_hip_schur_apply(self._h, out._h, inp._h, int(bool(dagger))))
+
+    def schur_apply_device(self, out_e_dev, in_e_dev, dagger=False):
+        """the same on half fields of the even sites in device memory; returns out_e_dev"""
+        n = self.volume(0) * 12
+        _check(self._lib.ddamg_hip_schur_apply_device(self._h, _dev(out_e_dev, n, "schur_apply_device"), _dev(in_e_dev, n, "schur_apply_device"),
+                                                      int(bool(dagger))))
+        return out_e_dev
+
+    def _schur_call(self, name, head, args, tol, squared=False):
+        it = (ctypes.c_int * 2)(); ci = (ctypes.c_int * 2)(); rr = ctypes.c_double(0)
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, *head, *args, float(tol), it, ci, ctypes.byref(rr)))
+        if squared:
+            return (it[0], it[1]), (ci[0], ci[1]), rr.value
+        return it[0], ci[0], rr.value
+
+    def _halves(self, name, x_e_dev, x_o_dev, b_e_dev):
+        n = self.volume(0) * 12
+        return (_dev(x_e_dev, n, name), _dev(x_o_dev, n, name) if x_o_dev is not None else None, _dev(b_e_dev, n, name))
+
+    def solve_schur_vec(self, x, b, tol=0.0, dagger=False, use_guess=False):
+        """Dhat x_e = b_e (dagger: Dhat^dagger x_e = b_e) on the even sites of fine fp64 Vectors; use_guess: x holds the guess.  On
+        return the odd sites of x hold the odd part of the full-lattice solution.  Returns (iterations, coarse_iterations, relres),
+        relres that of the Schur system"""
+        return self._schur_call("solve_schur_vec", (int(bool(dagger)), int(bool(use_guess))), (x._h, b._h), tol)
+
+    def solve_schur_device(self, x_e_dev, x_o_dev, b_e_dev, tol=0.0, dagger=False, use_guess=False):
+        """the same on half fields in device memory; x_o_dev (may be None) takes the odd part"""
+        return self._schur_call("solve_schur_device", (int(bool(dagger)), int(bool(use_guess))),
+                                self._halves("solve_schur_device", x_e_dev, x_o_dev, b_e_dev), tol)
+
+    def solve_schur_squared_vec(self, x, b, tol=0.0):
+        """Dhat^dagger Dhat x_e = b_e; returns the two pairs of counts and ||b_e - Dhat^dagger Dhat x_e|| / ||b_e|| as solve_squared_vec does"""
+        return self._schur_call("solve_schur_squared_vec", (), (x._h, b._h), tol, squared=True)
+
+    def solve_schur_squared_device(self, x_e_dev, x_o_dev, b_e_dev, tol=0.0):
+        return self._schur_call("solve_schur_squared_device", (), self._halves("solve_schur_squared_device", x_e_dev, x_o_dev, b_e_dev), tol, squared=True)
+
+    def clover_logdet(self, parity):
+        """(sum over the sites of `parity` of log|det D_ss|, sign of the product) of the operator as it is now; collective on a grid"""
+        ld = ctypes.c_double(0); sg = ctypes.c_int(0)
+        _check(self._lib.ddamg_hip_clover_logdet(self._h, int(parity), ctypes.byref(ld), ctypes.byref(sg)))
+        return ld.value, sg.value
 
     def preconditioner(self, in_lex):
         a = np.ascontiguousarray(in_lex, dtype=np.float64)

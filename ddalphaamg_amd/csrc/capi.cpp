@@ -704,6 +704,100 @@ int ddamg_hip_gamma5(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* 
   DDAMG_API_END
 }
 
+// ---- the even-odd preconditioned system: half fields, the Schur complement, log det of the clover blocks (eo_system.h) ----
+// what the half-field and Schur entry points ask of a vector: fine level; the parity table comes with the first operator
+static void require_eo_vec(const ddamg_hip_ctx* c, const ddamg_hip_vec* v, const char* name) {
+  DDAMG_REQUIRE(v, "null argument");
+  DDAMG_REQUIRE(v->level == 0, (std::string(name) + ": fine-level vectors expected").c_str());
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, (std::string(name) + ": no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)").c_str());
+}
+static void require_parity(int parity, const char* name) {
+  DDAMG_REQUIRE(parity == 0 || parity == 1, (std::string(name) + ": parity must be 0 (even) or 1 (odd)").c_str());
+}
+
+int ddamg_hip_vec_upload_parity_device(ddamg_hip_ctx* c, ddamg_hip_vec* v, int parity, const double* half_dev, int zero_other) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_eo_vec(c, v, "ddamg_hip_vec_upload_parity_device");
+  require_parity(parity, "ddamg_hip_vec_upload_parity_device");
+  ddamg_require_device_array(c, half_dev, sizeof(double) * vec_len(v) / 2, "ddamg_hip_vec_upload_parity_device");
+  with_vec(v, [&](auto* p) {
+    vec_from_half(p, half_dev, c->levels[0]->d_lex_of_site.get(), c->fop64.dev().parity, parity, zero_other != 0, false, v->V, c->stream);
+  });
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_vec_download_parity_device(ddamg_hip_ctx* c, const ddamg_hip_vec* v, int parity, double* half_dev) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_eo_vec(c, v, "ddamg_hip_vec_download_parity_device");
+  require_parity(parity, "ddamg_hip_vec_download_parity_device");
+  ddamg_require_device_array(c, half_dev, sizeof(double) * vec_len(v) / 2, "ddamg_hip_vec_download_parity_device");
+  with_vec(v, [&](const auto* p) {
+    vec_to_half(half_dev, p, c->levels[0]->d_lex_of_site.get(), c->fop64.dev().parity, parity, false, v->V, c->stream);
+  });
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_schur_apply(ddamg_hip_ctx* c, ddamg_hip_vec* out, const ddamg_hip_vec* in, int dagger) {
+  DDAMG_API_BEGIN
+  enter(c);
+  DDAMG_REQUIRE(out && in, "null argument");
+  require_eo_vec(c, out, "ddamg_hip_schur_apply");
+  require_eo_vec(c, in, "ddamg_hip_schur_apply");
+  DDAMG_REQUIRE(out->precision == in->precision, "precision mismatch");
+  DDAMG_REQUIRE(out->data.get() != in->data.get(), "in-place apply is not supported");
+  if (in->precision == 32) schur_apply<float>(c->fop32, vec_data<float>(out), vec_data<float>(in), dagger != 0, c->eo, c->stream);
+  else schur_apply<double>(c->fop64, vec_data<double>(out), vec_data<double>(in), dagger != 0, c->eo, c->stream);
+  DDAMG_API_END
+}
+
+int ddamg_hip_schur_apply_device(ddamg_hip_ctx* c, double* out_e_dev, const double* in_e_dev, int dagger) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_schur_apply_device";
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 12 * V;
+  ddamg_require_device_array(c, out_e_dev, nb, name);
+  ddamg_require_device_array(c, in_e_dev, nb, name);
+  ddamg_require_disjoint(out_e_dev, in_e_dev, nb, name);
+  DeviceBuffer<double> in, out;     // full-length vectors for this call only
+  in.alloc((size_t)24 * V);
+  out.alloc((size_t)24 * V);
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  const unsigned char* par = c->fop64.dev().parity;
+  vec_from_half<double>(in, in_e_dev, lex, par, 0, true, false, V, c->stream);
+  schur_apply<double>(c->fop64, out, in, dagger != 0, c->eo, c->stream);
+  vec_to_half<double>(out_e_dev, out, lex, par, 0, false, V, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_clover_logdet(ddamg_hip_ctx* c, int parity, double* log_abs_det, int* sign) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_clover_logdet";
+  DDAMG_REQUIRE(log_abs_det && sign, "null argument");
+  require_parity(parity, name);
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
+  DDAMG_REQUIRE(!c->levels[0]->geom.distributed() || c->comm != nullptr, "ddamg_hip_clover_logdet on a process grid sums over the processes: install a transport first");
+  ReduceWork& rw = blas_rw(c);
+  clover_logdet(c->fop64.clover_field(), c->fop64.dev().parity, parity, c->levels[0]->geom.V, rw, rw.d_result, c->stream);
+  publish_to_host(rw.d_result, 3, rw, c->stream);
+  wait_published(rw, c->stream);
+  DDAMG_REQUIRE(rw.h_result[2] == 0.0, parity ? "ddamg_hip_clover_logdet: a clover block on the odd sites (parity 1) is singular: zero or non-finite pivot"
+                                              : "ddamg_hip_clover_logdet: a clover block on the even sites (parity 0) is singular: zero or non-finite pivot");
+  *log_abs_det = rw.h_result[0];
+  *sign = ((long long)rw.h_result[1] & 1) ? -1 : 1;
+  DDAMG_API_END
+}
+
 int ddamg_hip_get_site_order(ddamg_hip_ctx* c, int level, int* lex_of_site) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c, "null context");   // host tables only: no device is selected

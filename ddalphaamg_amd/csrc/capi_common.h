@@ -47,6 +47,20 @@ void for_each_mg(ddamg_hip_ctx* c, F f) {
 template <typename MG> using real_of = typename std::remove_reference_t<MG>::real;
 template <typename P> using pointee = std::remove_pointer_t<P>;
 
+// the reduction workspace of the entry points that reduce outside a Krylov solver
+inline ReduceWork& blas_rw(ddamg_hip_ctx* c) {
+  if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
+  return c->rw_blas;
+}
+
+// the even-odd entry points: local and global parity agree, and every pair x = 2k, 2k+1 holds one site of each parity, only where
+// every local extent is even
+inline void require_even_extents(const ddamg_hip_ctx* c, const char* name) {
+  const Geometry& g = c->levels[0]->geom;
+  for (int mu = 0; mu < 4; mu++)
+    DDAMG_REQUIRE(g.L[mu] % 2 == 0, (std::string(name) + ": the even-odd entry points need even local lattice extents").c_str());
+}
+
 template <typename T> T* vec_data(const ddamg_hip_vec* v) { return reinterpret_cast<T*>(v->data.get()); }
 inline size_t vec_len(const ddamg_hip_vec* v) { return (size_t)v->V * v->ndof * 2; }   // in reals
 // f(float*) or f(double*) on the vector's numbers, by its precision

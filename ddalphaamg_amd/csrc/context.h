@@ -7,6 +7,7 @@
 #include "mg.h"
 #include "krylov.h"
 #include "bicgstab.h"
+#include "eo_system.h"
 #include "../../include/ddamg_hip.h"
 #include <vector>
 #include <memory>
@@ -102,6 +103,8 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   ddamg::OddEvenBicgstab<float> bicg32;
   ddamg::OddEvenBicgstab<double> bicg64;
   bool bicg_ready = false;
+  // the even-odd preconditioned system (ddamg_hip_schur_*, ddamg_hip_solve_schur_*): two work vectors per precision, from the first use on
+  ddamg::EoWork eo;
   // results of the last solve
   int last_iter = 0, last_coarse_iter = 0;
   double last_relres = 0;

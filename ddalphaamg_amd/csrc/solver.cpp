@@ -660,10 +660,6 @@ static auto store_lex(ddamg_hip_ctx* c, double* lex, double* st = nullptr, bool 
     if (st) DDAMG_HIP_CHECK(hipMemcpyAsync(lex, st, sizeof(double) * 24 * V, hipMemcpyDeviceToHost, c->stream));
   };
 }
-static ddamg::ReduceWork& blas_rw(ddamg_hip_ctx* c) {
-  if (!c->rw_blas_ready) { c->rw_blas.init(8); c->rw_blas_ready = true; }
-  return c->rw_blas;
-}
 // the two fine fp64 vectors of a *_vec solve
 static void require_solve_vecs(const ddamg_hip_vec* x, const ddamg_hip_vec* b, const char* msg) {
   DDAMG_REQUIRE(x && b, "null argument");
@@ -892,7 +888,171 @@ static void solve_squared_chrono_core(ddamg_hip_ctx* c, ddamg_hip_chrono* hy, dd
   if (relres) *relres = rr;
 }
 
+// ---- the even-odd preconditioned system  Dhat = D_ee - D_eo D_oo^-1 D_oe  (eo_system.h) ----------------------------------------
+// Ahat x_e = b_e, Ahat = Dhat or Dhat^dagger, through the identity [A^-1]_ee = Ahat^-1: the solve of the full system A E = (r, 0)
+// by solve_core gives E_e = Ahat^-1 r.  The full solve stops on the residual of the full system, which bounds the residual of
+// the Schur system only up to ||D_eo D_oo^-1||, so the loop measures the Schur residual itself with the fp64 operator and
+// corrects: r = b_e - Ahat x_e; done where ||r|| <= tol ||b||; else A E = (r, 0) from zero to tol ||b|| / ||r||, x_e += E_e.
+// At most MAX_SCHUR_SOLVES full solves: the cap makes the call terminate, relres says what was reached.
+// load_x(dst) fills the guess and load_b(dst) the right-hand side, both with zeros on the odd sites; store_x(src) takes the
+// full-lattice vector X with A X = (b_e, 0): x_e on the even sites, the odd part that belongs to it on the odd ones.  Everything
+// in the solver's layout.
+constexpr int MAX_SCHUR_SOLVES = 3;
+
+static void require_schur_solve(ddamg_hip_ctx* c, const char* name) {
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, "no operator set");
+  DDAMG_REQUIRE(c->par.method <= 0 || c->par.method == 5 || c->setup_done, "setup has not been run");
+}
+
+template <typename LoadX, typename LoadB, typename StoreX>
+static void solve_schur_core(ddamg_hip_ctx* c, bool dagger, bool use_guess, double tol, LoadX load_x, LoadB load_b, StoreX store_x, int* iterations,
+                             int* coarse_iterations, double* relres) {
+  const int V = c->levels[0]->geom.V;
+  const size_t n = (size_t)24 * V;
+  const View all = whole(n);
+  const unsigned char* parity = c->fop64.dev().parity;
+  if (!(tol > 0)) tol = c->par.tol;
+  DeviceBuffer<double> x, b, r, y;
+  for (DeviceBuffer<double>* p : {&x, &b, &r, &y}) p->alloc(n);
+  load_b(b);
+  if (use_guess) load_x(x); else vec_zero<double>(x, all, c->stream);
+  int it = 0, cit = 0;
+  double rr = 0;
+  c->last_history.clear();
+  for (int solves = 0;; solves++) {
+    // a zero start: r = b without an application (x is the zero vector); both norms from one reduction in either case
+    const bool zero_start = solves == 0 && !use_guess;
+    if (!zero_start) schur_apply<double>(c->fop64, y, x, dagger, c->eo, c->stream);
+    const auto [nb, nr] = residual_norms(c, r, b, zero_start ? x.get() : y.get());
+    if (!(nb > 0)) {
+      vec_zero<double>(x, all, c->stream);
+      rr = 0;
+      break;
+    }
+    rr = nr / nb;
+    if (nr <= tol * nb || solves == MAX_SCHUR_SOLVES) break;
+    int it1 = 0, cit1 = 0;
+    // the odd sites of r hold zeros: the right-hand side (r, 0).  The correction of Dhat^dagger through the gamma5 signs of the
+    // D^dagger solves.
+    solve_core(c, tol * (nb / nr), load_dev(c, r, dagger), [&](const double* E) {
+      parity_update<double>(x, E, parity, 0, ParityOp::Add, dagger, V, c->stream);
+    }, &it1, &cit1, nullptr);
+    it += it1; cit += cit1;
+  }
+  // X_o = -D_oo^-1 D_oe x_e (Dhat^dagger: -gamma5 D_oo^-1 D_oe gamma5 x_e), from the x_e that is returned
+  const double* t = schur_odd_part<double>(c->fop64, x, dagger, c->eo, c->stream);
+  parity_update<double>(x, t, parity, 1, ParityOp::MinusAssign, dagger, V, c->stream);
+  store_x(x);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->last_iter = it; c->last_coarse_iter = cit; c->last_relres = rr;
+  if (iterations) *iterations = it;
+  if (coarse_iterations) *coarse_iterations = cit;
+  if (relres) *relres = rr;
+}
+
+// Dhat^dagger Dhat x_e = b_e: y_e = Dhat^-dagger b_e, then x_e = Dhat^-1 y_e; y stays on the device and lives for this call only.
+// relres = ||b_e - Dhat^dagger Dhat x_e|| / ||b_e|| in fp64, of the system the caller asked for.
+template <typename LoadB, typename StoreX>
+static void solve_schur_squared_core(ddamg_hip_ctx* c, double tol, LoadB load_b, StoreX store_x, int* iterations, int* coarse_iterations, double* relres) {
+  const int V = c->levels[0]->geom.V;
+  const size_t n = (size_t)24 * V;
+  const View all = whole(n);
+  DeviceBuffer<double> y, t, u;
+  for (DeviceBuffer<double>* p : {&y, &t, &u}) p->alloc(n);
+  auto no_guess = [&](double* dst) { vec_zero<double>(dst, all, c->stream); };
+  solve_schur_core(c, true, false, tol, no_guess, load_b, [&](const double* X) {
+    c->fop64.parity_select(y, X, nullptr, 0, c->stream);      // y_e; the odd part of that solve is not wanted
+  }, iterations, coarse_iterations, nullptr);
+  double rr = 0;
+  solve_schur_core(c, false, false, tol, no_guess, load_dev(c, y), [&](const double* X) {
+    schur_apply<double>(c->fop64, t, X, false, c->eo, c->stream);
+    schur_apply<double>(c->fop64, u, t, true, c->eo, c->stream);
+    load_b(t);
+    const auto [nb, nr] = residual_norms(c, t, t, u);
+    rr = nb > 0 ? nr / nb : 0.0;
+    store_x(X);
+  }, iterations ? iterations + 1 : nullptr, coarse_iterations ? coarse_iterations + 1 : nullptr, nullptr);
+  c->last_relres = rr;
+  if (relres) *relres = rr;
+}
+
+// load / store callbacks of the Schur solves.  _vec: the even sites of a fine fp64 vector (its odd sites are not read); the
+// store writes the whole vector.  _device: half fields, the odd one optional.
+static auto load_even_vec(ddamg_hip_ctx* c, const double* v) {
+  return [=](double* dst) { c->fop64.parity_select(dst, v, nullptr, 0, c->stream); };
+}
+static auto load_even_half(ddamg_hip_ctx* c, const double* half_dev) {
+  return [=](double* dst) {
+    vec_from_half<double>(dst, half_dev, c->levels[0]->d_lex_of_site.get(), c->fop64.dev().parity, 0, true, false, c->levels[0]->geom.V, c->stream);
+  };
+}
+static auto store_halves(ddamg_hip_ctx* c, double* x_e_dev, double* x_o_dev) {
+  return [=](const double* src) {
+    const int* lex = c->levels[0]->d_lex_of_site.get();
+    const unsigned char* par = c->fop64.dev().parity;
+    vec_to_half<double>(x_e_dev, src, lex, par, 0, false, c->levels[0]->geom.V, c->stream);
+    if (x_o_dev) vec_to_half<double>(x_o_dev, src, lex, par, 1, false, c->levels[0]->geom.V, c->stream);
+  };
+}
+// the half fields of a Schur *_device solve: in the memory of the context's device, and apart; x_o_dev may be null
+static void require_device_halves(ddamg_hip_ctx* c, double* x_e_dev, double* x_o_dev, const double* b_e_dev, const char* name) {
+  const size_t nb = sizeof(double) * 12 * c->levels[0]->geom.V;
+  ddamg_require_device_array(c, x_e_dev, nb, name);
+  ddamg_require_device_array(c, b_e_dev, nb, name);
+  ddamg_require_disjoint(x_e_dev, b_e_dev, nb, name);
+  if (x_o_dev) {
+    ddamg_require_device_array(c, x_o_dev, nb, name);
+    ddamg_require_disjoint(x_o_dev, b_e_dev, nb, name);
+    ddamg_require_disjoint(x_o_dev, x_e_dev, nb, name);
+  }
+}
+
 extern "C" {
+
+int ddamg_hip_solve_schur_vec(ddamg_hip_ctx* c, int dagger, int use_guess, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations,
+                              int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_schur_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x != b, "solve_schur_vec: the solution and the right-hand side must be two vectors");
+  require_schur_solve(c, "ddamg_hip_solve_schur_vec");
+  solve_schur_core(c, dagger != 0, use_guess != 0, tol, load_even_vec(c, vec_data<double>(x)), load_even_vec(c, vec_data<double>(b)),
+                   store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_schur_device(ddamg_hip_ctx* c, int dagger, int use_guess, double* x_e_dev, double* x_o_dev, const double* b_e_dev, double tol,
+                                 int* iterations, int* coarse_iterations, double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_halves(c, x_e_dev, x_o_dev, b_e_dev, "ddamg_hip_solve_schur_device");
+  require_schur_solve(c, "ddamg_hip_solve_schur_device");
+  solve_schur_core(c, dagger != 0, use_guess != 0, tol, load_even_half(c, x_e_dev), load_even_half(c, b_e_dev), store_halves(c, x_e_dev, x_o_dev),
+                   iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_schur_squared_vec(ddamg_hip_ctx* c, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int iterations[2], int coarse_iterations[2],
+                                      double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_solve_vecs(x, b, "solve_schur_squared_vec needs fine-level fp64 vectors");
+  DDAMG_REQUIRE(x != b, "solve_schur_squared_vec: the solution and the right-hand side must be two vectors");
+  require_schur_solve(c, "ddamg_hip_solve_schur_squared_vec");
+  solve_schur_squared_core(c, tol, load_even_vec(c, vec_data<double>(b)), store_dev(c, vec_data<double>(x)), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_schur_squared_device(ddamg_hip_ctx* c, double* x_e_dev, double* x_o_dev, const double* b_e_dev, double tol, int iterations[2],
+                                         int coarse_iterations[2], double* relres) {
+  DDAMG_API_BEGIN
+  enter(c);
+  require_device_halves(c, x_e_dev, x_o_dev, b_e_dev, "ddamg_hip_solve_schur_squared_device");
+  require_schur_solve(c, "ddamg_hip_solve_schur_squared_device");
+  solve_schur_squared_core(c, tol, load_even_half(c, b_e_dev), store_halves(c, x_e_dev, x_o_dev), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
 
 int ddamg_hip_solve_guess(ddamg_hip_ctx* c, int system, double* x_lex, const double* b_lex, double tol, int* iterations, int* coarse_iterations,
                           double* relres, double* guess_relres) {

@@ -418,6 +418,67 @@ int ddamg_hip_solve_squared_chrono_vec(ddamg_hip_ctx* ctx, ddamg_hip_chrono* hy,
                                        double tol, int iterations[2], int coarse_iterations[2], double* relres);
 int ddamg_hip_solve_squared_chrono_device(ddamg_hip_ctx* ctx, ddamg_hip_chrono* hy, ddamg_hip_chrono* hx, double* x_dev_lex,
                                           const double* b_dev_lex, double tol, int iterations[2], int coarse_iterations[2], double* relres);
+/* ---- the even-odd preconditioned system (no library interface in the reference, which has the operator:
+ * apply_schur_complement_PRECISION, src/oddeven_generic.c:704-740) ---------------------------------------------------------
+ * Conventions of everything in this group:
+ *  - Parity.  The parity of a site is (t+z+y+x) mod 2 of its GLOBAL coordinates: 0 even, 1 odd.
+ *  - Every call refuses, with a message, a context in which a local lattice extent is odd.  With even extents local and global
+ *    parity agree, and every pair x = 2k, 2k+1 holds one site of each parity.
+ *  - Half field.  [V/2][12] complex fp64: the sites of ONE parity of the process's own lattice in lexicographic order (T,Z,Y,X, X
+ *    fastest); half index = lexicographic index >> 1.
+ *  - Full-length vectors (fine-level ddamg_hip_vec) keep their layout: results are defined on the even sites and the odd sites
+ *    hold zeros, unless stated otherwise below.
+ *  - Systems.  Dhat = D_ee - D_eo D_oo^-1 D_oe on the even sites (the asymmetric form), Dhat^dagger = gamma5 Dhat gamma5.  The
+ *    determinant factorises as det D = det D_oo * det Dhat; the symmetric form 1 - D_ee^-1 D_eo D_oo^-1 D_oe is D_ee^-1 Dhat.
+ * An operator must be set (the parity table comes with it).
+ *
+ * upload_parity_device: the half field half_dev becomes the sites of `parity` of v (fine level, precision 32 or 64; 32 rounds);
+ * zero_other != 0: the sites of the other parity become zero, else they are left alone.  download_parity_device: the reverse;
+ * the other parity is not read.  half_dev is checked as every *_device array is, with half the size. */
+int ddamg_hip_vec_upload_parity_device(ddamg_hip_ctx* ctx, ddamg_hip_vec* v, int parity, const double* half_dev, int zero_other);
+int ddamg_hip_vec_download_parity_device(ddamg_hip_ctx* ctx, const ddamg_hip_vec* v, int parity, double* half_dev);
+/* out = Dhat in (dagger != 0: Dhat^dagger in) on fine-level vectors of equal precision, 32 or 64, as ddamg_hip_dirac_apply takes
+ * them: two half-lattice launches of the hopping term with fused epilogues, t_o = D_oo^-1 D_oe in_e, out_e = D_ee in_e - D_eo t_o.
+ * The odd sites of `in` are not read, the odd sites of `out` become zero; out == in is refused.  The dagger form has the bits of
+ * ddamg_hip_gamma5, this call, ddamg_hip_gamma5.  Needs no setup and works on one-level contexts and process grids.  _device: the
+ * same on half fields of the even sites, fp64. */
+int ddamg_hip_schur_apply(ddamg_hip_ctx* ctx, ddamg_hip_vec* out, const ddamg_hip_vec* in, int dagger);
+int ddamg_hip_schur_apply_device(ddamg_hip_ctx* ctx, double* out_e_dev, const double* in_e_dev, int dagger);
+/* Dhat x_e = b_e (dagger != 0: Dhat^dagger x_e = b_e) through the identity [D^-1]_ee = Dhat^-1: the solve of the full system
+ * D E = (r_e, 0) by the solver of ddamg_hip_solve (ddamg_hip_solve_dagger) gives E_e = Dhat^-1 r_e, so every `method`, every
+ * `mixed_precision`, the hierarchy, mass shifts and process grids come along.  That solver stops on the residual of the full
+ * system, which is not the residual of this one, so the call measures its own: x_e = the guess (use_guess != 0: x holds it on
+ * entry) or 0; r = b_e - Dhat x_e with the fp64 operator; where ||r|| > tol ||b_e||, the full solve from zero to tol ||b_e|| / ||r||,
+ * x_e += E_e, and again -- at most two such corrections after the first solve, which makes the call terminate; it returns 0 then
+ * too, and relres says what was reached.  relres = ||b_e - Dhat x_e|| / ||b_e|| of the x_e that is returned, in fp64, relative to
+ * b.  The iteration counts are summed over the solves; ddamg_hip_residual_history is that of the last one.  A zero guess and
+ * use_guess = 0 give the same bits and counts; a guess that meets tol costs nothing and is returned as it is; b_e = 0 gives x = 0
+ * with zero counts.  tol <= 0: params.tol.  Refused before a setup as ddamg_hip_solve is.
+ * On return the odd sites of x (x_o_dev, which may be NULL) hold the odd part of the full-lattice vector X with D X = (b_e, 0):
+ * -D_oo^-1 D_oe x_e (dagger: -gamma5 D_oo^-1 D_oe gamma5 x_e, and D^dagger X = (b_e, 0)), computed from the returned x_e and so
+ * exact for it -- what the fermion force takes.  The odd sites of b, and of the guess, are not read.
+ * _vec: fine-level fp64 vectors, x != b.  _device: half fields in device memory, pairwise apart.
+ * Chronological stores (ddamg_hip_chrono_*) are not offered for these systems: `system` there stays 0 or 1; the guess argument
+ * here is what a caller's own extrapolation feeds. */
+int ddamg_hip_solve_schur_vec(ddamg_hip_ctx* ctx, int dagger, int use_guess, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                              int* iterations, int* coarse_iterations, double* relres);
+int ddamg_hip_solve_schur_device(ddamg_hip_ctx* ctx, int dagger, int use_guess, double* x_e_dev, double* x_o_dev, const double* b_e_dev, double tol,
+                                 int* iterations, int* coarse_iterations, double* relres);
+/* Dhat^dagger Dhat x_e = b_e as the two solves above back to back from zero, y_e = Dhat^-dagger b_e staying on the device.
+ * iterations[0], coarse_iterations[0]: the Dhat^dagger solve; [1]: the Dhat solve.  relres = ||b_e - Dhat^dagger Dhat x_e|| / ||b_e||
+ * in fp64, NOT promised to be below tol (it carries the condition of Dhat^dagger, as for ddamg_hip_solve_squared).  The odd part
+ * that is returned belongs to the second solve: -D_oo^-1 D_oe x_e. */
+int ddamg_hip_solve_schur_squared_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol,
+                                      int iterations[2], int coarse_iterations[2], double* relres);
+int ddamg_hip_solve_schur_squared_device(ddamg_hip_ctx* ctx, double* x_e_dev, double* x_o_dev, const double* b_e_dev, double tol,
+                                         int iterations[2], int coarse_iterations[2], double* relres);
+/* *log_abs_det = the sum over the sites of `parity` of log|det D_ss| (both 6x6 clover blocks of a site), *sign = the sign of the
+ * product of those determinants (+1 / -1), of the fp64 operator as it is NOW: it follows ddamg_hip_shift_mass,
+ * ddamg_hip_scale_clover and every set_gauge* / set_operator without an upload.  The blocks are eliminated in registers without
+ * pivoting, in the order of the inverse the odd-even kernels read; the sum is a fixed-order fp64 reduction (two calls give the same
+ * bits).  A zero or non-finite pivot is an error naming the parity, not a NaN.  Collective on a process grid: one all-reduce.  Needs
+ * no setup. */
+int ddamg_hip_clover_logdet(ddamg_hip_ctx* ctx, int parity, double* log_abs_det, int* sign);
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
