@@ -174,6 +174,9 @@ def load_library():
         "ddamg_hip_solve_schur_squared_vec": [vp, vp, vp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_solve_schur_squared_device": [vp, dp, dp, dp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_clover_logdet": [vp, ctypes.c_int, dp, ip],
+        "ddamg_hip_force_bilinear_vec": [vp, dp, vp, vp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_device": [vp, dp, dp, dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_logdet": [vp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -957,6 +960,27 @@ class Context:
         ld = ctypes.c_double(0); sg = ctypes.c_int(0)
         _check(self._lib.ddamg_hip_clover_logdet(self._h, int(parity), ctypes.byref(ld), ctypes.byref(sg)))
         return ld.value, sg.value
+
+    # ---- forces: the derivative of the operator that is set with respect to its links (include/ddamg_hip.h, "Forces") ----
+    def force_bilinear_vec(self, force_dev, y, x, coeff=1.0, accumulate=False):
+        """force_dev (+)= coeff * the force of Re <y, D x> for fine fp64 Vectors; force_dev: [V][4][9] complex float64 in device
+        memory, the layout of the links.  Returns force_dev"""
+        _check(self._lib.ddamg_hip_force_bilinear_vec(self._h, _dev(force_dev, self.volume(0) * 72, "force_bilinear_vec"), y._h, x._h, float(coeff),
+                                                      int(bool(accumulate))))
+        return force_dev
+
+    def force_bilinear_device(self, force_dev, y_dev, x_dev, coeff=1.0, accumulate=False):
+        """the same for lexicographic [V][12] complex float64 arrays in device memory; the same bits"""
+        V = self.volume(0)
+        _check(self._lib.ddamg_hip_force_bilinear_device(self._h, _dev(force_dev, V * 72, "force_bilinear_device"), _dev(y_dev, V * 24, "force_bilinear_device"),
+                                                         _dev(x_dev, V * 24, "force_bilinear_device"), float(coeff), int(bool(accumulate))))
+        return force_dev
+
+    def force_logdet(self, force_dev, parity, coeff=1.0, accumulate=False):
+        """force_dev (+)= coeff * the force of the sum over the sites of `parity` of log|det D_ss| (clover_logdet)"""
+        _check(self._lib.ddamg_hip_force_logdet(self._h, _dev(force_dev, self.volume(0) * 72, "force_logdet"), int(parity), float(coeff),
+                                                int(bool(accumulate))))
+        return force_dev
 
     def preconditioner(self, in_lex):
         a = np.ascontiguousarray(in_lex, dtype=np.float64)

@@ -209,6 +209,7 @@ static void upload_operator(ddamg_hip_ctx* c) {
   c->fop64.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
   c->fop32.upload(g, c->D_host.data(), c->clover_host.data(), c->knobs, c->stream);
   c->mirror_valid = true;
+  c->from_links = false;    // ddamg_hip_set_gauge sets it behind this call
   operator_replaced(c);
 }
 
@@ -252,6 +253,7 @@ static void links_to_operator(ddamg_hip_ctx* c, const double* hopp_dev, const do
   c->mirror_valid = false;
   std::vector<double>().swap(c->D_host);
   std::vector<double>().swap(c->clover_host);
+  c->from_links = hopp_dev == clover_dev;
   operator_replaced(c);
 }
 
@@ -293,6 +295,7 @@ int ddamg_hip_set_gauge2(ddamg_hip_ctx* c, const double* hopp_gauge_lex, const d
   const double pl = gauge_fields(c, clover_gauge_lex, anti_pbc, two ? D_unused.data() : c->D_host.data(), c->clover_host.data());
   if (plaquette) *plaquette = pl;
   upload_operator(c);
+  c->from_links = !two;
   DDAMG_API_END
 }
 int ddamg_hip_set_gauge(ddamg_hip_ctx* c, const double* gauge_lex, int anti_pbc, double* plaquette) { return ddamg_hip_set_gauge2(c, gauge_lex, gauge_lex, anti_pbc, plaquette); }
@@ -795,6 +798,80 @@ int ddamg_hip_clover_logdet(ddamg_hip_ctx* c, int parity, double* log_abs_det, i
                                               : "ddamg_hip_clover_logdet: a clover block on the even sites (parity 0) is singular: zero or non-finite pivot");
   *log_abs_det = rw.h_result[0];
   *sign = ((long long)rw.h_result[1] & 1) ? -1 : 1;
+  DDAMG_API_END
+}
+
+// ---- the fermion force: derivatives of the operator that is set with respect to its links (force.h) ----
+// what every force entry point asks of the context and of the output array, which must lie apart from [in, in + in_bytes) of each input
+static void require_force(const ddamg_hip_ctx* c, const double* force_dev, const char* name) {
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": the force on a process grid is not built yet (it needs the neighbours' shell of the site tensor "
+                                   "and of the links): single process only").c_str());
+  DDAMG_REQUIRE(c->have_operator, (std::string(name) + ": no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_gauge_device)").c_str());
+  DDAMG_REQUIRE(c->from_links, (std::string(name) + ": the operator did not come from one link field (ddamg_hip_set_operator and the two-field "
+                                "ddamg_hip_set_gauge2* forms have none behind them): set it with ddamg_hip_set_gauge* / ddamg_hip_load_ildg_conf").c_str());
+  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * g.V, name);
+}
+static void require_force_apart(const double* force_dev, const void* in, size_t in_bytes, size_t V, const char* name) {
+  const char* a = (const char*)force_dev; const char* b = (const char*)in;
+  DDAMG_REQUIRE(a + sizeof(double) * 72 * V <= b || b + in_bytes <= a, (std::string(name) + ": the output and the input array overlap").c_str());
+}
+static void force_bilinear_any(ddamg_hip_ctx* c, double* force_dev, const double* y, const double* x, double coeff, int accumulate) {
+  force_bilinear(c->fop64, c->levels[0]->geom.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, y, x, coeff, accumulate,
+                 force_dev, c->force, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+int ddamg_hip_force_bilinear_vec(ddamg_hip_ctx* c, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_force_bilinear_vec";
+  DDAMG_REQUIRE(y && x, "null argument");
+  DDAMG_REQUIRE(y->level == 0 && x->level == 0, "ddamg_hip_force_bilinear_vec: fine-level vectors expected");
+  DDAMG_REQUIRE(y->precision == 64 && x->precision == 64, "ddamg_hip_force_bilinear_vec: the force is computed in fp64: fp32 vectors are refused");
+  require_force(c, force_dev, name);
+  require_force_apart(force_dev, y->data.get(), y->data.bytes(), y->V, name);
+  require_force_apart(force_dev, x->data.get(), x->data.bytes(), x->V, name);
+  force_bilinear_any(c, force_dev, vec_data<double>(y), vec_data<double>(x), coeff, accumulate);
+  DDAMG_API_END
+}
+
+int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_force_bilinear_device";
+  require_force(c, force_dev, name);
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 24 * V;
+  ddamg_require_device_array(c, y_dev, nb, name);
+  ddamg_require_device_array(c, x_dev, nb, name);
+  require_force_apart(force_dev, y_dev, nb, V, name);
+  require_force_apart(force_dev, x_dev, nb, V, name);
+  if (!c->force.x.get()) { c->force.x.alloc((size_t)24 * V); c->force.y.alloc((size_t)24 * V); }
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  vec_from_lex<double>(c->force.y, y_dev, lex, V, 12, c->stream);
+  vec_from_lex<double>(c->force.x, x_dev, lex, V, 12, c->stream);
+  force_bilinear_any(c, force_dev, c->force.y, c->force.x, coeff, accumulate);
+  DDAMG_API_END
+}
+
+int ddamg_hip_force_logdet(ddamg_hip_ctx* c, double* force_dev, int parity, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_force_logdet";
+  require_parity(parity, name);
+  require_even_extents(c, name);
+  require_force(c, force_dev, name);
+  // the pivot check of ddamg_hip_clover_logdet: the inverse blocks of a singular block are not a derivative of anything
+  ReduceWork& rw = blas_rw(c);
+  clover_logdet(c->fop64.clover_field(), c->fop64.dev().parity, parity, c->levels[0]->geom.V, rw, rw.d_result, c->stream);
+  publish_to_host(rw.d_result, 3, rw, c->stream);
+  wait_published(rw, c->stream);
+  DDAMG_REQUIRE(rw.h_result[2] == 0.0, parity ? "ddamg_hip_force_logdet: a clover block on the odd sites (parity 1) is singular: zero or non-finite pivot"
+                                              : "ddamg_hip_force_logdet: a clover block on the even sites (parity 0) is singular: zero or non-finite pivot");
+  force_logdet(c->fop64, c->levels[0]->geom.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, parity, coeff, accumulate,
+               force_dev, c->force, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
   DDAMG_API_END
 }
 

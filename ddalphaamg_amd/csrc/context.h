@@ -8,6 +8,7 @@
 #include "krylov.h"
 #include "bicgstab.h"
 #include "eo_system.h"
+#include "force.h"
 #include "../../include/ddamg_hip.h"
 #include <vector>
 #include <memory>
@@ -70,6 +71,10 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   // whether D_host / clover_host show the operator that is set: cleared by ddamg_hip_set_gauge*_device, which fills neither; who
   // needs them then rebuilds them from the fp64 operator first (ddamg_hip_get_operator)
   bool mirror_valid = false;
+  // whether the operator came from ONE link field (ddamg_hip_set_gauge*, _set_gauge*_device, _load_ildg_conf; kept by shift_mass and
+  // scale_clover): then D and the clover term are functions of the links W = 2 D, which is what ddamg_hip_force_* differentiate.
+  // ddamg_hip_set_operator and the two-field ddamg_hip_set_gauge2* forms clear it
+  bool from_links = false;
   // scale_clover: unscaled fp64 copy of the clover field on the device while the operator is scaled (ddamg_hip_scale_clover)
   ddamg::DeviceBuffer<double> clover_base;
   double scale_even = 1.0, scale_odd = 1.0;
@@ -105,6 +110,8 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   bool bicg_ready = false;
   // the even-odd preconditioned system (ddamg_hip_schur_*, ddamg_hip_solve_schur_*): two work vectors per precision, from the first use on
   ddamg::EoWork eo;
+  // the fermion force (ddamg_hip_force_*): links, site tensors and per-plane parts, from the first use on
+  ddamg::ForceWork force;
   // results of the last solve
   int last_iter = 0, last_coarse_iter = 0;
   double last_relres = 0;

@@ -479,6 +479,40 @@ int ddamg_hip_solve_schur_squared_device(ddamg_hip_ctx* ctx, double* x_e_dev, do
  * bits).  A zero or non-finite pivot is an error naming the parity, not a NaN.  Collective on a process grid: one all-reduce.  Needs
  * no setup. */
 int ddamg_hip_clover_logdet(ddamg_hip_ctx* ctx, int parity, double* log_abs_det, int* sign);
+
+/* ---- Forces: the derivative of the operator that is set with respect to its links -------------------------------------------
+ * Let W_mu(x) be the links of the operator that is set: what D stores, times 2, with the anti-periodic sign in it.  Vary every
+ * link as  W_mu(x) -> exp(eps Omega_mu(x)) W_mu(x)  with Omega_mu(x) traceless anti-Hermitian: multiplication from the left, at the
+ * site that owns the link.  For the caller's links U this is the same variation, because the sign commutes.  For a real function S
+ * of the links, its force is the unique field G_mu(x) of traceless anti-Hermitian 3x3 matrices with
+ *     d/d eps S |_{eps=0} = sum_{x,mu} tr( Omega_mu(x) G_mu(x) )          (real for anti-Hermitian arguments)
+ * Equivalently G = TA(M) with TA(M) = 1/2 (M - M^dagger) - 1/6 tr(M - M^dagger) 1, where d/d eps S = sum Re tr(Omega M).
+ * The force field has the layout of the links: [V][4][9] complex fp64, lexicographic T,Z,Y,X with X fastest, directions T,Z,Y,X,
+ * in device memory.  Two functions S are built, both from
+ *     D psi(x) = C(x) psi(x) - sum_mu [ (W_mu(x)/2) (1 - gamma_mu) psi(x+mu) + (W_mu(x-mu)/2)^dagger (1 + gamma_mu) psi(x-mu) ]
+ *     C(x) = s(x) [ (4 + m0) - csw sum_{mu<nu} (gamma_mu gamma_nu) (x) F_mu_nu(x) ],   F_mu_nu = (Q_mu_nu - Q_mu_nu^dagger) / 16,
+ * Q the sum of the four leaves in the (mu, nu) plane and s(x) the ddamg_hip_scale_clover factor of the site's parity:
+ *   bilinear:     S = Re <Y, D X>  for two fine fp64 vectors;
+ *   determinant:  S = sum over the sites x of `parity` of log|det C(x)|  (what ddamg_hip_clover_logdet returns).
+ * force_dev (+)= coeff * G: accumulate == 0 writes, != 0 adds to what force_dev holds.  _vec takes fine fp64 vectors, _device
+ * lexicographic [V][12] complex arrays in device memory; both give the same bits.  x, y and the operator are never written, and no
+ * link is read from the caller: the links are those of the fp64 operator, so the force cannot belong to another field than the
+ * operator, whatever form the fp32 operator keeps its links in.  Everything is fp64 and free of atomics: two calls give the same
+ * bits.  Needs no setup.  The calls wait for their result.
+ * Two-flavour action S = phi^dagger (D^dagger D)^-1 phi:  X = (D^dagger D)^-1 phi, Y = D X, force = force_bilinear(Y, X, coeff = -2).
+ * Refused with a message, never computed:
+ *   - a context on a process grid: not built yet, because the derivative kernel would need the neighbours' shell of the site
+ *     tensor and of the links (the machinery of ddamg_hip_set_gauge_device_grid);
+ *   - an operator that did not come from ONE link field: ddamg_hip_set_operator and the two-field ddamg_hip_set_gauge2* forms
+ *     (two different fields) have none behind them.  ddamg_hip_set_gauge*, ddamg_hip_set_gauge*_device with one field and
+ *     ddamg_hip_load_ildg_conf qualify; ddamg_hip_shift_mass and ddamg_hip_scale_clover keep that;
+ *   - fp32 vectors; a parity outside 0 / 1; odd local extents (determinant); a force_dev that is not device memory of the
+ *     context's device, is too small, or overlaps an input;
+ *   - ddamg_hip_force_logdet on a singular block (the pivot check of ddamg_hip_clover_logdet). */
+int ddamg_hip_force_bilinear_vec(ddamg_hip_ctx* ctx, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate);
+int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* ctx, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate);
+int ddamg_hip_force_logdet(ddamg_hip_ctx* ctx, double* force_dev, int parity, double coeff, int accumulate);
+
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
