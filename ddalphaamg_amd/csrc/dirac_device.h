@@ -105,8 +105,10 @@ __device__ __forceinline__ void su3_mul(const T (&U)[18], const T (&h)[12], T (&
       for (int j = 0; j < 3; j++) {
         T ur = U[2 * (3 * i + j)], ui = U[2 * (3 * i + j) + 1];
         T hr = h[2 * (3 * s + j)], hi = h[2 * (3 * s + j) + 1];
-        re += ur * hr - ui * hi;
-        im += ur * hi + ui * hr;
+        // the fused steps of pk_cmac, spelled out: every instance of this product, packed or scalar, in whichever kernel the
+        // compiler meets it, rounds alike (a neighbour across a process boundary gets its product in the pack kernel)
+        re = fma(-hi, ui, fma(hr, ur, re));
+        im = fma(hi, ur, fma(hr, ui, im));
       }
       g[2 * (3 * s + i)] = re; g[2 * (3 * s + i) + 1] = im;
     }
@@ -135,10 +137,10 @@ __device__ __forceinline__ void su3_mul_dag(const T (&U)[18], const T (&h)[12], 
       T re = 0, im = 0;
 #pragma unroll
       for (int j = 0; j < 3; j++) {
-        T ur = U[2 * (3 * j + i)], ui = -U[2 * (3 * j + i) + 1];
+        T ur = U[2 * (3 * j + i)], ui = U[2 * (3 * j + i) + 1];
         T hr = h[2 * (3 * s + j)], hi = h[2 * (3 * s + j) + 1];
-        re += ur * hr - ui * hi;
-        im += ur * hi + ui * hr;
+        re = fma(ui, hi, fma(ur, hr, re));      // the fused steps of pk_cmac_conj
+        im = fma(-ui, hr, fma(ur, hi, im));
       }
       g[2 * (3 * s + i)] = re; g[2 * (3 * s + i) + 1] = im;
     }

@@ -296,12 +296,14 @@ def coarse_solve(Mc, Lc, n, b, tol, restart, max_restart):
 class Schwarz:
     SIGMA = [0, 1, 3, 2, 6, 4, 5, 7, 15, 14, 12, 13, 9, 11, 10, 8]   # src/schwarz_generic.c:335
 
-    def __init__(self, L, B, A, block_iter, method=2, ndof=12, odd_even=True):
+    def __init__(self, L, B, A, block_iter, method=2, ndof=12, odd_even=True, eps=0.0):
         """A: matrix of the level's operator (ndof per site; odd_even=False: MinRes on the whole block, the smoother of an
         intermediate level, coarse_block_operator src/coarse_operator_generic.c:208-235); blocks of extent B; the 8 block lists of the reference (colour x {inner, -boundary only,
         both boundaries, +boundary only}, src/schwarz_generic.c:383-428).  method: 1 additive, 2 red-black, 3 sixteen
-        colours (src/schwarz_generic.c:318-333; an odd number of blocks in a direction falls back to two colours)"""
-        self.A = A.tocsr(); self.block_iter = block_iter; self.method = method; self.odd_even = odd_even
+        colours (src/schwarz_generic.c:318-333; an odd number of blocks in a direction falls back to two colours).  eps: a MinRes
+        step whose <Dr,Dr> lies below it is skipped (local_xy_over_xx returns 0 below EPS_PRECISION, src/linalg_generic.c:164-166;
+        EPS_float = 1e-6 and EPS_double = 1e-14, src/main.h:45-46); 0 restates the arithmetic alone"""
+        self.A = A.tocsr(); self.block_iter = block_iter; self.method = method; self.odd_even = odd_even; self.eps = eps
         self.sixteen = method == 3 and all((L[mu] // B[mu]) % 2 == 0 for mu in range(4))
         c = coords(L)
         nblk = [L[mu] // B[mu] for mu in range(4)]
@@ -349,7 +351,7 @@ class Schwarz:
             for _ in range(self.block_iter):
                 Dr = Dbb @ rb
                 dn = np.vdot(Dr, Dr).real
-                alpha = np.vdot(Dr, rb) / dn if dn > 0 else 0.0
+                alpha = np.vdot(Dr, rb) / dn if dn > 0 and dn >= self.eps else 0.0
                 d = d + alpha * rb
                 rb = rb - alpha * Dr
             x[I] += d; latest[I] = d; r[I] = rb
@@ -362,7 +364,7 @@ class Schwarz:
         for _ in range(self.block_iter):                      # local_minres on the Schur complement
             Dr = Dee @ re - Deo @ Dinv.solve(Doe @ re)
             dn = np.vdot(Dr, Dr).real
-            alpha = np.vdot(Dr, re) / dn if dn > 0 else 0.0
+            alpha = np.vdot(Dr, re) / dn if dn > 0 and dn >= self.eps else 0.0
             de = de + alpha * re
             re = re - alpha * Dr
         do = Dinv.solve(ro - Doe @ de)
