@@ -177,6 +177,9 @@ def load_library():
         "ddamg_hip_force_bilinear_vec": [vp, dp, vp, vp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_bilinear_device": [vp, dp, dp, dp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_logdet": [vp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_vec_grid": [vp, dp, vp, vp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_device_grid": [vp, dp, dp, dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_logdet_grid": [vp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -980,6 +983,28 @@ class Context:
         """force_dev (+)= coeff * the force of the sum over the sites of `parity` of log|det D_ss| (clover_logdet)"""
         _check(self._lib.ddamg_hip_force_logdet(self._h, _dev(force_dev, self.volume(0) * 72, "force_logdet"), int(parity), float(coeff),
                                                 int(bool(accumulate))))
+        return force_dev
+
+    def force_bilinear_vec_grid(self, force_dev, y, x, coeff=1.0, accumulate=False):
+        """force_bilinear_vec on any process grid: this process's part of the force, the neighbours' shell of the links and of the site
+        tensor and their face of x and y exchanged device to device.  Collective: every process of the grid calls it, with a
+        transport installed.  On an undivided context it is force_bilinear_vec"""
+        _check(self._lib.ddamg_hip_force_bilinear_vec_grid(self._h, _dev(force_dev, self.volume(0) * 72, "force_bilinear_vec_grid"), y._h, x._h,
+                                                           float(coeff), int(bool(accumulate))))
+        return force_dev
+
+    def force_bilinear_device_grid(self, force_dev, y_dev, x_dev, coeff=1.0, accumulate=False):
+        """the same for this process's lexicographic [V_local][12] complex float64 arrays in device memory; the same bits"""
+        V = self.volume(0)
+        name = "force_bilinear_device_grid"
+        _check(self._lib.ddamg_hip_force_bilinear_device_grid(self._h, _dev(force_dev, V * 72, name), _dev(y_dev, V * 24, name), _dev(x_dev, V * 24, name),
+                                                              float(coeff), int(bool(accumulate))))
+        return force_dev
+
+    def force_logdet_grid(self, force_dev, parity, coeff=1.0, accumulate=False):
+        """force_logdet on any process grid (collective); `parity` is the global parity"""
+        _check(self._lib.ddamg_hip_force_logdet_grid(self._h, _dev(force_dev, self.volume(0) * 72, "force_logdet_grid"), int(parity), float(coeff),
+                                                     int(bool(accumulate))))
         return force_dev
 
     def preconditioner(self, in_lex):

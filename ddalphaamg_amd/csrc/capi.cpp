@@ -802,11 +802,16 @@ int ddamg_hip_clover_logdet(ddamg_hip_ctx* c, int parity, double* log_abs_det, i
 }
 
 // ---- the fermion force: derivatives of the operator that is set with respect to its links (force.h) ----
-// what every force entry point asks of the context and of the output array, which must lie apart from [in, in + in_bytes) of each input
-static void require_force(const ddamg_hip_ctx* c, const double* force_dev, const char* name) {
+// what every force entry point asks of the context and of the output array, which must lie apart from [in, in + in_bytes) of each input.
+// grid: the collective _grid entry points, which take any context; the others refuse a process grid.  Everything here is checked
+// before the first message of a collective call.
+static void require_force(const ddamg_hip_ctx* c, const double* force_dev, const char* name, bool grid) {
   const Geometry& g = c->levels[0]->geom;
-  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": the force on a process grid is not built yet (it needs the neighbours' shell of the site tensor "
-                                   "and of the links): single process only").c_str());
+  DDAMG_REQUIRE(grid || !g.distributed(), (std::string(name) + ": on a process grid the force needs the neighbours' shell of the links and of the site "
+                                           "tensor and their face of the vectors, so the call is collective there; this non-collective form is not built "
+                                           "yet for a process grid: use " + name + "_grid there (every process calls it, with a transport installed)").c_str());
+  DDAMG_REQUIRE(!g.distributed() || c->comm != nullptr, (std::string(name) + " on a process grid fetches the neighbours' shell: install a transport first "
+                                                         "(ddamg_hip_comm_init_rccl / ddamg_hip_comm_init_host / ddamg_hip_comm_init_mpi)").c_str());
   DDAMG_REQUIRE(c->have_operator, (std::string(name) + ": no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_gauge_device)").c_str());
   DDAMG_REQUIRE(c->from_links, (std::string(name) + ": the operator did not come from one link field (ddamg_hip_set_operator and the two-field "
                                 "ddamg_hip_set_gauge2* forms have none behind them): set it with ddamg_hip_set_gauge* / ddamg_hip_load_ildg_conf").c_str());
@@ -817,30 +822,43 @@ static void require_force_apart(const double* force_dev, const void* in, size_t 
   DDAMG_REQUIRE(a + sizeof(double) * 72 * V <= b || b + in_bytes <= a, (std::string(name) + ": the output and the input array overlap").c_str());
 }
 static void force_bilinear_any(ddamg_hip_ctx* c, double* force_dev, const double* y, const double* x, double coeff, int accumulate) {
-  force_bilinear(c->fop64, c->levels[0]->geom.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, y, x, coeff, accumulate,
-                 force_dev, c->force, c->stream);
+  const Geometry& g = c->levels[0]->geom;
+  if (g.distributed())
+    force_bilinear_grid(c->fop64, g, c->comm, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, y, x, coeff, accumulate, force_dev,
+                        c->force, c->stream);
+  else
+    force_bilinear(c->fop64, g.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, y, x, coeff, accumulate, force_dev, c->force,
+                   c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (g.distributed()) comm_release_device_staging(c->comm);     // the pinned staging of the host transport
 }
 
-int ddamg_hip_force_bilinear_vec(ddamg_hip_ctx* c, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate) {
-  DDAMG_API_BEGIN
+static void force_bilinear_vec_any(ddamg_hip_ctx* c, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate,
+                                   const char* name, bool grid) {
   enter(c);
-  const char* name = "ddamg_hip_force_bilinear_vec";
   DDAMG_REQUIRE(y && x, "null argument");
-  DDAMG_REQUIRE(y->level == 0 && x->level == 0, "ddamg_hip_force_bilinear_vec: fine-level vectors expected");
-  DDAMG_REQUIRE(y->precision == 64 && x->precision == 64, "ddamg_hip_force_bilinear_vec: the force is computed in fp64: fp32 vectors are refused");
-  require_force(c, force_dev, name);
+  DDAMG_REQUIRE(y->level == 0 && x->level == 0, (std::string(name) + ": fine-level vectors expected").c_str());
+  DDAMG_REQUIRE(y->precision == 64 && x->precision == 64, (std::string(name) + ": the force is computed in fp64: fp32 vectors are refused").c_str());
+  require_force(c, force_dev, name, grid);
   require_force_apart(force_dev, y->data.get(), y->data.bytes(), y->V, name);
   require_force_apart(force_dev, x->data.get(), x->data.bytes(), x->V, name);
   force_bilinear_any(c, force_dev, vec_data<double>(y), vec_data<double>(x), coeff, accumulate);
+}
+int ddamg_hip_force_bilinear_vec(ddamg_hip_ctx* c, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_vec_any(c, force_dev, y, x, coeff, accumulate, "ddamg_hip_force_bilinear_vec", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_bilinear_vec_grid(ddamg_hip_ctx* c, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_vec_any(c, force_dev, y, x, coeff, accumulate, "ddamg_hip_force_bilinear_vec_grid", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate) {
-  DDAMG_API_BEGIN
+static void force_bilinear_device_any(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate,
+                                      const char* name, bool grid) {
   enter(c);
-  const char* name = "ddamg_hip_force_bilinear_device";
-  require_force(c, force_dev, name);
+  require_force(c, force_dev, name, grid);
   const int V = c->levels[0]->geom.V;
   const size_t nb = sizeof(double) * 24 * V;
   ddamg_require_device_array(c, y_dev, nb, name);
@@ -852,26 +870,50 @@ int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* c, double* force_dev, const d
   vec_from_lex<double>(c->force.y, y_dev, lex, V, 12, c->stream);
   vec_from_lex<double>(c->force.x, x_dev, lex, V, 12, c->stream);
   force_bilinear_any(c, force_dev, c->force.y, c->force.x, coeff, accumulate);
+}
+int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_device_any(c, force_dev, y_dev, x_dev, coeff, accumulate, "ddamg_hip_force_bilinear_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_bilinear_device_grid(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_device_any(c, force_dev, y_dev, x_dev, coeff, accumulate, "ddamg_hip_force_bilinear_device_grid", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_force_logdet(ddamg_hip_ctx* c, double* force_dev, int parity, double coeff, int accumulate) {
-  DDAMG_API_BEGIN
+static void force_logdet_any(ddamg_hip_ctx* c, double* force_dev, int parity, double coeff, int accumulate, const char* name, bool grid) {
   enter(c);
-  const char* name = "ddamg_hip_force_logdet";
   require_parity(parity, name);
   require_even_extents(c, name);
-  require_force(c, force_dev, name);
-  // the pivot check of ddamg_hip_clover_logdet: the inverse blocks of a singular block are not a derivative of anything
+  require_force(c, force_dev, name, grid);
+  // the pivot check of ddamg_hip_clover_logdet: the inverse blocks of a singular block are not a derivative of anything.  On a
+  // process grid the flag is summed over the processes with the log det (sum_partials), so all of them refuse together, before
+  // any shell is sent
+  const Geometry& g = c->levels[0]->geom;
   ReduceWork& rw = blas_rw(c);
-  clover_logdet(c->fop64.clover_field(), c->fop64.dev().parity, parity, c->levels[0]->geom.V, rw, rw.d_result, c->stream);
+  clover_logdet(c->fop64.clover_field(), c->fop64.dev().parity, parity, g.V, rw, rw.d_result, c->stream);
   publish_to_host(rw.d_result, 3, rw, c->stream);
   wait_published(rw, c->stream);
-  DDAMG_REQUIRE(rw.h_result[2] == 0.0, parity ? "ddamg_hip_force_logdet: a clover block on the odd sites (parity 1) is singular: zero or non-finite pivot"
-                                              : "ddamg_hip_force_logdet: a clover block on the even sites (parity 0) is singular: zero or non-finite pivot");
-  force_logdet(c->fop64, c->levels[0]->geom.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, parity, coeff, accumulate,
-               force_dev, c->force, c->stream);
+  DDAMG_REQUIRE(rw.h_result[2] == 0.0, (std::string(name) + (parity ? ": a clover block on the odd sites (parity 1) is singular: zero or non-finite pivot"
+                                                                      : ": a clover block on the even sites (parity 0) is singular: zero or non-finite pivot")).c_str());
+  if (g.distributed())
+    force_logdet_grid(c->fop64, g, c->comm, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, parity, coeff, accumulate, force_dev,
+                      c->force, c->stream);
+  else
+    force_logdet(c->fop64, g.L, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, parity, coeff, accumulate, force_dev, c->force,
+                 c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (g.distributed()) comm_release_device_staging(c->comm);
+}
+int ddamg_hip_force_logdet(ddamg_hip_ctx* c, double* force_dev, int parity, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_logdet_any(c, force_dev, parity, coeff, accumulate, "ddamg_hip_force_logdet", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_logdet_grid(ddamg_hip_ctx* c, double* force_dev, int parity, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_logdet_any(c, force_dev, parity, coeff, accumulate, "ddamg_hip_force_logdet_grid", true);
   DDAMG_API_END
 }
 

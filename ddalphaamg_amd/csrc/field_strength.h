@@ -124,6 +124,17 @@ inline Shell make_shell(const int L[4], const bool split[4]) {
   return s;
 }
 
+// where the own site with lexicographic index lx lies in the extended array; t: its own T coordinate, where asked for
+DDAMG_FS_HD size_t extended_site(const Shell& s, size_t lx, int* t = nullptr) {
+  size_t r = lx;
+  const int x3 = (int)(r % s.L[3]); r /= s.L[3];
+  const int x2 = (int)(r % s.L[2]); r /= s.L[2];
+  const int x1 = (int)(r % s.L[1]); r /= s.L[1];
+  const int x0 = (int)r;
+  if (t) *t = x0;
+  return (size_t)(x0 + s.h[0]) * s.stride[0] + (size_t)(x1 + s.h[1]) * s.stride[1] + (size_t)(x2 + s.h[2]) * s.stride[2] + (size_t)(x3 + s.h[3]);
+}
+
 // W doubles moved by one thread: 2 (one 16-byte access) where every array involved is 16-byte aligned, 1 otherwise
 template <int W> struct Reals;
 template <> struct alignas(16) Reals<2> { double v[2]; };
@@ -138,12 +149,8 @@ DDAMG_FS_HD void extend_links(const Shell& s, const double* __restrict__ U, doub
   constexpr size_t PER_SITE = 72 / W;
   if (i >= s.V * PER_SITE) return;
   const size_t lx = i / PER_SITE; const int k = (int)(i - lx * PER_SITE) * W;   // first real inside the site
-  size_t r = lx;
-  const int x3 = (int)(r % s.L[3]); r /= s.L[3];
-  const int x2 = (int)(r % s.L[2]); r /= s.L[2];
-  const int x1 = (int)(r % s.L[1]); r /= s.L[1];
-  const int x0 = (int)r;
-  const size_t e = (size_t)(x0 + s.h[0]) * s.stride[0] + (size_t)(x1 + s.h[1]) * s.stride[1] + (size_t)(x2 + s.h[2]) * s.stride[2] + (size_t)(x3 + s.h[3]);
+  int x0;
+  const size_t e = extended_site(s, lx, &x0);
   Reals<W> v = *reinterpret_cast<const Reals<W>*>(U + lx * 72 + k);
   if (negate_last_t && k < 18 && x0 == s.L[0] - 1) {
 #pragma unroll
@@ -174,14 +181,19 @@ inline Slab make_slab(const Shell& s, int mu) {
 // the slab at own coordinate c of direction mu: c = L - 1 and 0 are packed, -1 and L are filled from what arrived
 inline Slab slab_at(const Shell& s, Slab b, int c) { b.first[b.mu] = c + s.h[b.mu]; return b; }
 
+// site `site` of the slab, in the slab's own lexicographic order, as a site of the extended array
+DDAMG_FS_HD size_t slab_site(const Shell& s, const Slab& b, size_t site) {
+  size_t r = site, e = 0;
+#pragma unroll
+  for (int d = 3; d >= 0; d--) { e += (size_t)(b.first[d] + (int)(r % b.n[d])) * s.stride[d]; r /= b.n[d]; }
+  return e;
+}
 // link_slab_pack_kernel (to_buffer) / link_slab_unpack_kernel, thread i of sites * 36: 16 bytes, consecutive threads consecutive
 // reals of a site; buf [sites][72] in the slab's own lexicographic order, the same on the sender and the receiver
 DDAMG_FS_HD void slab_copy(const Shell& s, const Slab& b, double* __restrict__ Ue, double* __restrict__ buf, size_t i, bool to_buffer) {
   if (i >= b.sites * 36) return;
   const size_t site = i / 36; const int k = (int)(i - site * 36) * 2;
-  size_t r = site, e = 0;
-#pragma unroll
-  for (int d = 3; d >= 0; d--) { e += (size_t)(b.first[d] + (int)(r % b.n[d])) * s.stride[d]; r /= b.n[d]; }
+  const size_t e = slab_site(s, b, site);
   Reals<2>* in_array = reinterpret_cast<Reals<2>*>(Ue + e * 72 + k);
   Reals<2>* in_buffer = reinterpret_cast<Reals<2>*>(buf + site * 72 + k);
   if (to_buffer) *in_buffer = *in_array; else *in_array = *in_buffer;

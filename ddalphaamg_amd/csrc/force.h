@@ -20,8 +20,13 @@
 // factors lie within one site of the link's own site.  clover_derivative_kernel is field_strength_kernel turned round: the same
 // 8 x 8 tile of one plane per wave, the same staged (8+2)^2 neighbourhood of W_mu and W_nu, and next to it that of A_p.
 //
+// On a process grid (the ddamg_hip_force_*_grid calls) who writes what stays as it is; only where a boundary thread reads from
+// changes: W and A live in arrays extended by a one-site shell of the neighbours' values in every split direction (fs::Shell), the
+// derivative kernel stages its neighbourhood through fs::extended_tile / fs::stage_offsets<true> as field_strength_kernel<true> does,
+// and the hopping part reads X and Y at x + mu from the face the + mu neighbour sent (Grid).
+//
 // The bodies are plain functions of (workgroup, thread) or of a site, so that a host program can run them thread by thread
-// (tests/native/clover_force_check.cpp does).
+// (tests/native/clover_force_check.cpp and force_shell_check.cpp do).
 #pragma once
 #include "field_strength.h"
 
@@ -71,6 +76,15 @@ struct Sites {
   const int* lex;                // [V] lexicographic index of every site
   const unsigned char* parity;   // [V]
   double csw, scale_even, scale_odd;
+};
+
+// what the site kernels of the ddamg_hip_force_*_grid calls need besides: the extended array A goes into (fs::Shell), and for every
+// split direction mu the spinors the + mu neighbour sent from its face x_mu = 0: X then Y, each a chunked-SoA fp64 field of F[mu]
+// face sites in slot order (geometry.h); a site with x_mu = L - 1 finds its slot as -1 - nb there
+struct Grid {
+  fs::Shell shell;
+  const double* face[4];
+  int F[4];
 };
 
 // real r of site s of a chunked-SoA fp64 field
@@ -128,11 +142,17 @@ DDAMG_FS_HD void add_outer(M3& out, cplx g, const cplx (&x)[12], int sx, const c
 //   Lambda_p(x)[b][a] = sum_{s,s'} (gamma_mu gamma_nu)[s][s'] X[s'][b](x) conj(Y[s][a](x)),
 // A[(p * 9 + r) * V + lex] (clover == 0: not written), and the hopping part of the four links the site owns,
 //   M_mu(x) = -1/2 W_mu(x) tr_spin[X(x+mu) Y(x)^dagger (1 - gamma_mu)] + 1/2 tr_spin[X(x) Y(x+mu)^dagger (1 + gamma_mu)] W_mu(x)^dagger,
-// anti-Hermitian part into slots[((mu * SLOTS + HOP_SLOT) * 9 + r) * V + lex]
+// anti-Hermitian part into slots[((mu * SLOTS + HOP_SLOT) * 9 + r) * V + lex].
+// GRID (gr: the process's Grid): A is the extended array [54][Ve] and the site writes its place in the interior; X and Y at x + mu
+// come from gr->face[mu] where the neighbour table holds a slot.  The sums and their order are those of the undivided lattice.
+template <bool GRID = false>
 DDAMG_FS_HD void site_force_tensor(const Sites& g, const Gammas& gm, const double* __restrict__ X, const double* __restrict__ Y,
-                                   const double* __restrict__ W, int clover, double* __restrict__ A, double* __restrict__ slots, size_t s) {
+                                   const double* __restrict__ W, int clover, double* __restrict__ A, double* __restrict__ slots, size_t s,
+                                   const Grid* gr = nullptr) {
   if (s >= g.V) return;
   const size_t V = g.V, lx = (size_t)g.lex[s];
+  size_t AV = V, ax = lx;     // sites of A and this site's place in it
+  if constexpr (GRID) { AV = gr->shell.Ve; ax = fs::extended_site(gr->shell, lx); }
   cplx x[12], y[12];
   load_spinor(X, V, s, x);
   load_spinor(Y, V, s, y);
@@ -153,15 +173,21 @@ DDAMG_FS_HD void site_force_tensor(const Sites& g, const Gammas& gm, const doubl
       double a9[9];
       pack_antihermitian(lam, f, a9);
 #pragma unroll
-      for (int r = 0; r < 9; r++) A[((size_t)p * 9 + r) * V + lx] = a9[r];
+      for (int r = 0; r < 9; r++) A[((size_t)p * 9 + r) * AV + ax] = a9[r];
     }
   }
 #pragma unroll
   for (int mu = 0; mu < 4; mu++) {   // unrolled: every spin index below is a constant, so the spinors stay in registers
-    const size_t n = (size_t)g.nb[(size_t)mu * V + s];
+    const int nb = g.nb[(size_t)mu * V + s];
     cplx xn[12], yn[12];
-    load_spinor(X, V, n, xn);
-    load_spinor(Y, V, n, yn);
+    if (GRID && nb < 0) {
+      const size_t F = (size_t)gr->F[mu], slot = (size_t)(-1 - nb);
+      load_spinor(gr->face[mu], F, slot, xn);
+      load_spinor(gr->face[mu] + 24 * F, F, slot, yn);
+    } else {
+      load_spinor(X, V, (size_t)nb, xn);
+      load_spinor(Y, V, (size_t)nb, yn);
+    }
     M3 pf, pb;     // tr_spin[X(x+mu) Y(x)^dagger (1 - gamma_mu)], tr_spin[X(x) Y(x+mu)^dagger (1 + gamma_mu)]
 #pragma unroll
     for (int k = 0; k < 9; k++) { pf.a[k] = cplx{0.0, 0.0}; pb.a[k] = cplx{0.0, 0.0}; }
@@ -196,13 +222,15 @@ DDAMG_FS_HD cplx herm6_entry(const double* b, int i, int j) {
 
 // force_inverse_tensor_kernel, one thread per site: A_p of  sum over the sites of parity `par` of log|det C(x)|,
 //   Lambda_p(x)[b][a] = sum_{s,s'} (gamma_mu gamma_nu)[s][s'] [C(x)^-1][s' b][s a]
-// from the inverse blocks the odd-even kernels read (clover_inv: 72 reals per site, chunked SoA), zero on the other parity
+// from the inverse blocks the odd-even kernels read (clover_inv: 72 reals per site, chunked SoA), zero on the other parity.
+// shell != nullptr: A is the extended array [54][Ve] of that shell and the site writes its place in the interior
 DDAMG_FS_HD void site_inverse_tensor(const Sites& g, const Gammas& gm, const double* __restrict__ clover_inv, int par,
-                                     double* __restrict__ A, size_t s) {
+                                     double* __restrict__ A, size_t s, const fs::Shell* shell = nullptr) {
   if (s >= g.V) return;
   const size_t V = g.V, lx = (size_t)g.lex[s];
+  const size_t AV = shell ? shell->Ve : V, ax = shell ? fs::extended_site(*shell, lx) : lx;
   if (g.parity[s] != par) {
-    for (int k = 0; k < 54; k++) A[(size_t)k * V + lx] = 0.0;
+    for (int k = 0; k < 54; k++) A[(size_t)k * AV + ax] = 0.0;
     return;
   }
   double inv[72];
@@ -233,12 +261,36 @@ DDAMG_FS_HD void site_inverse_tensor(const Sites& g, const Gammas& gm, const dou
     double a9[9];
     pack_antihermitian(lam, f, a9);
 #pragma unroll
-    for (int r = 0; r < 9; r++) A[((size_t)p * 9 + r) * V + lx] = a9[r];
+    for (int r = 0; r < 9; r++) A[((size_t)p * 9 + r) * AV + ax] = a9[r];
   }
 }
 
+// tensor_slab_pack_kernel (to_buffer) / tensor_slab_unpack_kernel, thread i of 54 * sites: one real of the slab `b` of the extended
+// array A [54][Ve]; buf [54][sites], component-major as A, the sites in the slab's own lexicographic order (fs::slab_site), the same
+// on the sender and the receiver.  Consecutive threads: consecutive sites of one component, which are consecutive reals of buf and,
+// along the slab's fastest direction, of A.  8-byte accesses: a row of the slab starts at any site of A, so a pair of sites is not
+// 16-byte aligned in general.
+DDAMG_FS_HD void tensor_slab_copy(const fs::Shell& s, const fs::Slab& b, double* __restrict__ A, double* __restrict__ buf, size_t i, bool to_buffer) {
+  if (i >= b.sites * 54) return;
+  const size_t comp = i / b.sites, site = i - comp * b.sites;
+  double* in_array = A + comp * s.Ve + fs::slab_site(s, b, site);
+  if (to_buffer) buf[i] = *in_array; else *in_array = buf[i];
+}
+
+// face_spinor_pack_kernel, thread i of 24 * F: complex k = i / F of (X, Y) (k < 12: X) at the face site of slot i % F, 16 bytes,
+// into buf: X then Y as chunked-SoA fields of F sites -- what Grid::face[mu] is on the receiver.  sites[slot]: the device site
+// with x_mu = 0 of that slot (Geometry::face_sites[4 + mu]).  Consecutive threads write consecutive 16 bytes.
+DDAMG_FS_HD void face_spinor_pack(const double* __restrict__ X, const double* __restrict__ Y, size_t V, const int* __restrict__ sites, size_t F,
+                                  double* __restrict__ buf, size_t i) {
+  if (i >= 24 * F) return;
+  const size_t k = i / F, slot = i - k * F;
+  const double* v = (k < 12 ? X : Y) + soa2(V, (size_t)sites[slot], 2 * (int)(k % 12));
+  *reinterpret_cast<fs::Reals<2>*>(buf + 2 * i) = *reinterpret_cast<const fs::Reals<2>*>(v);
+}
+
 // clover_derivative_kernel, step 2b, all threads: A of plane p on the staged neighbourhood, lds_a[e * APITCH + r]
-// (off: fs::stage_offsets of the tile)
+// (off: fs::stage_offsets of the tile).  On a process grid: V the sites of the extended array, t and off those of
+// fs::extended_tile and fs::stage_offsets<true>
 DDAMG_FS_HD void stage_tensor(const double* __restrict__ A, size_t V, int p, const fs::Tile& t, int tid, const size_t* off, double* lds_a) {
   for (int k = tid; k < fs::NEXT * 9; k += fs::THREADS) {
     const int r = k / fs::NEXT, e = k - r * fs::NEXT;      // consecutive threads: consecutive sites of one component
@@ -345,12 +397,19 @@ DDAMG_FS_HD void site_assemble(const double* __restrict__ slots, size_t V, size_
 }  // namespace ddamg
 
 #if defined(__HIPCC__)
+#include "extended_links.h"
 #include "fine_op.h"
+#include <memory>
 namespace ddamg {
 // work space of the force entry points, in the context from the first call on: the links, A (54 reals per site), the slots
 // (4 x 4 x 9) and, for the _device entry point, X and Y in the operator's layout
 struct ForceWork {
   DeviceBuffer<double> W, A, slots, x, y;
+  // the _grid entry points on a process grid, from the first such call on: W = 2 D and A extended by the neighbours' shell (the slab
+  // buffers of the links serve the tensor too: 54 reals per site against 72), and the face spinors of the hopping part
+  std::unique_ptr<ExtendedLinks> links;
+  DeviceBuffer<double> Ae, face_send, face_recv;
+  DeviceBuffer<int> face_sites;     // Geometry::face_sites[4 + mu] of the split directions, one after the other
 };
 // force_dev (+)= coeff * the force of Re <Y, D X> (x, y: fine fp64 vectors in the operator's layout; lex: the site table of level 0)
 void force_bilinear(const FineOp<double>& op, const int L[4], const int* lex, double csw, double scale_even, double scale_odd, const double* y,
@@ -358,5 +417,12 @@ void force_bilinear(const FineOp<double>& op, const int L[4], const int* lex, do
 // ... of the sum over the sites of parity `par` of log|det C(x)|
 void force_logdet(const FineOp<double>& op, const int L[4], const int* lex, double csw, double scale_even, double scale_odd, int par, double coeff,
                   int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
+// the same on a process grid (g.distributed()), collective: this process's part of the force; the neighbours' shell of W and of A
+// and their face spinors travel over comm (comm_sendrecv_device).  Messages per split direction: bilinear 1 (spinors), and with a
+// clover term 2 (links) + 2 (tensor) more; determinant 2 + 2, none without a clover term.
+void force_bilinear_grid(const FineOp<double>& op, const Geometry& g, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd,
+                         const double* y, const double* x, double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
+void force_logdet_grid(const FineOp<double>& op, const Geometry& g, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd, int par,
+                       double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
 }  // namespace ddamg
 #endif

@@ -1,10 +1,11 @@
 // gauge_device.hip -- clover term and plaquette on the device, for the own lattice of a single process and for the
-// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them for links in host memory, ExtendedLinks
-// below for links in device memory).
+// lattice extended by the neighbours' links on a process grid (gauge.cpp fetches them for links in host memory, ExtendedLinks,
+// extended_links.h, for links in device memory).
 // Reference: compute_clover_term src/dirac.c:24-58, Q / Qdiff / set_clover :304-402, calc_plaq :568-622.
 // One thread per lexicographic site; links are read straight from the reference layout [V][4][3x3] complex fp64.
 #include "gauge.h"
 #include "common.h"
+#include "extended_links.h"
 #include "field_strength.h"
 #include "geometry.h"
 #include "halo.h"
@@ -318,48 +319,32 @@ struct ResidentWork {
   double plaquette(hipStream_t st) { return plaquette_sum(st) / ((double)V * 6.0); }   // the average
 };
 
-// The lattice extended by the neighbours' links, on the device: the caller's links go into the interior (with the anti-periodic
-// sign, on the processes that hold the last global time slice), then the shell arrives direction by direction, device to device
-// (comm_sendrecv_device), each slab spanning what the directions before it brought so that the corners travel along -- a corner
-// of a (T, Z) plane comes from the diagonal process in two hops.  A full extended copy, not a compact shell next to the caller's
-// array: it costs one streaming pass and (E/L)^4 of the field for the duration of the call, and keeps the staging of
-// field_strength_kernel a sum of a row and a column offset.  All four links of a shell site travel (72 doubles), though the
-// leaves never read U_mu at x + mu: trimming the slab at L would save a quarter of half the messages and cost a second layout.
-struct ExtendedLinks {
-  fs::Shell shell;
-  DeviceBuffer<double> Ue, sbuf, rbuf;
-  explicit ExtendedLinks(const Geometry& g) : shell(fs::make_shell(g.L, g.split)) {
-    Ue.alloc(72 * shell.Ve);
-    size_t most = 0;
-    for (int mu = 0; mu < 4; mu++) if (shell.h[mu]) most = std::max(most, fs::make_slab(shell, mu).sites);
-    if (most) { sbuf.alloc(72 * most); rbuf.alloc(72 * most); }
-  }
-  // enqueued on st; collective over the process grid.  dU is read, never written.
-  void fill(const Geometry& g, Comm* comm, const double* dU, int anti_pbc, hipStream_t st) {
-    const int negate_last_t = (anti_pbc && g.pc[0] == g.P[0] - 1) ? 1 : 0;
-    if (reinterpret_cast<uintptr_t>(dU) % 16 == 0)
-      hipLaunchKernelGGL(links_extend_kernel<2>, dim3((unsigned)((shell.V * 36 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
-    else
-      hipLaunchKernelGGL(links_extend_kernel<1>, dim3((unsigned)((shell.V * 72 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
-    DDAMG_HIP_CHECK(hipGetLastError());
-    for (int mu = 0; mu < 4; mu++) {
-      if (!shell.h[mu]) continue;
-      const fs::Slab slab = fs::make_slab(shell, mu);
-      const unsigned blocks = (unsigned)((slab.sites * 36 + 255) / 256);
-      for (int side = 0; side < 2; side++) {
-        // side 0: my slice x_mu = L-1 goes to the +mu neighbour (its x_mu = -1); side 1: x_mu = 0 to the -mu neighbour (its x_mu = L)
-        const int src_c = side == 0 ? shell.L[mu] - 1 : 0, dst_c = side == 0 ? -1 : shell.L[mu];
-        hipLaunchKernelGGL(link_slab_pack_kernel, dim3(blocks), dim3(256), 0, st, sbuf, Ue, shell, fs::slab_at(shell, slab, src_c));
-        DDAMG_HIP_CHECK(hipGetLastError());
-        comm_sendrecv_device(comm, sbuf, g.neighbor_rank[side == 0 ? mu : 4 + mu], rbuf, g.neighbor_rank[side == 0 ? 4 + mu : mu],
-                             sizeof(double) * 72 * slab.sites, 100 + 2 * mu + side, st);
-        hipLaunchKernelGGL(link_slab_unpack_kernel, dim3(blocks), dim3(256), 0, st, Ue, rbuf, shell, fs::slab_at(shell, slab, dst_c));
-        DDAMG_HIP_CHECK(hipGetLastError());
-      }
+}  // namespace
+
+// ExtendedLinks (extended_links.h)
+void ExtendedLinks::fill(const Geometry& g, Comm* comm, const double* dU, int anti_pbc, hipStream_t st) {
+  const int negate_last_t = (anti_pbc && g.pc[0] == g.P[0] - 1) ? 1 : 0;
+  if (reinterpret_cast<uintptr_t>(dU) % 16 == 0)
+    hipLaunchKernelGGL(links_extend_kernel<2>, dim3((unsigned)((shell.V * 36 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
+  else
+    hipLaunchKernelGGL(links_extend_kernel<1>, dim3((unsigned)((shell.V * 72 + 255) / 256)), dim3(256), 0, st, Ue, dU, shell, negate_last_t);
+  DDAMG_HIP_CHECK(hipGetLastError());
+  for (int mu = 0; mu < 4; mu++) {
+    if (!shell.h[mu]) continue;
+    const fs::Slab slab = fs::make_slab(shell, mu);
+    const unsigned blocks = (unsigned)((slab.sites * 36 + 255) / 256);
+    for (int side = 0; side < 2; side++) {
+      // side 0: my slice x_mu = L-1 goes to the +mu neighbour (its x_mu = -1); side 1: x_mu = 0 to the -mu neighbour (its x_mu = L)
+      const int src_c = side == 0 ? shell.L[mu] - 1 : 0, dst_c = side == 0 ? -1 : shell.L[mu];
+      hipLaunchKernelGGL(link_slab_pack_kernel, dim3(blocks), dim3(256), 0, st, sbuf, Ue, shell, fs::slab_at(shell, slab, src_c));
+      DDAMG_HIP_CHECK(hipGetLastError());
+      comm_sendrecv_device(comm, sbuf, g.neighbor_rank[side == 0 ? mu : 4 + mu], rbuf, g.neighbor_rank[side == 0 ? 4 + mu : mu],
+                           sizeof(double) * 72 * slab.sites, 100 + 2 * mu + side, st);
+      hipLaunchKernelGGL(link_slab_unpack_kernel, dim3(blocks), dim3(256), 0, st, Ue, rbuf, shell, fs::slab_at(shell, slab, dst_c));
+      DDAMG_HIP_CHECK(hipGetLastError());
     }
   }
-};
-}  // namespace
+}
 
 double gauge_to_operator_resident(const int L[4], const double* dU_hopp, const double* dU_clover, int anti_pbc, double m0, double csw, double* dD,
                                   double* dC, hipStream_t st) {

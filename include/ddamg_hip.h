@@ -501,8 +501,9 @@ int ddamg_hip_clover_logdet(ddamg_hip_ctx* ctx, int parity, double* log_abs_det,
  * bits.  Needs no setup.  The calls wait for their result.
  * Two-flavour action S = phi^dagger (D^dagger D)^-1 phi:  X = (D^dagger D)^-1 phi, Y = D X, force = force_bilinear(Y, X, coeff = -2).
  * Refused with a message, never computed:
- *   - a context on a process grid: not built yet, because the derivative kernel would need the neighbours' shell of the site
- *     tensor and of the links (the machinery of ddamg_hip_set_gauge_device_grid);
+ *   - a context on a process grid: not built yet in these three non-collective forms, because the force needs the neighbours'
+ *     shell of the links, of the site tensor and of the vectors there, which makes the call collective.  Their _grid twins below
+ *     are built for it;
  *   - an operator that did not come from ONE link field: ddamg_hip_set_operator and the two-field ddamg_hip_set_gauge2* forms
  *     (two different fields) have none behind them.  ddamg_hip_set_gauge*, ddamg_hip_set_gauge*_device with one field and
  *     ddamg_hip_load_ildg_conf qualify; ddamg_hip_shift_mass and ddamg_hip_scale_clover keep that;
@@ -512,6 +513,21 @@ int ddamg_hip_clover_logdet(ddamg_hip_ctx* ctx, int parity, double* log_abs_det,
 int ddamg_hip_force_bilinear_vec(ddamg_hip_ctx* ctx, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate);
 int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* ctx, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate);
 int ddamg_hip_force_logdet(ddamg_hip_ctx* ctx, double* force_dev, int parity, double coeff, int accumulate);
+/* The same three on any process grid.  COLLECTIVE: every process of the grid calls them, with a transport installed (RCCL, host or
+ * MPI).  Definitions, layouts, coeff / accumulate and the refusals are those above; force_dev, y_dev and x_dev are the process's own
+ * part, [V_local][4][9] and [V_local][12] complex fp64, lexicographic in the local lattice; parity is the global parity.  Who writes
+ * what does not change (one thread per number, no atomics, two calls give the same bits); a boundary thread reads the neighbours'
+ * values, which travel device to device (comm_stats: "device_sendrecv"), per split direction of the grid:
+ *   - the shell of W = 2 D, one site deep, corners included: 2 messages of 576 bytes per slab site (clover term only);
+ *   - the shell of the site tensor A_p: 2 messages of 432 bytes per slab site, behind the tensor kernel (clover term only);
+ *   - X and Y in full on the face x_mu = 0, towards - mu: 1 message of 384 bytes per face site (bilinear only).
+ * The link shell is sent again on every call.  Everything that can be refused from what a process sees by itself (pointers, sizes,
+ * overlap, precision, parity range, the operator's origin, a missing transport) is refused before the first message; the singular
+ * block of ddamg_hip_force_logdet_grid is found in the all-reduce of ddamg_hip_clover_logdet, before any shell is sent, so every
+ * process returns the same error.  On a context that is not divided they are the calls above, bit for bit. */
+int ddamg_hip_force_bilinear_vec_grid(ddamg_hip_ctx* ctx, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate);
+int ddamg_hip_force_bilinear_device_grid(ddamg_hip_ctx* ctx, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate);
+int ddamg_hip_force_logdet_grid(ddamg_hip_ctx* ctx, double* force_dev, int parity, double coeff, int accumulate);
 
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
