@@ -173,6 +173,10 @@ def load_library():
         "ddamg_hip_solve_schur_device": [vp, ctypes.c_int, ctypes.c_int, dp, dp, dp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_solve_schur_squared_vec": [vp, vp, vp, ctypes.c_double, ip, ip, dp],
         "ddamg_hip_solve_schur_squared_device": [vp, dp, dp, dp, ctypes.c_double, ip, ip, dp],
+        "ddamg_hip_solve_schur_multishift_device": [vp, ctypes.c_int, dp, dp, ctypes.POINTER(dp), ctypes.POINTER(dp), dp, ctypes.c_int, ip, dp, dp],
+        "ddamg_hip_solve_schur_multishift_vec": [vp, ctypes.c_int, dp, dp, ctypes.POINTER(vp), vp, ctypes.c_int, ip, dp, dp],
+        "ddamg_hip_schur_odd_part_device": [vp, ctypes.c_int, dp, dp],
+        "ddamg_hip_multishift_update_time": [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)],
         "ddamg_hip_clover_logdet": [vp, ctypes.c_int, dp, ip],
         "ddamg_hip_force_bilinear_vec": [vp, dp, vp, vp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_bilinear_device": [vp, dp, dp, dp, ctypes.c_double, ctypes.c_int],
@@ -957,6 +961,51 @@ class Context:
 
     def solve_schur_squared_device(self, x_e_dev, x_o_dev, b_e_dev, tol=0.0):
         return self._schur_call("solve_schur_squared_device", (), self._halves("solve_schur_squared_device", x_e_dev, x_o_dev, b_e_dev), tol, squared=True)
+
+    def _multishift_call(self, name, shifts, tols, args, max_iterations):
+        n = len(shifts)
+        sh = (ctypes.c_double * max(n, 1))(*[float(s) for s in shifts])
+        if tols is not None and len(tols) != n:
+            raise DDAMGError(f"{name}: {len(tols)} tolerances for {n} shifts")
+        tl = (ctypes.c_double * max(n, 1))(*[float(t) for t in tols]) if tols is not None else None
+        it = (ctypes.c_int * max(n, 1))(); rr = (ctypes.c_double * max(n, 1))(); rz = (ctypes.c_double * 2)()
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, n, sh, tl, *args, int(max_iterations), it, rr, rz))
+        return list(it[:n]), list(rr[:n]), (rz[0], rz[1])
+
+    def solve_schur_multishift_vec(self, shifts, xs, b, tols=None, max_iterations=0):
+        """x_s = (Dhat^dagger Dhat + shifts[s])^-1 b_e for every shift from one Krylov space (multi-shift CG), on fine fp64 Vectors xs[s]:
+        x_s on their even sites, its odd part on the odd ones.  tols: None (params.tol) or one per shift.  Returns (iterations per
+        shift, relres per shift, (smallest, largest Ritz value of Dhat^dagger Dhat))"""
+        if len(xs) != len(shifts):
+            raise DDAMGError(f"solve_schur_multishift_vec: {len(xs)} vectors for {len(shifts)} shifts")
+        hs = (ctypes.c_void_p * max(len(xs), 1))(*[x._h for x in xs])
+        return self._multishift_call("solve_schur_multishift_vec", shifts, tols, (hs, b._h), max_iterations)
+
+    def solve_schur_multishift_device(self, shifts, x_e_devs, x_o_devs, b_e_dev, tols=None, max_iterations=0):
+        """the same on half fields in device memory; x_o_devs: None, or one entry per shift of which any may be None"""
+        name = "solve_schur_multishift_device"
+        n = self.volume(0) * 12
+        if len(x_e_devs) != len(shifts) or (x_o_devs is not None and len(x_o_devs) != len(shifts)):
+            raise DDAMGError(f"{name}: one array per shift expected")
+        dpp = ctypes.POINTER(ctypes.c_double)
+        xe = (dpp * max(len(shifts), 1))(*[_dev(a, n, name) for a in x_e_devs])
+        xo = None
+        if x_o_devs is not None:
+            xo = (dpp * max(len(shifts), 1))(*[_dev(a, n, name) if a is not None else dpp() for a in x_o_devs])
+        return self._multishift_call(name, shifts, tols, (xe, xo, _dev(b_e_dev, n, name)), max_iterations)
+
+    def schur_odd_part_device(self, x_o_dev, x_e_dev, dagger=False):
+        """x_o_dev = -D_oo^-1 D_oe x_e (dagger: -gamma5 D_oo^-1 D_oe gamma5 x_e) of the even half field x_e_dev; returns x_o_dev"""
+        n = self.volume(0) * 12
+        _check(self._lib.ddamg_hip_schur_odd_part_device(self._h, int(bool(dagger)), _dev(x_o_dev, n, "schur_odd_part_device"),
+                                                         _dev(x_e_dev, n, "schur_odd_part_device")))
+        return x_o_dev
+
+    def multishift_update_time(self, nshift, nactive, reps=20):
+        """milliseconds per launch of the multi-shift update kernel with the base system and `nactive` further shifts active"""
+        ms = ctypes.c_float(0)
+        _check(self._lib.ddamg_hip_multishift_update_time(self._h, int(nshift), int(nactive), int(reps), ctypes.byref(ms)))
+        return ms.value
 
     def clover_logdet(self, parity):
         """(sum over the sites of `parity` of log|det D_ss|, sign of the product) of the operator as it is now; collective on a grid"""

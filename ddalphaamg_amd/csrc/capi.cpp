@@ -781,6 +781,69 @@ int ddamg_hip_schur_apply_device(ddamg_hip_ctx* c, double* out_e_dev, const doub
   DDAMG_API_END
 }
 
+int ddamg_hip_schur_odd_part_device(ddamg_hip_ctx* c, int dagger, double* x_o_dev, const double* x_e_dev) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_schur_odd_part_device";
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, "no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)");
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 12 * V;
+  ddamg_require_device_array(c, x_o_dev, nb, name);
+  ddamg_require_device_array(c, x_e_dev, nb, name);
+  ddamg_require_disjoint(x_o_dev, x_e_dev, nb, name);
+  DeviceBuffer<double> X;     // a full-length vector for this call only
+  X.alloc((size_t)24 * V);
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  const unsigned char* par = c->fop64.dev().parity;
+  vec_from_half<double>(X, x_e_dev, lex, par, 0, true, false, V, c->stream);
+  // as solve_schur_core ends: X_o = -D_oo^-1 D_oe x_e (dagger: -gamma5 D_oo^-1 D_oe gamma5 x_e)
+  const double* t = schur_odd_part<double>(c->fop64, X, dagger != 0, c->eo, c->stream);
+  parity_update<double>(X, t, par, 1, ParityOp::MinusAssign, dagger != 0, V, c->stream);
+  vec_to_half<double>(x_o_dev, X, lex, par, 1, false, V, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_multishift_update_time(ddamg_hip_ctx* c, int nshift, int nactive, int reps, float* milliseconds) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_multishift_update_time";
+  DDAMG_REQUIRE(milliseconds, "null argument");
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(nshift >= 1 && nshift <= DDAMG_HIP_MAX_SHIFTS && nactive >= 0 && nactive < nshift && reps >= 1,
+                "ddamg_hip_multishift_update_time: 1 <= nshift <= DDAMG_HIP_MAX_SHIFTS, 0 <= nactive < nshift (the base system comes on top), reps >= 1");
+  const Geometry& g = c->levels[0]->geom;
+  const size_t n = (size_t)24 * g.V, half = n / 2;
+  multishift_prepare(c->ms, g.parity, c->stream);
+  ReduceWork& rw = c->ms.rw;
+  DeviceBuffer<double> p, r, slab;
+  p.alloc(n); r.alloc(n); slab.alloc(2 * (size_t)nshift * half);
+  vec_random<double>(p, n, 11, 0, c->stream);
+  vec_random<double>(r, n, 11, 1, c->stream);
+  vec_random<double>(slab, 2 * (size_t)nshift * half, 11, 2, c->stream);
+  // coefficients under which every field stays bounded over any number of launches: slot 0 is the base system, the last
+  // `nactive` slots are the active shifts
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));   // no upload of an earlier solve still reads h_coef
+  double* hc = rw.h_coef;
+  hc[0] = nactive; hc[1] = 0.5; hc[2] = 0.0; hc[3] = 0.0;
+  for (int a = 0; a < nactive; a++) {
+    double* e = hc + MS_COEF_HEAD + MS_COEF_PER * a;
+    e[0] = nshift - nactive + a; e[1] = 0.0; e[2] = 0.5; e[3] = 0.25;
+  }
+  upload_coefficients(rw, MS_COEF_HEAD + MS_COEF_PER * nactive, c->stream);
+  auto launch = [&] { multishift_update(p, r, slab, slab + (size_t)nshift * half, rw.d_coef, c->ms.even_site.get(), g.V, c->stream); };
+  launch();
+  DDAMG_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
+  for (int i = 0; i < reps; i++) launch();
+  DDAMG_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
+  DDAMG_HIP_CHECK(hipEventSynchronize(c->ev1));
+  float ms = 0;
+  DDAMG_HIP_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  *milliseconds = ms / reps;
+  DDAMG_API_END
+}
+
 int ddamg_hip_clover_logdet(ddamg_hip_ctx* c, int parity, double* log_abs_det, int* sign) {
   DDAMG_API_BEGIN
   enter(c);

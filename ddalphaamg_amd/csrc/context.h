@@ -9,6 +9,7 @@
 #include "bicgstab.h"
 #include "eo_system.h"
 #include "force.h"
+#include "multishift.h"
 #include "../../include/ddamg_hip.h"
 #include <vector>
 #include <memory>
@@ -112,6 +113,9 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   ddamg::EoWork eo;
   // the fermion force (ddamg_hip_force_*): links, site tensors and per-plane parts, from the first use on
   ddamg::ForceWork force;
+  // multi-shift CG on Dhat^dagger Dhat + sigma_s (ddamg_hip_solve_schur_multishift_*): the loop's reduction workspace and the list of
+  // even sites, from the first use on; the vectors of a solve live for the call
+  ddamg::MultishiftWork ms;
   // results of the last solve
   int last_iter = 0, last_coarse_iter = 0;
   double last_relres = 0;

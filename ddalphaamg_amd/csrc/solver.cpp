@@ -6,6 +6,7 @@
 #include "chrono.h"
 #include <cstring>
 #include <cstdio>
+#include <cmath>
 
 using namespace ddamg;
 
@@ -1008,6 +1009,150 @@ static void require_device_halves(ddamg_hip_ctx* c, double* x_e_dev, double* x_o
   }
 }
 
+// ---- multi-shift CG on A_s = Dhat^dagger Dhat + sigma_s (multishift.h) ---------------------------------------------------------
+// load_b(dst) fills the right-hand side with zeros on the odd sites; want_odd(s) says whether shift s gets its odd part
+// -D_oo^-1 D_oe x_s; store_x(s, X) takes the full-length vector of shift s (x_s on the even sites, the odd part or zeros on the odd
+// ones), all in the solver's layout.  Per iteration two read-backs (<p, A p> and <r, r>) through publish_to_host, one upload of the
+// coefficients, and on top of the four hopping launches of Dhat^dagger Dhat a dot product, the residual kernel and the update
+// kernel.  Works on a process grid as it is: schur_apply exchanges the faces and every reduction goes through rw.comm.
+static void require_multishift(const ddamg_hip_ctx* c, int nshift, const double* shifts, const char* name) {
+  const std::string n(name);
+  DDAMG_REQUIRE(shifts != nullptr, "null argument");
+  DDAMG_REQUIRE(nshift >= 1 && nshift <= DDAMG_HIP_MAX_SHIFTS, (n + ": nshift must lie between 1 and DDAMG_HIP_MAX_SHIFTS (32)").c_str());
+  for (int s = 0; s < nshift; s++)
+    DDAMG_REQUIRE(std::isfinite(shifts[s]) && shifts[s] >= 0, (n + ": every shift must be finite and not negative").c_str());
+  require_even_extents(c, name);
+  DDAMG_REQUIRE(c->have_operator, (n + ": no operator set (call ddamg_hip_set_gauge / ddamg_hip_set_operator)").c_str());
+  DDAMG_REQUIRE(!c->levels[0]->geom.distributed() || c->comm != nullptr, (n + " on a process grid is collective: install a transport first").c_str());
+}
+
+template <typename LoadB, typename WantOdd, typename StoreX>
+static void solve_schur_multishift_core(ddamg_hip_ctx* c, int nshift, const double* shifts, const double* tols, int max_iterations, LoadB load_b,
+                                        WantOdd want_odd, StoreX store_x, int* iterations, double* relres, double* ritz) {
+  const int V = c->levels[0]->geom.V;
+  const size_t n = (size_t)24 * V, half = (size_t)12 * V;
+  const View all = whole(n);
+  hipStream_t st = c->stream;
+  const unsigned char* parity = c->fop64.dev().parity;
+  multishift_prepare(c->ms, c->levels[0]->geom.parity, st);
+  ReduceWork& rw = c->ms.rw;
+  rw.comm = c->comm;
+  const int* even = c->ms.even_site.get();
+  const int maxit = max_iterations > 0 ? max_iterations : c->par.restart * c->par.max_restart;
+  int base = 0;
+  for (int s = 1; s < nshift; s++)
+    if (shifts[s] < shifts[base]) base = s;
+  const double sigma = shifts[base];
+  std::vector<double> tol(nshift);
+  for (int s = 0; s < nshift; s++) tol[s] = tols && tols[s] > 0 ? tols[s] : c->par.tol;
+
+  DeviceBuffer<double> b, r, p, t, u, slab;
+  for (DeviceBuffer<double>* v : {&b, &r, &p, &t, &u}) v->alloc(n);
+  slab.alloc(2 * (size_t)nshift * half);
+  double* xs = slab;
+  double* ps = slab + (size_t)nshift * half;
+  load_b(b);
+  vec_dot_and_norm2<double>(b, b, all, rw, rw.d_result, st);
+  publish_to_host(rw.d_result, 3, rw, st);
+  wait_published(rw, st);
+  const double bb = rw.h_result[2];
+  std::vector<int> its(nshift, 0);
+  std::vector<double> res(nshift, 0.0), al, be;
+  double rz[2] = {0, 0};
+  c->last_history.clear();
+  DDAMG_HIP_CHECK(hipMemsetAsync(slab.get(), 0, slab.bytes(), st));
+  if (bb > 0) {
+    const double nb = std::sqrt(bb);
+    vec_copy<double>(r, b, all, st);
+    vec_copy<double>(p, b, all, st);
+    for (int s = 0; s < nshift; s++)
+      if (s != base) multishift_gather(ps + s * half, b, even, V, st);
+    std::vector<double> zeta(nshift, 1.0), zeta_old(nshift, 1.0);
+    std::vector<char> active(nshift, 1);
+    int nactive = nshift, k = 0;
+    for (int s = 0; s < nshift; s++)
+      if (nb <= tol[s] * nb) { active[s] = 0; nactive--; }   // a tolerance of one or more: x_s = 0 meets it
+    double alpha_old = 1.0, beta_old = 0.0, rr = bb;
+    while (nactive > 0 && k < maxit) {
+      schur_apply<double>(c->fop64, t, p, false, c->eo, st);
+      schur_apply<double>(c->fop64, u, t, true, c->eo, st);
+      vec_dot_and_norm2<double>(p, u, all, rw, rw.d_result, st);
+      publish_to_host(rw.d_result, 3, rw, st);
+      wait_published(rw, st);
+      const double pAp = rw.h_result[0] + sigma * rw.h_result[2];
+      if (!(pAp > 0) || !std::isfinite(pAp)) break;   // the direction has run out: what is reached is reported
+      const double alpha = rr / pAp;
+      multishift_residual(r, u, p, alpha, sigma, even, V, rw, rw.d_result, st);
+      publish_to_host(rw.d_result, 1, rw, st);
+      wait_published(rw, st);
+      const double rr_new = rw.h_result[0];
+      k++;
+      const double beta = rr_new / rr, rnorm = std::sqrt(rr_new);
+      // INVARIANT (h_coef, krylov.h): written only here, after the wait above, which the previous upload cannot outlive
+      double* hc = rw.h_coef;
+      int na = 0;
+      hc[1] = beta; hc[2] = alpha; hc[3] = active[base] ? (double)base : -1.0;
+      for (int s = 0; s < nshift; s++) {
+        if (!active[s]) continue;
+        const double ds = shifts[s] - sigma;
+        const double zn = zeta[s] * zeta_old[s] * alpha_old / (alpha * beta_old * (zeta_old[s] - zeta[s]) + zeta_old[s] * alpha_old * (1.0 + ds * alpha));
+        bool done = false;
+        if (std::fpclassify(zn) != FP_NORMAL) {
+          done = true;   // its residual zeta_s r has left the number format: frozen as it is, without this step
+        } else {
+          const double ratio = zn / zeta[s];
+          if (s != base) {
+            double* e = hc + MS_COEF_HEAD + MS_COEF_PER * na++;
+            e[0] = (double)s; e[1] = alpha * ratio; e[2] = beta * ratio * ratio; e[3] = zn;
+          }
+          zeta_old[s] = zeta[s]; zeta[s] = zn;
+          done = std::fabs(zn) * rnorm <= tol[s] * nb;
+        }
+        its[s] = k;
+        if (done) { active[s] = 0; nactive--; }
+      }
+      hc[0] = (double)na;
+      upload_coefficients(rw, MS_COEF_HEAD + MS_COEF_PER * na, st);
+      multishift_update(p, r, xs, ps, rw.d_coef, even, V, st);
+      al.push_back(alpha); be.push_back(beta);
+      alpha_old = alpha; beta_old = beta; rr = rr_new;
+      c->last_history.push_back(rnorm / nb);
+    }
+    lanczos_extremes(al, be, rz);
+    if (!al.empty()) { rz[0] -= sigma; rz[1] -= sigma; }
+  }
+  // per shift: the residual of the x_s that is returned with the fp64 operator, its odd part, the store.  X and w reuse r and p.
+  double* X = r;
+  double* w = p;
+  int total = 0;
+  double worst = 0;
+  for (int s = 0; s < nshift; s++) {
+    vec_zero<double>(X, all, st);
+    if (bb > 0) {
+      multishift_scatter(X, xs + s * half, even, V, st);
+      schur_apply<double>(c->fop64, t, X, false, c->eo, st);
+      schur_apply<double>(c->fop64, u, t, true, c->eo, st);
+      vec_axpy<double>(w, u, X, shifts[s], 0.0, all, st);
+      const auto [nb, nr] = residual_norms(c, t, b, w);
+      res[s] = nb > 0 ? nr / nb : 0.0;
+      if (want_odd(s)) {
+        const double* o = schur_odd_part<double>(c->fop64, X, false, c->eo, st);
+        parity_update<double>(X, o, parity, 1, ParityOp::MinusAssign, false, V, st);
+      }
+    }
+    store_x(s, X);
+    total = std::max(total, its[s]);
+    worst = std::max(worst, res[s]);
+  }
+  DDAMG_HIP_CHECK(hipStreamSynchronize(st));
+  c->last_iter = total; c->last_coarse_iter = 0; c->last_relres = worst;
+  for (int s = 0; s < nshift; s++) {
+    if (iterations) iterations[s] = its[s];
+    if (relres) relres[s] = res[s];
+  }
+  if (ritz) { ritz[0] = rz[0]; ritz[1] = rz[1]; }
+}
+
 extern "C" {
 
 int ddamg_hip_solve_schur_vec(ddamg_hip_ctx* c, int dagger, int use_guess, ddamg_hip_vec* x, const ddamg_hip_vec* b, double tol, int* iterations,
@@ -1051,6 +1196,57 @@ int ddamg_hip_solve_schur_squared_device(ddamg_hip_ctx* c, double* x_e_dev, doub
   require_device_halves(c, x_e_dev, x_o_dev, b_e_dev, "ddamg_hip_solve_schur_squared_device");
   require_schur_solve(c, "ddamg_hip_solve_schur_squared_device");
   solve_schur_squared_core(c, tol, load_even_half(c, b_e_dev), store_halves(c, x_e_dev, x_o_dev), iterations, coarse_iterations, relres);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_schur_multishift_device(ddamg_hip_ctx* c, int nshift, const double* shifts, const double* tols, double* const* x_e_dev,
+                                            double* const* x_o_dev, const double* b_e_dev, int max_iterations, int* iterations, double* relres,
+                                            double ritz[2]) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_solve_schur_multishift_device";
+  DDAMG_REQUIRE(x_e_dev != nullptr, "null argument");
+  require_multishift(c, nshift, shifts, name);
+  const size_t nb = sizeof(double) * 12 * c->levels[0]->geom.V;
+  ddamg_require_device_array(c, b_e_dev, nb, name);
+  std::vector<double*> outs;
+  for (int s = 0; s < nshift; s++) {
+    outs.push_back(x_e_dev[s]);
+    if (x_o_dev && x_o_dev[s]) outs.push_back(x_o_dev[s]);
+  }
+  for (size_t i = 0; i < outs.size(); i++) {
+    ddamg_require_device_array(c, outs[i], nb, name);
+    ddamg_require_disjoint(outs[i], b_e_dev, nb, name);
+    for (size_t j = 0; j < i; j++)
+      DDAMG_REQUIRE(outs[i] + nb / sizeof(double) <= outs[j] || outs[j] + nb / sizeof(double) <= outs[i], (std::string(name) + ": two output arrays overlap").c_str());
+  }
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  const unsigned char* par = c->fop64.dev().parity;
+  const int V = c->levels[0]->geom.V;
+  solve_schur_multishift_core(c, nshift, shifts, tols, max_iterations, load_even_half(c, b_e_dev),
+                              [&](int s) { return x_o_dev && x_o_dev[s]; },
+                              [&](int s, const double* X) {
+                                vec_to_half<double>(x_e_dev[s], X, lex, par, 0, false, V, c->stream);
+                                if (x_o_dev && x_o_dev[s]) vec_to_half<double>(x_o_dev[s], X, lex, par, 1, false, V, c->stream);
+                              }, iterations, relres, ritz);
+  DDAMG_API_END
+}
+
+int ddamg_hip_solve_schur_multishift_vec(ddamg_hip_ctx* c, int nshift, const double* shifts, const double* tols, ddamg_hip_vec* const* x,
+                                         const ddamg_hip_vec* b, int max_iterations, int* iterations, double* relres, double ritz[2]) {
+  DDAMG_API_BEGIN
+  enter(c);
+  const char* name = "ddamg_hip_solve_schur_multishift_vec";
+  DDAMG_REQUIRE(x != nullptr && b != nullptr, "null argument");
+  require_multishift(c, nshift, shifts, name);
+  for (int s = 0; s < nshift; s++) {
+    require_solve_vecs(x[s], b, "solve_schur_multishift_vec needs fine-level fp64 vectors");
+    DDAMG_REQUIRE(x[s] != b, "solve_schur_multishift_vec: a solution and the right-hand side must be two vectors");
+    for (int t = 0; t < s; t++) DDAMG_REQUIRE(x[s] != x[t], "solve_schur_multishift_vec: the solutions must be distinct vectors");
+  }
+  solve_schur_multishift_core(c, nshift, shifts, tols, max_iterations, load_even_vec(c, vec_data<double>(b)), [](int) { return true; },
+                              [&](int s, const double* X) { vec_copy<double>(vec_data<double>(x[s]), X, whole((size_t)24 * c->levels[0]->geom.V), c->stream); },
+                              iterations, relres, ritz);
   DDAMG_API_END
 }
 

@@ -472,6 +472,50 @@ int ddamg_hip_solve_schur_squared_vec(ddamg_hip_ctx* ctx, ddamg_hip_vec* x, cons
                                       int iterations[2], int coarse_iterations[2], double* relres);
 int ddamg_hip_solve_schur_squared_device(ddamg_hip_ctx* ctx, double* x_e_dev, double* x_o_dev, const double* b_e_dev, double tol,
                                          int iterations[2], int coarse_iterations[2], double* relres);
+/* Multi-shift conjugate gradients: x_s = (Dhat^dagger Dhat + shifts[s])^-1 b_e for all nshift shifts from ONE Krylov space (B.
+ * Jegerlehner, hep-lat/9612014), what rational HMC needs for phi^dagger [a_0 + sum_s rho_s (Dhat^dagger Dhat + sigma_s)^-1] phi.  All
+ * fp64, no hierarchy involved: an operator is needed, a setup is not, and one-level contexts work.  On a process grid the call is
+ * collective (the operator's face exchange and the all-reduce of every inner product; nothing else is communicated).
+ *  - shifts: nshift numbers, finite and >= 0, in any order; a value may repeat, and equal shifts get equal bits.  The smallest one is
+ *    the base system, which runs plain CG; every other shift is updated from the same residual with its own three real scalars.
+ *    The result of a shift does not depend on its position or on which other (larger) shifts are asked for, bit for bit.
+ *  - tols: NULL for params.tol on every shift, else nshift numbers; an entry <= 0 means params.tol.  Shift s is converged at the first
+ *    iteration k with |zeta_s^k| ||r_k|| <= tols[s] ||b_e||, the norm of its recursed residual.  From then on its x_s is frozen: never
+ *    touched again, so a shift costs nothing after it has converged, and a run stopped at iterations[s] returns the same x_s.  A
+ *    shift whose zeta_s leaves the normal range of fp64 is frozen too.
+ *  - The loop ends when every shift is frozen, or after max_iterations (<= 0: params.restart * params.max_restart, as method -1).  The
+ *    call returns 0 then too; relres says what was reached.
+ *  - iterations[s] (may be NULL): the iteration at which shift s was frozen, or the length of the loop.  relres[s] (may be NULL):
+ *    ||b_e - (Dhat^dagger Dhat + shifts[s]) x_s|| / ||b_e|| of the x_s that is returned, recomputed with the fp64 operator (one Dhat^dagger
+ *    Dhat per shift); as the loop stops on the recursed residual, it meets tols[s] up to rounding, not exactly.
+ *  - ritz (may be NULL): ritz[0], ritz[1] = the smallest and largest eigenvalue of the Lanczos matrix of the base system, minus the base
+ *    shift: they lie inside the spectrum of Dhat^dagger Dhat and approach its ends from inside, for a caller that checks the interval
+ *    of its rational approximation.  Both 0 where no iteration ran.
+ *  - ddamg_hip_residual_history: ||r_k|| / ||b_e|| of the base system.  b_e = 0: every x_s = 0, zero counts, zero residuals.
+ *  - _device: x_e_dev[s], b_e_dev half fields in device memory; x_o_dev NULL, or nshift entries of which any may be NULL: where given,
+ *    the odd part -D_oo^-1 D_oe x_s of the full-lattice vector, as ddamg_hip_solve_schur_device returns it.  All arrays pairwise apart.
+ *    _vec: fine-level fp64 vectors, all distinct; the even sites of x[s] take x_s, the odd sites its odd part; the odd sites of b are not
+ *    read.  Both forms give the same bits.
+ *  - Memory: 2 nshift half fields (x_s and the search direction p_s of every shift, kept as packed even-site fields) and five
+ *    full-length vectors, for the call only.
+ * Refused with a message before any work: nshift outside 1 .. DDAMG_HIP_MAX_SHIFTS; a negative or non-finite shift; vectors that are not
+ * fine-level fp64; an x that is b, or two x that are one vector or overlapping arrays; arrays that are not memory of the context's device
+ * or too small; odd local extents; no operator. */
+enum { DDAMG_HIP_MAX_SHIFTS = 32 };
+int ddamg_hip_solve_schur_multishift_device(ddamg_hip_ctx* ctx, int nshift, const double* shifts, const double* tols, double* const* x_e_dev,
+                                            double* const* x_o_dev, const double* b_e_dev, int max_iterations, int* iterations, double* relres,
+                                            double ritz[2]);
+int ddamg_hip_solve_schur_multishift_vec(ddamg_hip_ctx* ctx, int nshift, const double* shifts, const double* tols, ddamg_hip_vec* const* x,
+                                         const ddamg_hip_vec* b, int max_iterations, int* iterations, double* relres, double ritz[2]);
+/* x_o = -D_oo^-1 D_oe x_e (dagger != 0: -gamma5 D_oo^-1 D_oe gamma5 x_e) of a given even half field: the odd part that the solves above
+ * and ddamg_hip_solve_schur_device return, with the same bits, for a vector that did not come out of a solve -- Y_s = Dhat x_s of the
+ * rational force takes the dagger form.  Half fields in device memory, apart from each other.  Needs an operator, no setup. */
+int ddamg_hip_schur_odd_part_device(ddamg_hip_ctx* ctx, int dagger, double* x_o_dev, const double* x_e_dev);
+/* Milliseconds per launch of the update kernel of the multi-shift solve on this context's lattice, between the context's timer events
+ * after one untimed launch: the base system and `nactive` of nshift - 1 further shifts active, on fields of random numbers that live
+ * for the call (algorithmic traffic 1 + 4 (nactive + 1) half fields per launch).  For measurements (tools/multishift_bench.py); needs
+ * no operator.  No counterpart in the reference. */
+int ddamg_hip_multishift_update_time(ddamg_hip_ctx* ctx, int nshift, int nactive, int reps, float* milliseconds);
 /* *log_abs_det = the sum over the sites of `parity` of log|det D_ss| (both 6x6 clover blocks of a site), *sign = the sign of the
  * product of those determinants (+1 / -1), of the fp64 operator as it is NOW: it follows ddamg_hip_shift_mass,
  * ddamg_hip_scale_clover and every set_gauge* / set_operator without an upload.  The blocks are eliminated in registers without
