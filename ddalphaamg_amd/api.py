@@ -7,6 +7,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBNAME = os.environ.get("DDAMG_HIP_LIBRARY") or os.path.join(_HERE, "libddamg_hip.so")
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddamg_hip.h")
 MAX_LEVELS = 4
+MAX_FORCE_PAIRS = 32      # DDAMG_HIP_MAX_FORCE_PAIRS
+FORCE_GROUP = 8           # DDAMG_HIP_FORCE_GROUP: the pairs of one launch of the many-pair force
 
 
 class DDAMGError(RuntimeError):
@@ -184,6 +186,12 @@ def load_library():
         "ddamg_hip_force_bilinear_vec_grid": [vp, dp, vp, vp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_bilinear_device_grid": [vp, dp, dp, dp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_logdet_grid": [vp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_multi_vec": [vp, dp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_multi_device": [vp, dp, ctypes.c_int, ctypes.POINTER(dp), ctypes.POINTER(dp), dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_multi_vec_grid": [vp, dp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_bilinear_multi_device_grid": [vp, dp, ctypes.c_int, ctypes.POINTER(dp), ctypes.POINTER(dp), dp, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_rational_device": [vp, dp, ctypes.c_int, dp, ctypes.POINTER(dp), ctypes.POINTER(dp), ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_force_rational_device_grid": [vp, dp, ctypes.c_int, dp, ctypes.POINTER(dp), ctypes.POINTER(dp), ctypes.c_double, ctypes.c_int],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -1055,6 +1063,58 @@ class Context:
         _check(self._lib.ddamg_hip_force_logdet_grid(self._h, _dev(force_dev, self.volume(0) * 72, "force_logdet_grid"), int(parity), float(coeff),
                                                      int(bool(accumulate))))
         return force_dev
+
+    def _force_multi_call(self, name, force_dev, ys, xs, weights, coeff, accumulate, convert, ptr):
+        n = len(weights)
+        if len(ys) != n or len(xs) != n:
+            raise DDAMGError(f"{name}: {len(ys)} y, {len(xs)} x for {n} weights: one of each per pair expected")
+        ya = (ptr * max(n, 1))(*[convert(a) for a in ys]); xa = (ptr * max(n, 1))(*[convert(a) for a in xs])
+        w = (ctypes.c_double * max(n, 1))(*[float(v) for v in weights])
+        _check(getattr(self._lib, "ddamg_hip_" + name)(self._h, _dev(force_dev, self.volume(0) * 72, name), n, ya, xa, w, float(coeff),
+                                                       int(bool(accumulate))))
+        return force_dev
+
+    def force_bilinear_multi_vec(self, force_dev, ys, xs, weights, coeff=1.0, accumulate=False, _name="force_bilinear_multi_vec"):
+        """force_dev (+)= coeff * sum_s weights[s] * the force of Re <ys[s], D xs[s]> for lists of fine fp64 Vectors, in one pass: the
+        links, the clover derivative and the assembly once, the pairs in groups of FORCE_GROUP.  A vector may repeat.  Returns force_dev"""
+        return self._force_multi_call(_name, force_dev, ys, xs, weights, coeff, accumulate, lambda v: v._h if v is not None else None,
+                                      ctypes.c_void_p)
+
+    def force_bilinear_multi_device(self, force_dev, y_devs, x_devs, weights, coeff=1.0, accumulate=False, _name="force_bilinear_multi_device"):
+        """the same for lists of lexicographic [V][12] complex float64 arrays in device memory; the same bits"""
+        n = self.volume(0) * 24
+        dpp = ctypes.POINTER(ctypes.c_double)
+        return self._force_multi_call(_name, force_dev, y_devs, x_devs, weights, coeff, accumulate, lambda a: _dev(a, n, _name) if a is not None else dpp(), dpp)
+
+    def force_bilinear_multi_vec_grid(self, force_dev, ys, xs, weights, coeff=1.0, accumulate=False):
+        """force_bilinear_multi_vec on any process grid (collective): the face spinors of a whole group travel in one message per
+        split direction.  On an undivided context it is force_bilinear_multi_vec"""
+        return self.force_bilinear_multi_vec(force_dev, ys, xs, weights, coeff, accumulate, _name="force_bilinear_multi_vec_grid")
+
+    def force_bilinear_multi_device_grid(self, force_dev, y_devs, x_devs, weights, coeff=1.0, accumulate=False):
+        return self.force_bilinear_multi_device(force_dev, y_devs, x_devs, weights, coeff, accumulate, _name="force_bilinear_multi_device_grid")
+
+    def force_rational_device(self, force_dev, rho, x_e_devs, x_o_devs=None, coeff=1.0, accumulate=False, _name="force_rational_device"):
+        """force_dev (+)= coeff * sum_s rho[s] * force_bilinear(Y_s, X_s) with X_s = (x_s, its odd part), Y_s = (Dhat x_s, its dagger odd
+        part), built on the device from the even half fields x_e_devs[s] as solve_schur_multishift_device returns them: coeff = -2 gives
+        the force of sum_s rho_s phi^dagger (Dhat^dagger Dhat + sigma_s)^-1 phi.  x_o_devs: None, or one entry per shift of which any may
+        be None: the odd part is computed inside where it is not given.  Returns force_dev"""
+        ns = len(rho)
+        n = self.volume(0) * 12
+        if len(x_e_devs) != ns or (x_o_devs is not None and len(x_o_devs) != ns):
+            raise DDAMGError(f"{_name}: one array per shift expected")
+        dpp = ctypes.POINTER(ctypes.c_double)
+        conv = lambda a: _dev(a, n, _name) if a is not None else dpp()
+        xe = (dpp * max(ns, 1))(*[conv(a) for a in x_e_devs])
+        xo = (dpp * max(ns, 1))(*[conv(a) for a in x_o_devs]) if x_o_devs is not None else None
+        r = (ctypes.c_double * max(ns, 1))(*[float(v) for v in rho])
+        _check(getattr(self._lib, "ddamg_hip_" + _name)(self._h, _dev(force_dev, self.volume(0) * 72, _name), ns, r, xe, xo, float(coeff),
+                                                        int(bool(accumulate))))
+        return force_dev
+
+    def force_rational_device_grid(self, force_dev, rho, x_e_devs, x_o_devs=None, coeff=1.0, accumulate=False):
+        """force_rational_device on any process grid (collective)"""
+        return self.force_rational_device(force_dev, rho, x_e_devs, x_o_devs, coeff, accumulate, _name="force_rational_device_grid")
 
     def preconditioner(self, in_lex):
         a = np.ascontiguousarray(in_lex, dtype=np.float64)

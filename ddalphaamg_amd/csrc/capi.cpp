@@ -5,7 +5,9 @@
 #include "ildg_device.h"
 #include "io_common.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <fcntl.h>
 
@@ -942,6 +944,161 @@ int ddamg_hip_force_bilinear_device(ddamg_hip_ctx* c, double* force_dev, const d
 int ddamg_hip_force_bilinear_device_grid(ddamg_hip_ctx* c, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate) {
   DDAMG_API_BEGIN
   force_bilinear_device_any(c, force_dev, y_dev, x_dev, coeff, accumulate, "ddamg_hip_force_bilinear_device_grid", true);
+  DDAMG_API_END
+}
+
+// ---- many pairs in one pass: force_dev (+)= coeff * sum_s weights[s] G(Y_s, X_s) (force.h: force_multi_*) ----
+static_assert(DDAMG_HIP_FORCE_GROUP == force::GROUP, "include/ddamg_hip.h and force.h disagree on the pairs of a launch");
+// the count, the arrays of pointers and the weights: what is checked before anything else is looked at
+static void require_force_pairs(int n, const void* a, const void* b, const double* weights, const char* count, const char* name) {
+  DDAMG_REQUIRE(n >= 1 && n <= DDAMG_HIP_MAX_FORCE_PAIRS,
+                (std::string(name) + ": " + count + " = " + std::to_string(n) + " is outside 1 .. DDAMG_HIP_MAX_FORCE_PAIRS (32)").c_str());
+  DDAMG_REQUIRE(a && b && weights, (std::string(name) + ": null argument (an array of pointers or the weights)").c_str());
+  for (int s = 0; s < n; s++)
+    DDAMG_REQUIRE(std::isfinite(weights[s]), (std::string(name) + ": weight " + std::to_string(s) + " is not finite").c_str());
+}
+// begin, the groups, end.  prepare(first, count, y, x): the vectors of the pairs first .. first + count - 1 in the operator's layout,
+// which may live in c->force.group -- the stream orders a group's kernels before the next group's conversion
+static void force_multi_run(ddamg_hip_ctx* c, double* force_dev, int n, const double* weights, double coeff, int accumulate,
+                            const std::function<void(int, int, const double**, const double**)>& prepare) {
+  const Geometry& g = c->levels[0]->geom;
+  ForceMulti m = force_multi_begin(c->fop64, g, c->comm, c->levels[0]->d_lex_of_site.get(), c->par.csw, c->scale_even, c->scale_odd, c->force, c->stream);
+  for (int first = 0; first < n; first += force::GROUP) {
+    const int count = std::min((int)force::GROUP, n - first);
+    const double* y[force::GROUP]; const double* x[force::GROUP];
+    prepare(first, count, y, x);
+    force_multi_group(m, g, c->comm, count, y, x, weights + first, c->force, c->stream);
+  }
+  force_multi_end(m, g, c->comm, coeff, accumulate, force_dev, c->force, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (g.distributed()) comm_release_device_staging(c->comm);
+}
+// X then Y of pair k of a group in the workspace of 2 GROUP full vectors, in the context from the first call on
+static double* force_group_vec(ddamg_hip_ctx* c, int k, bool is_y) {
+  const size_t n = (size_t)24 * c->levels[0]->geom.V;
+  if (!c->force.group.get()) c->force.group.alloc(2 * force::GROUP * n);
+  DDAMG_REQUIRE(c->force.group.bytes() == sizeof(double) * 2 * force::GROUP * n, "force workspace of another lattice");
+  return c->force.group.get() + (2 * (size_t)k + (is_y ? 1 : 0)) * n;
+}
+
+static void force_bilinear_multi_vec_any(ddamg_hip_ctx* c, double* force_dev, int npairs, const ddamg_hip_vec* const* y, const ddamg_hip_vec* const* x,
+                                         const double* weights, double coeff, int accumulate, const char* name, bool grid) {
+  enter(c);
+  require_force_pairs(npairs, y, x, weights, "npairs", name);
+  for (int s = 0; s < npairs; s++) {
+    DDAMG_REQUIRE(y[s] && x[s], (std::string(name) + ": null argument (vector " + std::to_string(s) + ")").c_str());
+    DDAMG_REQUIRE(y[s]->level == 0 && x[s]->level == 0, (std::string(name) + ": fine-level vectors expected").c_str());
+    DDAMG_REQUIRE(y[s]->precision == 64 && x[s]->precision == 64, (std::string(name) + ": the force is computed in fp64: fp32 vectors are refused").c_str());
+  }
+  require_force(c, force_dev, name, grid);
+  for (int s = 0; s < npairs; s++) {
+    require_force_apart(force_dev, y[s]->data.get(), y[s]->data.bytes(), y[s]->V, name);
+    require_force_apart(force_dev, x[s]->data.get(), x[s]->data.bytes(), x[s]->V, name);
+  }
+  force_multi_run(c, force_dev, npairs, weights, coeff, accumulate, [&](int first, int count, const double** yy, const double** xx) {
+    for (int k = 0; k < count; k++) { yy[k] = vec_data<double>(y[first + k]); xx[k] = vec_data<double>(x[first + k]); }
+  });
+}
+int ddamg_hip_force_bilinear_multi_vec(ddamg_hip_ctx* c, double* force_dev, int npairs, const ddamg_hip_vec* const* y, const ddamg_hip_vec* const* x,
+                                       const double* weights, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_multi_vec_any(c, force_dev, npairs, y, x, weights, coeff, accumulate, "ddamg_hip_force_bilinear_multi_vec", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_bilinear_multi_vec_grid(ddamg_hip_ctx* c, double* force_dev, int npairs, const ddamg_hip_vec* const* y, const ddamg_hip_vec* const* x,
+                                            const double* weights, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_multi_vec_any(c, force_dev, npairs, y, x, weights, coeff, accumulate, "ddamg_hip_force_bilinear_multi_vec_grid", true);
+  DDAMG_API_END
+}
+
+static void force_bilinear_multi_device_any(ddamg_hip_ctx* c, double* force_dev, int npairs, const double* const* y_dev, const double* const* x_dev,
+                                            const double* weights, double coeff, int accumulate, const char* name, bool grid) {
+  enter(c);
+  require_force_pairs(npairs, y_dev, x_dev, weights, "npairs", name);
+  for (int s = 0; s < npairs; s++)
+    DDAMG_REQUIRE(y_dev[s] && x_dev[s], (std::string(name) + ": null argument (array " + std::to_string(s) + ")").c_str());
+  require_force(c, force_dev, name, grid);
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 24 * V;
+  for (int s = 0; s < npairs; s++) {
+    ddamg_require_device_array(c, y_dev[s], nb, name);
+    ddamg_require_device_array(c, x_dev[s], nb, name);
+    require_force_apart(force_dev, y_dev[s], nb, V, name);
+    require_force_apart(force_dev, x_dev[s], nb, V, name);
+  }
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  force_multi_run(c, force_dev, npairs, weights, coeff, accumulate, [&](int first, int count, const double** yy, const double** xx) {
+    for (int k = 0; k < count; k++) {
+      double* X = force_group_vec(c, k, false); double* Y = force_group_vec(c, k, true);
+      vec_from_lex<double>(Y, y_dev[first + k], lex, V, 12, c->stream);
+      vec_from_lex<double>(X, x_dev[first + k], lex, V, 12, c->stream);
+      yy[k] = Y; xx[k] = X;
+    }
+  });
+}
+int ddamg_hip_force_bilinear_multi_device(ddamg_hip_ctx* c, double* force_dev, int npairs, const double* const* y_dev, const double* const* x_dev,
+                                          const double* weights, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_multi_device_any(c, force_dev, npairs, y_dev, x_dev, weights, coeff, accumulate, "ddamg_hip_force_bilinear_multi_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_bilinear_multi_device_grid(ddamg_hip_ctx* c, double* force_dev, int npairs, const double* const* y_dev, const double* const* x_dev,
+                                               const double* weights, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_bilinear_multi_device_any(c, force_dev, npairs, y_dev, x_dev, weights, coeff, accumulate, "ddamg_hip_force_bilinear_multi_device_grid", true);
+  DDAMG_API_END
+}
+
+// the rational force: X_s = (x_s, -D_oo^-1 D_oe x_s), Y_s = (Dhat x_s, -gamma5 D_oo^-1 D_oe gamma5 Dhat x_s), built group by group with
+// the functions behind ddamg_hip_schur_apply_device, ddamg_hip_schur_odd_part_device and ddamg_hip_vec_upload_parity_device
+static void force_rational_any(ddamg_hip_ctx* c, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
+                               const double* const* x_o_dev, double coeff, int accumulate, const char* name, bool grid) {
+  enter(c);
+  require_force_pairs(nshift, x_e_dev, x_e_dev, rho, "nshift", name);
+  for (int s = 0; s < nshift; s++) DDAMG_REQUIRE(x_e_dev[s], (std::string(name) + ": null argument (x_e_dev[" + std::to_string(s) + "])").c_str());
+  require_even_extents(c, name);
+  require_force(c, force_dev, name, grid);
+  const int V = c->levels[0]->geom.V;
+  const size_t nb = sizeof(double) * 12 * V;
+  for (int s = 0; s < nshift; s++) {
+    ddamg_require_device_array(c, x_e_dev[s], nb, name);
+    require_force_apart(force_dev, x_e_dev[s], nb, V, name);
+    if (x_o_dev && x_o_dev[s]) {
+      ddamg_require_device_array(c, x_o_dev[s], nb, name);
+      require_force_apart(force_dev, x_o_dev[s], nb, V, name);
+    }
+  }
+  const int* lex = c->levels[0]->d_lex_of_site.get();
+  const unsigned char* par = c->fop64.dev().parity;
+  force_multi_run(c, force_dev, nshift, rho, coeff, accumulate, [&](int first, int count, const double** yy, const double** xx) {
+    for (int k = 0; k < count; k++) {
+      const int s = first + k;
+      double* X = force_group_vec(c, k, false); double* Y = force_group_vec(c, k, true);
+      vec_from_half<double>(X, x_e_dev[s], lex, par, 0, true, false, V, c->stream);
+      schur_apply<double>(c->fop64, Y, X, false, c->eo, c->stream);
+      if (x_o_dev && x_o_dev[s]) {
+        vec_from_half<double>(X, x_o_dev[s], lex, par, 1, false, false, V, c->stream);
+      } else {
+        const double* t = schur_odd_part<double>(c->fop64, X, false, c->eo, c->stream);
+        parity_update<double>(X, t, par, 1, ParityOp::MinusAssign, false, V, c->stream);
+      }
+      const double* t = schur_odd_part<double>(c->fop64, Y, true, c->eo, c->stream);
+      parity_update<double>(Y, t, par, 1, ParityOp::MinusAssign, true, V, c->stream);
+      yy[k] = Y; xx[k] = X;
+    }
+  });
+}
+int ddamg_hip_force_rational_device(ddamg_hip_ctx* c, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
+                                    const double* const* x_o_dev, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_rational_any(c, force_dev, nshift, rho, x_e_dev, x_o_dev, coeff, accumulate, "ddamg_hip_force_rational_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_force_rational_device_grid(ddamg_hip_ctx* c, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
+                                         const double* const* x_o_dev, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  force_rational_any(c, force_dev, nshift, rho, x_e_dev, x_o_dev, coeff, accumulate, "ddamg_hip_force_rational_device_grid", true);
   DDAMG_API_END
 }
 

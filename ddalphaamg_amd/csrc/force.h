@@ -26,7 +26,7 @@
 // and the hopping part reads X and Y at x + mu from the face the + mu neighbour sent (Grid).
 //
 // The bodies are plain functions of (workgroup, thread) or of a site, so that a host program can run them thread by thread
-// (tests/native/clover_force_check.cpp and force_shell_check.cpp do).
+// (tests/native/clover_force_check.cpp, force_shell_check.cpp and force_multi_check.cpp do).
 #pragma once
 #include "field_strength.h"
 
@@ -209,6 +209,133 @@ DDAMG_FS_HD void site_force_tensor(const Sites& g, const Gammas& gm, const doubl
     pack_antihermitian(m, 1.0, h9);
 #pragma unroll
     for (int r = 0; r < 9; r++) slots[((size_t)(mu * SLOTS + HOP_SLOT) * 9 + r) * V + lx] = h9[r];
+  }
+}
+
+// ---- the tensor stage for many pairs (ddamg_hip_force_bilinear_multi_*, ddamg_hip_force_rational_*) ----
+// Everything behind the tensor stage is linear in A_p(x) and in the hopping matrices, and both are sums of outer products X Y^dagger:
+// sum_s w_s G(Y_s, X_s) needs one accumulation over the pairs and then the derivative and the assembly once.  A launch takes a group
+// of up to GROUP pairs by value; `add` says whether it writes A and the hopping slots or adds to what they hold, so more pairs are a
+// sequence of launches.  The sum runs over s in ascending order, every number has one writer, and two calls give the same bits.
+// Two bodies, because four spinors and all accumulators do not fit the registers of one thread:
+//   site_planes_multi   one thread per site: x_s, y_s of one pair at a time and the 54 packed reals of A as accumulators
+//   site_hop_multi      one thread per (site, mu): two spinors at a time and the two 3x3 spin traces as accumulators; W_mu(x) does
+//                       not depend on s and multiplies the sums once
+#ifndef DDAMG_FORCE_GROUP
+#define DDAMG_FORCE_GROUP 8
+#endif
+constexpr int GROUP = DDAMG_FORCE_GROUP;                // DDAMG_HIP_FORCE_GROUP of include/ddamg_hip.h
+struct Pairs {
+  const double* x[GROUP];
+  const double* y[GROUP];       // fine fp64 vectors in the operator's layout
+  double w[GROUP];
+  int n, add;                   // pairs in this group; add != 0: onto what A and the hopping slots hold
+};
+
+// force_planes_multi_kernel: A_p(x) (+)= sum_s w_s A_p(x) of site_force_tensor for the pair s, in the packed 9 reals per plane.
+// add: the sum starts from what A holds, so the result is the left fold over all pairs of all groups.  grid: the process
+// grid's form with its Grid gr, as site_force_tensor<true> -- a run-time choice in ONE kernel, so that the undivided lattice and a process grid run
+// the same instructions and give the same bits (the compiler contracts products and sums kernel by kernel)
+DDAMG_FS_HD void site_planes_multi(const Sites& g, const Gammas& gm, const Pairs& pr, double* __restrict__ A, size_t s, bool grid = false,
+                                   const Grid* gr = nullptr) {
+  if (s >= g.V) return;
+  const size_t V = g.V, lx = (size_t)g.lex[s];
+  size_t AV = V, ax = lx;
+  if (grid) { AV = gr->shell.Ve; ax = fs::extended_site(gr->shell, lx); }
+  double acc[6][9];
+#pragma unroll
+  for (int p = 0; p < 6; p++)
+#pragma unroll
+    for (int r = 0; r < 9; r++) acc[p][r] = pr.add ? A[((size_t)p * 9 + r) * AV + ax] : 0.0;
+  const double f = -g.csw * (g.parity[s] ? g.scale_odd : g.scale_even) / 8.0;
+#pragma unroll 1
+  for (int k = 0; k < pr.n; k++) {
+    cplx x[12], y[12];
+    load_spinor(pr.x[k], V, s, x);
+    load_spinor(pr.y[k], V, s, y);
+    const double fw = f * pr.w[k];
+#pragma unroll
+    for (int p = 0; p < 6; p++) {   // unrolled: the accumulators are registers.  Row sp of gamma_mu gamma_nu has its one entry in column sq
+      M3 lam;
+#pragma unroll
+      for (int q = 0; q < 9; q++) lam.a[q] = cplx{0.0, 0.0};
+#pragma unroll
+      for (int sp = 0; sp < 4; sp++) {
+        const int sq = gamma_col(fs::plane_nu(p), gamma_col(fs::plane_mu(p), sp));
+        add_outer(lam, cplx{gm.prod.re[p][4 * sp + sq], gm.prod.im[p][4 * sp + sq]}, x, sq, y, sp);
+      }
+      double a9[9];
+      pack_antihermitian(lam, fw, a9);
+#pragma unroll
+      for (int r = 0; r < 9; r++) acc[p][r] += a9[r];
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 6; p++)
+#pragma unroll
+    for (int r = 0; r < 9; r++) A[((size_t)p * 9 + r) * AV + ax] = acc[p][r];
+}
+
+// force_hop_multi_kernel, one thread per (site, MU): the hopping part of W_MU(x) of site_force_tensor for sum_s w_s (pair s),
+//   pf = sum_s w_s tr_spin[X_s(x+mu) Y_s(x)^dagger (1 - gamma_mu)],  pb = sum_s w_s tr_spin[X_s(x) Y_s(x+mu)^dagger (1 + gamma_mu)],
+// then  M = (pb W^dagger - W pf) / 2  once; anti-Hermitian part into (add: onto) the link's hopping slot.
+// grid: where the neighbour table holds -1 - slot, X_s and Y_s at x + mu come from gr->face[MU], which holds X then Y of every
+// pair of the group one after the other, 48 F doubles per pair
+template <int MU>
+DDAMG_FS_HD void site_hop_multi_dir(const Sites& g, const Gammas& gm, const Pairs& pr, const double* __restrict__ W, double* __restrict__ slots, size_t s,
+                                    bool grid, const Grid* gr) {
+  const size_t V = g.V, lx = (size_t)g.lex[s];
+  const int nb = g.nb[(size_t)MU * V + s];
+  M3 pf, pb;
+#pragma unroll
+  for (int q = 0; q < 9; q++) { pf.a[q] = cplx{0.0, 0.0}; pb.a[q] = cplx{0.0, 0.0}; }
+#pragma unroll 1
+  for (int k = 0; k < pr.n; k++) {
+    const double w = pr.w[k];
+    const double* fx = nullptr; size_t F = 0, slot = 0;
+    if (grid && nb < 0) { F = (size_t)gr->F[MU]; slot = (size_t)(-1 - nb); fx = gr->face[MU] + (size_t)k * 48 * F; }
+    {   // two spinors at a time: X(x+mu) and Y(x) ...
+      cplx xn[12], y[12];
+      if (grid && nb < 0) load_spinor(fx, F, slot, xn); else load_spinor(pr.x[k], V, (size_t)nb, xn);
+      load_spinor(pr.y[k], V, s, y);
+#pragma unroll
+      for (int sp = 0; sp < 4; sp++) {
+        add_outer(pf, cplx{w, 0.0}, xn, sp, y, sp);
+        add_outer(pf, cplx{-w * gm.re[MU][sp], -w * gm.im[MU][sp]}, xn, gamma_col(MU, sp), y, sp);
+      }
+    }
+    {   // ... then X(x) and Y(x+mu)
+      cplx x[12], yn[12];
+      load_spinor(pr.x[k], V, s, x);
+      if (grid && nb < 0) load_spinor(fx + 24 * F, F, slot, yn); else load_spinor(pr.y[k], V, (size_t)nb, yn);
+#pragma unroll
+      for (int sp = 0; sp < 4; sp++) {
+        add_outer(pb, cplx{w, 0.0}, x, sp, yn, sp);
+        add_outer(pb, cplx{w * gm.re[MU][sp], w * gm.im[MU][sp]}, x, gamma_col(MU, sp), yn, sp);
+      }
+    }
+  }
+  const M3 link = load_link(W, lx, MU);
+  const M3 m1 = fs::mul(link, pf), m2 = fs::mul(pb, fs::dag(link));
+  M3 m;
+#pragma unroll
+  for (int q = 0; q < 9; q++) m.a[q] = cplx{0.5 * (m2.a[q].r - m1.a[q].r), 0.5 * (m2.a[q].i - m1.a[q].i)};
+  double h9[9];
+  pack_antihermitian(m, 1.0, h9);
+#pragma unroll
+  for (int r = 0; r < 9; r++) {
+    double* o = slots + ((size_t)(MU * SLOTS + HOP_SLOT) * 9 + r) * V + lx;
+    *o = pr.add ? *o + h9[r] : h9[r];
+  }
+}
+DDAMG_FS_HD void site_hop_multi(const Sites& g, const Gammas& gm, const Pairs& pr, const double* __restrict__ W, double* __restrict__ slots, size_t s, int mu,
+                                bool grid = false, const Grid* gr = nullptr) {
+  if (s >= g.V) return;
+  switch (mu) {     // a constant direction in each body: every spin index is one too
+    case 0: site_hop_multi_dir<0>(g, gm, pr, W, slots, s, grid, gr); break;
+    case 1: site_hop_multi_dir<1>(g, gm, pr, W, slots, s, grid, gr); break;
+    case 2: site_hop_multi_dir<2>(g, gm, pr, W, slots, s, grid, gr); break;
+    default: site_hop_multi_dir<3>(g, gm, pr, W, slots, s, grid, gr); break;
   }
 }
 
@@ -405,8 +532,10 @@ namespace ddamg {
 // (4 x 4 x 9) and, for the _device entry point, X and Y in the operator's layout
 struct ForceWork {
   DeviceBuffer<double> W, A, slots, x, y;
+  DeviceBuffer<double> group;     // the many-pair _device and rational entry points: X then Y of the force::GROUP pairs of a group
   // the _grid entry points on a process grid, from the first such call on: W = 2 D and A extended by the neighbours' shell (the slab
-  // buffers of the links serve the tensor too: 54 reals per site against 72), and the face spinors of the hopping part
+  // buffers of the links serve the tensor too: 54 reals per site against 72), and the face spinors of the hopping part, of a
+  // whole group of pairs
   std::unique_ptr<ExtendedLinks> links;
   DeviceBuffer<double> Ae, face_send, face_recv;
   DeviceBuffer<int> face_sites;     // Geometry::face_sites[4 + mu] of the split directions, one after the other
@@ -424,5 +553,23 @@ void force_bilinear_grid(const FineOp<double>& op, const Geometry& g, Comm* comm
                          const double* y, const double* x, double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
 void force_logdet_grid(const FineOp<double>& op, const Geometry& g, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd, int par,
                        double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
+// force_dev (+)= coeff * sum_s weights[s] * the force of Re <Y_s, D X_s>, in three steps so that a caller can build the pairs of a
+// group in one workspace while the call runs: begin (the links once; on a process grid their shell), any number of groups of
+// 1 .. force::GROUP pairs (the tensor stage; on a process grid one message per split direction with the face spinors of the whole
+// group), end (with a clover term the shell of A and the derivative, then the assembly, all once).  g.distributed() chooses the form.
+struct ForceMulti {
+  force::Sites sites;
+  force::Grid grid;
+  const double* W = nullptr;
+  double* A = nullptr;
+  double* slots = nullptr;
+  bool clover = false, distributed = false;
+  int groups = 0;
+};
+ForceMulti force_multi_begin(const FineOp<double>& op, const Geometry& g, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd,
+                             ForceWork& w, hipStream_t st);
+void force_multi_group(ForceMulti& m, const Geometry& g, Comm* comm, int n, const double* const* y, const double* const* x, const double* weights,
+                       ForceWork& w, hipStream_t st);
+void force_multi_end(ForceMulti& m, const Geometry& g, Comm* comm, double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st);
 }  // namespace ddamg
 #endif

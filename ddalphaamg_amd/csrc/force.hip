@@ -4,6 +4,8 @@
 //   force_tensor_kernel / force_inverse_tensor_kernel    A_p per site and plane (+ the hopping part of the four own links)
 //   clover_derivative_kernel                 per plane tile: the plane's part of the two links every site owns (csw != 0 only)
 //   force_assemble_kernel                    sum of the slots, traceless part, times coeff into the caller's array
+// Many pairs (force_multi_*): force_planes_multi_kernel + force_hop_multi_kernel per group of force::GROUP pairs in place of
+// force_tensor_kernel; everything else once.
 // No atomics and no reduction: every number is written by one thread.
 // On a process grid (force_bilinear_grid / force_logdet_grid) the same kernels in their GRID / EXTENDED forms, and between them:
 //   face_spinor_pack_kernel + one message per split direction     X and Y of the face x_mu = 0 to the - mu neighbour (bilinear)
@@ -36,6 +38,22 @@ __global__ __launch_bounds__(128) void force_tensor_grid_kernel(force::Sites g, 
                                                                 const double* __restrict__ W, int clover, double* __restrict__ A, double* __restrict__ slots,
                                                                 force::Grid gr) {
   force::site_force_tensor<true>(g, gm, X, Y, W, clover, A, slots, (size_t)blockIdx.x * 128 + threadIdx.x, &gr);
+}
+
+// the tensor stage for a group of pairs (force.h): the six planes of a site, and the hopping part of one link per thread, y = mu
+// grid != 0: on a process grid (gr).  One kernel for both, so that both give the same bits
+__global__ __launch_bounds__(128) void force_planes_multi_kernel(force::Sites g, force::Gammas gm, force::Pairs pr, double* __restrict__ A, int grid,
+                                                                 force::Grid gr) {
+  force::site_planes_multi(g, gm, pr, A, (size_t)blockIdx.x * 128 + threadIdx.x, grid != 0, &gr);
+}
+__global__ __launch_bounds__(128) void force_hop_multi_kernel(force::Sites g, force::Gammas gm, force::Pairs pr, const double* __restrict__ W,
+                                                              double* __restrict__ slots, int grid, force::Grid gr) {
+  force::site_hop_multi(g, gm, pr, W, slots, (size_t)blockIdx.x * 128 + threadIdx.x, (int)blockIdx.y, grid != 0, &gr);
+}
+// y = the pair of the group: its X and Y of the face, 48 F doubles, behind those of the pairs before it
+__global__ __launch_bounds__(256) void face_spinor_pack_multi_kernel(double* __restrict__ buf, force::Pairs pr, size_t V, const int* __restrict__ sites, size_t F) {
+  const int k = blockIdx.y;
+  force::face_spinor_pack(pr.x[k], pr.y[k], V, sites, F, buf + (size_t)k * 48 * F, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 // EXTENDED: A is the extended array of `shell`
@@ -141,8 +159,8 @@ void grid_work(ForceWork& w, const Geometry& g, hipStream_t st) {
   w.face_sites.alloc(sites.size());
   DDAMG_HIP_CHECK(hipMemcpyAsync(w.face_sites, sites.data(), sizeof(int) * sites.size(), hipMemcpyHostToDevice, st));
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));     // `sites` goes
-  w.face_send.alloc(48 * most);
-  w.face_recv.alloc(48 * sites.size());
+  w.face_send.alloc(48 * most * force::GROUP);     // of a whole group of pairs (force_multi_group)
+  w.face_recv.alloc(48 * sites.size() * force::GROUP);
 }
 
 // X and Y of the face x_mu = 0 to the - mu neighbour, those of the + mu neighbour's into w.face_recv: one message per split direction
@@ -160,6 +178,26 @@ force::Grid exchange_face_spinors(const Geometry& g, Comm* comm, const double* x
                        w.face_sites + first, F);
     DDAMG_HIP_CHECK(hipGetLastError());
     comm_sendrecv_device(comm, w.face_send, g.neighbor_rank[4 + mu], recv, g.neighbor_rank[mu], sizeof(double) * 48 * F, 140 + mu, st);
+    first += F;
+  }
+  return gr;
+}
+
+// the same for the pairs of a group: X then Y of every pair, one after the other, in ONE message per split direction
+force::Grid exchange_face_spinors_multi(const Geometry& g, Comm* comm, const force::Pairs& pr, ForceWork& w, hipStream_t st) {
+  force::Grid gr;
+  gr.shell = w.links->shell;
+  size_t first = 0;
+  for (int mu = 0; mu < 4; mu++) {
+    gr.face[mu] = nullptr; gr.F[mu] = 0;
+    if (!g.split[mu]) continue;
+    const size_t F = (size_t)g.face_size(mu);
+    double* recv = w.face_recv + 48 * first * force::GROUP;
+    gr.face[mu] = recv; gr.F[mu] = (int)F;
+    hipLaunchKernelGGL(face_spinor_pack_multi_kernel, dim3((unsigned)((24 * F + 255) / 256), (unsigned)pr.n), dim3(256), 0, st, w.face_send.get(), pr,
+                       (size_t)g.V, w.face_sites + first, F);
+    DDAMG_HIP_CHECK(hipGetLastError());
+    comm_sendrecv_device(comm, w.face_send, g.neighbor_rank[4 + mu], recv, g.neighbor_rank[mu], sizeof(double) * 48 * F * (size_t)pr.n, 140 + mu, st);
     first += F;
   }
   return gr;
@@ -241,6 +279,58 @@ void force_bilinear_grid(const FineOp<double>& op, const Geometry& geom, Comm* c
     clover_derivative_extended(geom.L, w.links->Ue, w.Ae, gr.shell, slots, g.V, st);
   }
   assemble(force_dev, slots, g.V, clover, true, coeff, accumulate, st);
+}
+
+ForceMulti force_multi_begin(const FineOp<double>& op, const Geometry& geom, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd,
+                             ForceWork& w, hipStream_t st) {
+  ForceMulti m;
+  m.sites = sites_of(op, lex, csw, scale_even, scale_odd);
+  m.clover = csw != 0.0;
+  m.distributed = geom.distributed();
+  for (int mu = 0; mu < 4; mu++) { m.grid.face[mu] = nullptr; m.grid.F[mu] = 0; }
+  m.grid.shell = fs::Shell{};
+  if (m.distributed) {
+    DDAMG_REQUIRE(comm != nullptr, "the force on a process grid needs a transport");
+    grid_work(w, geom, st);
+  }
+  m.W = export_links(op, m.sites, w, st);
+  m.slots = work(w.slots, (size_t)4 * force::SLOTS * 9 * m.sites.V);
+  if (m.distributed) {
+    if (m.clover) w.links->fill(geom, comm, m.W, 0, st);   // no sign: it is in W
+    m.A = m.clover ? w.Ae.get() : nullptr;
+  } else {
+    m.A = m.clover ? work(w.A, 54 * m.sites.V) : nullptr;
+  }
+  return m;
+}
+
+void force_multi_group(ForceMulti& m, const Geometry& geom, Comm* comm, int n, const double* const* y, const double* const* x, const double* weights,
+                       ForceWork& w, hipStream_t st) {
+  DDAMG_REQUIRE(n >= 1 && n <= force::GROUP, "force_multi_group: 1 .. force::GROUP pairs");
+  force::Pairs pr;
+  for (int k = 0; k < force::GROUP; k++) { pr.x[k] = k < n ? x[k] : nullptr; pr.y[k] = k < n ? y[k] : nullptr; pr.w[k] = k < n ? weights[k] : 0.0; }
+  pr.n = n; pr.add = m.groups > 0;
+  const force::Sites& g = m.sites;
+  const dim3 sites((unsigned)((g.V + 127) / 128)), links((unsigned)((g.V + 127) / 128), 4);
+  const force::Gammas gm = force::make_gammas();
+  if (m.distributed) m.grid = exchange_face_spinors_multi(geom, comm, pr, w, st);
+  if (m.clover) hipLaunchKernelGGL(force_planes_multi_kernel, sites, dim3(128), 0, st, g, gm, pr, m.A, (int)m.distributed, m.grid);
+  hipLaunchKernelGGL(force_hop_multi_kernel, links, dim3(128), 0, st, g, gm, pr, m.W, m.slots, (int)m.distributed, m.grid);
+  DDAMG_HIP_CHECK(hipGetLastError());
+  m.groups++;
+}
+
+void force_multi_end(ForceMulti& m, const Geometry& geom, Comm* comm, double coeff, int accumulate, double* force_dev, ForceWork& w, hipStream_t st) {
+  DDAMG_REQUIRE(m.groups > 0, "force_multi_end: no group of pairs");
+  if (m.clover) {
+    if (m.distributed) {
+      exchange_tensor_shell(geom, comm, w, st);
+      clover_derivative_extended(geom.L, w.links->Ue, w.Ae, w.links->shell, m.slots, m.sites.V, st);
+    } else {
+      clover_derivative(geom.L, m.W, m.A, m.slots, m.sites.V, st);
+    }
+  }
+  assemble(force_dev, m.slots, m.sites.V, m.clover, true, coeff, accumulate, st);
 }
 
 void force_logdet_grid(const FineOp<double>& op, const Geometry& geom, Comm* comm, const int* lex, double csw, double scale_even, double scale_odd, int par,

@@ -572,6 +572,44 @@ int ddamg_hip_force_logdet(ddamg_hip_ctx* ctx, double* force_dev, int parity, do
 int ddamg_hip_force_bilinear_vec_grid(ddamg_hip_ctx* ctx, double* force_dev, const ddamg_hip_vec* y, const ddamg_hip_vec* x, double coeff, int accumulate);
 int ddamg_hip_force_bilinear_device_grid(ddamg_hip_ctx* ctx, double* force_dev, const double* y_dev, const double* x_dev, double coeff, int accumulate);
 int ddamg_hip_force_logdet_grid(ddamg_hip_ctx* ctx, double* force_dev, int parity, double coeff, int accumulate);
+/* Many pairs in one pass:  force_dev (+)= coeff * sum_s weights[s] * G(Y_s, X_s),  G the bilinear force of ddamg_hip_force_bilinear_*.
+ * Everything behind the site tensor A_p(x) and the hopping matrices is linear in them, and both are sums of outer products X Y^dagger:
+ * the links are exported once, the tensor stage accumulates over the pairs in groups of DDAMG_HIP_FORCE_GROUP per launch, and the
+ * clover derivative and the assembly run once -- what a rational approximation, a Hasenbusch chain or several pseudofermion fields on
+ * one operator need.  The sum runs over s in ascending order with one writer per number and no atomics: two calls give the same bits,
+ * _vec and _device give the same bits.  Against the loop of single calls with coeff * weights[s] the result agrees to rounding, not in
+ * its bits.  Definitions, layouts, coeff / accumulate, "the calls wait for their result" and the refusals are those of
+ * ddamg_hip_force_bilinear_* (the plain forms refuse a process grid and name their _grid twins); refused besides: npairs / nshift
+ * outside 1 .. DDAMG_HIP_MAX_FORCE_PAIRS; a null array or entry (except x_o_dev, below); a weight that is not finite; any input that
+ * overlaps force_dev; for the rational form odd local extents.  Inputs may repeat: one vector may be the x of two pairs.
+ * _vec reads the vectors where they are.  _device converts the lexicographic arrays group by group into a workspace of
+ * 2 DDAMG_HIP_FORCE_GROUP full vectors, kept in the context from the first call on.
+ * The _grid forms are COLLECTIVE as the _grid calls above.  Messages per split direction and call: 2 (link shell) + 2 (tensor shell),
+ * only with a clover term, and ceil(npairs / DDAMG_HIP_FORCE_GROUP) for the face spinors -- X and Y of all pairs of a group in one
+ * message of 384 bytes per face site and pair -- where the loop of single calls sends 5 npairs.  Everything a process can check by
+ * itself is refused before the first message.  On a context that is not divided they are the plain calls, bit for bit. */
+enum { DDAMG_HIP_MAX_FORCE_PAIRS = 32, DDAMG_HIP_FORCE_GROUP = 8 };
+int ddamg_hip_force_bilinear_multi_vec(ddamg_hip_ctx* ctx, double* force_dev, int npairs, const ddamg_hip_vec* const* y, const ddamg_hip_vec* const* x,
+                                       const double* weights, double coeff, int accumulate);
+int ddamg_hip_force_bilinear_multi_device(ddamg_hip_ctx* ctx, double* force_dev, int npairs, const double* const* y_dev, const double* const* x_dev,
+                                          const double* weights, double coeff, int accumulate);
+int ddamg_hip_force_bilinear_multi_vec_grid(ddamg_hip_ctx* ctx, double* force_dev, int npairs, const ddamg_hip_vec* const* y, const ddamg_hip_vec* const* x,
+                                            const double* weights, double coeff, int accumulate);
+int ddamg_hip_force_bilinear_multi_device_grid(ddamg_hip_ctx* ctx, double* force_dev, int npairs, const double* const* y_dev, const double* const* x_dev,
+                                               const double* weights, double coeff, int accumulate);
+/* The rational force:  force_dev (+)= coeff * sum_s rho[s] * G(Y_s, X_s)  with  X_s = (x_s, -D_oo^-1 D_oe x_s)  and
+ * Y_s = (Dhat x_s, -gamma5 D_oo^-1 D_oe gamma5 Dhat x_s):  the derivative of  sum_s rho_s phi^dagger (Dhat^dagger Dhat + sigma_s)^-1 phi  for
+ * coeff = -2, the loop of ddamg_hip_schur_apply_device, ddamg_hip_schur_odd_part_device, four ddamg_hip_vec_upload_parity_device and
+ * ddamg_hip_force_bilinear_vec(-2 rho_s) per shift in one call.  x_e_dev[s]: half fields of the even sites in device memory, as
+ * ddamg_hip_solve_schur_multishift_device returns them.  x_o_dev NULL, or entries NULL: the odd part is computed inside (as
+ * ddamg_hip_schur_odd_part_device does, with its bits); else it is taken as given.  X_s and Y_s are built group by group with the
+ * functions behind those calls, without a lexicographic round trip, so Y_s has the bits of the loop's Y_s.  Memory: the workspace of
+ * 2 DDAMG_HIP_FORCE_GROUP full vectors of the _device form plus the two of ddamg_hip_schur_apply, kept in the context from the first
+ * call on.  On a process grid the Schur applications are collective as they are on their own. */
+int ddamg_hip_force_rational_device(ddamg_hip_ctx* ctx, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
+                                    const double* const* x_o_dev, double coeff, int accumulate);
+int ddamg_hip_force_rational_device_grid(ddamg_hip_ctx* ctx, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
+                                         const double* const* x_o_dev, double coeff, int accumulate);
 
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
