@@ -22,7 +22,8 @@ cm_block_minres_op_kernel cannot be reached through the library.)"""
 import numpy as np
 import pytest
 from conftest import relerr, random_su3, splitmix_uniform
-from coarse_reference import IntegerOperator, pack
+from coarse_reference import IntegerOperator
+from coarse_schwarz_reference import random_operator     # well conditioned: MinRes on a Schwarz block never meets its eps guard
 from ddalphaamg_amd import api
 import ddalphaamg_amd as dd
 
@@ -248,26 +249,6 @@ def test_dof_counts_the_matrix_cores_do_not_cover_are_refused(nv):
 
 
 # ---- 2. the intermediate level: three-level contexts, n = 8, 16, ..., 64 ------------------------------------------------
-def random_operator(n, Lc, seed):
-    """well conditioned, so that MinRes on a Schwarz block never meets its eps guard: self coupling 4 + 0.3 H with H Hermitian of
-    unit-size entries in A and D, B = 0.3 x random, links 0.5 / sqrt(n) x random; in the storage of set_coarse_operator"""
-    rng = np.random.default_rng(seed)
-    V = int(np.prod(Lc)); N = n // 2
-
-    def unit(*shape):
-        return rng.uniform(-1, 1, size=shape) + 1j * rng.uniform(-1, 1, size=shape)
-
-    def hermitian():
-        up = np.triu(unit(V, N, N), 1)
-        return up + up.conj().transpose(0, 2, 1) + np.eye(N) * rng.uniform(-1, 1, size=(V, N, 1))
-
-    M0 = np.zeros((V, n, n), dtype=complex)
-    B = 0.3 * unit(V, N, N)
-    M0[:, :N, :N] = 4 * np.eye(N) + 0.3 * hermitian(); M0[:, N:, N:] = 4 * np.eye(N) + 0.3 * hermitian()
-    M0[:, :N, N:] = B; M0[:, N:, :N] = -B.conj().transpose(0, 2, 1)
-    return pack(M0, 0.5 / np.sqrt(n) * unit(V, 4, n, n), Lc)
-
-
 class Intermediate(Level):
     def __init__(self, nv0):
         super().__init__(three_level_ctx(nv0), 1, L1, seed=2000 + nv0)
