@@ -192,6 +192,12 @@ def load_library():
         "ddamg_hip_force_bilinear_multi_device_grid": [vp, dp, ctypes.c_int, ctypes.POINTER(dp), ctypes.POINTER(dp), dp, ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_rational_device": [vp, dp, ctypes.c_int, dp, ctypes.POINTER(dp), ctypes.POINTER(dp), ctypes.c_double, ctypes.c_int],
         "ddamg_hip_force_rational_device_grid": [vp, dp, ctypes.c_int, dp, ctypes.POINTER(dp), ctypes.POINTER(dp), ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_gauge_loops_device": [vp, dp, dp, dp],
+        "ddamg_hip_gauge_force_device": [vp, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_links_update_device": [vp, dp, dp, ctypes.c_double],
+        "ddamg_hip_links_reunitarize_device": [vp, dp, dp],
+        "ddamg_hip_momentum_update_device": [vp, dp, dp, ctypes.c_double],
+        "ddamg_hip_momentum_kinetic_device": [vp, dp, dp],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -1063,6 +1069,50 @@ class Context:
         _check(self._lib.ddamg_hip_force_logdet_grid(self._h, _dev(force_dev, self.volume(0) * 72, "force_logdet_grid"), int(parity), float(coeff),
                                                      int(bool(accumulate))))
         return force_dev
+
+    # ---- the gauge sector of the molecular dynamics (include/ddamg_hip.h, "Gauge sector"): fields are [V][4][9] complex float64 in
+    # device memory, links without the anti-periodic sign; not on a process grid ----
+    def gauge_loops_device(self, links_dev, rectangles=True):
+        """(sum_x sum_{mu<nu} Re tr P, sum_x sum_{mu!=nu} Re tr R) of the links; rectangles=False: the rectangles are not computed
+        and None stands in their place.  S = beta [c0 (6 V - plaquettes / 3) + c1 (12 V - rectangles / 3)], c0 = 1 - 8 c1"""
+        plaq, rect = ctypes.c_double(0), ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_gauge_loops_device(self._h, _dev(links_dev, self.volume(0) * 72, "gauge_loops_device"), ctypes.byref(plaq),
+                                                      ctypes.byref(rect) if rectangles else None))
+        return plaq.value, (rect.value if rectangles else None)
+
+    def gauge_force_device(self, force_dev, links_dev, beta, c1=0.0, coeff=1.0, accumulate=False):
+        """force_dev (+)= coeff * the force of the gauge action (beta, c1: 0 Wilson, -1/12 Symanzik, -0.331 Iwasaki).  Returns force_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_gauge_force_device(self._h, _dev(force_dev, n, "gauge_force_device"), _dev(links_dev, n, "gauge_force_device"),
+                                                      float(beta), float(c1), float(coeff), int(bool(accumulate))))
+        return force_dev
+
+    def links_update_device(self, links_dev, mom_dev, eps):
+        """U <- exp(eps P) U in place.  Returns links_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_links_update_device(self._h, _dev(links_dev, n, "links_update_device"), _dev(mom_dev, n, "links_update_device"),
+                                                       float(eps)))
+        return links_dev
+
+    def links_reunitarize_device(self, links_dev):
+        """every link projected back to SU(3) in place (Gram-Schmidt on the first two rows, the third their conjugated cross product).
+        Returns the largest |U U^dagger - 1| before the projection"""
+        dev = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_links_reunitarize_device(self._h, _dev(links_dev, self.volume(0) * 72, "links_reunitarize_device"), ctypes.byref(dev)))
+        return dev.value
+
+    def momentum_update_device(self, mom_dev, force_dev, eps):
+        """P <- P + eps F.  Returns mom_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_momentum_update_device(self._h, _dev(mom_dev, n, "momentum_update_device"), _dev(force_dev, n, "momentum_update_device"),
+                                                          float(eps)))
+        return mom_dev
+
+    def momentum_kinetic_device(self, mom_dev):
+        """1/2 sum |P_ij|^2"""
+        kin = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_momentum_kinetic_device(self._h, _dev(mom_dev, self.volume(0) * 72, "momentum_kinetic_device"), ctypes.byref(kin)))
+        return kin.value
 
     def _force_multi_call(self, name, force_dev, ys, xs, weights, coeff, accumulate, convert, ptr):
         n = len(weights)

@@ -1137,6 +1137,91 @@ int ddamg_hip_force_logdet_grid(ddamg_hip_ctx* c, double* force_dev, int parity,
   DDAMG_API_END
 }
 
+// ---- the gauge sector of the molecular dynamics (gauge_md.h): the context's lattice only, no operator ----
+// the way into each of the six: the device, the refusal of a process grid, and the sites of the lattice
+static size_t enter_gauge_md(const ddamg_hip_ctx* c, const char* name) {
+  enter(c);
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": refused on a process grid: the rectangle needs the neighbours' links two sites deep and the shell "
+                                   "that ddamg_hip_set_gauge_device_grid exchanges is one site deep; the _grid twins of the gauge sector are not built yet").c_str());
+  return (size_t)g.V;
+}
+static void require_finite(double v, const char* what, const char* name) {
+  DDAMG_REQUIRE(std::isfinite(v), (std::string(name) + ": " + what + " is not finite").c_str());
+}
+
+int ddamg_hip_gauge_loops_device(ddamg_hip_ctx* c, const double* links_dev, double* plaquette_sum, double* rectangle_sum) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_gauge_loops_device";
+  const size_t V = enter_gauge_md(c, name);
+  DDAMG_REQUIRE(plaquette_sum, "null argument");
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
+  gauge_loops(c->levels[0]->geom.L, links_dev, plaquette_sum, rectangle_sum, c->gauge_md, c->stream);
+  DDAMG_API_END
+}
+
+int ddamg_hip_gauge_force_device(ddamg_hip_ctx* c, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_gauge_force_device";
+  const size_t V = enter_gauge_md(c, name);
+  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_disjoint(force_dev, links_dev, sizeof(double) * 72 * V, name);
+  require_finite(beta, "beta", name); require_finite(c1, "c1", name); require_finite(coeff, "coeff", name);
+  const size_t nslots = (size_t)4 * force::SLOTS * 9 * V;     // the plane slots of the fermion force: the same layout and size
+  if (!c->force.slots.get()) c->force.slots.alloc(nslots);
+  DDAMG_REQUIRE(c->force.slots.size() == nslots, "force workspace of another lattice");
+  gauge_force(c->levels[0]->geom.L, links_dev, beta, c1, coeff, accumulate, force_dev, c->force.slots, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_links_update_device(ddamg_hip_ctx* c, double* links_dev, const double* mom_dev, double eps) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_links_update_device";
+  const size_t V = enter_gauge_md(c, name);
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_disjoint(links_dev, mom_dev, sizeof(double) * 72 * V, name);
+  require_finite(eps, "eps", name);
+  links_update(V, links_dev, mom_dev, eps, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_links_reunitarize_device(ddamg_hip_ctx* c, double* links_dev, double* max_deviation) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_links_reunitarize_device";
+  const size_t V = enter_gauge_md(c, name);
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
+  links_reunitarize(V, links_dev, max_deviation, c->gauge_md, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_momentum_update_device(ddamg_hip_ctx* c, double* mom_dev, const double* force_dev, double eps) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_momentum_update_device";
+  const size_t V = enter_gauge_md(c, name);
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name);
+  ddamg_require_disjoint(mom_dev, force_dev, sizeof(double) * 72 * V, name);
+  require_finite(eps, "eps", name);
+  momentum_update(V, mom_dev, force_dev, eps, c->stream);
+  DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  DDAMG_API_END
+}
+
+int ddamg_hip_momentum_kinetic_device(ddamg_hip_ctx* c, const double* mom_dev, double* kinetic) {
+  DDAMG_API_BEGIN
+  const char* name = "ddamg_hip_momentum_kinetic_device";
+  const size_t V = enter_gauge_md(c, name);
+  DDAMG_REQUIRE(kinetic, "null argument");
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
+  *kinetic = momentum_kinetic(V, mom_dev, c->gauge_md, c->stream);
+  DDAMG_API_END
+}
+
 int ddamg_hip_get_site_order(ddamg_hip_ctx* c, int level, int* lex_of_site) {
   DDAMG_API_BEGIN
   DDAMG_REQUIRE(c, "null context");   // host tables only: no device is selected

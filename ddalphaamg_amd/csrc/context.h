@@ -9,6 +9,7 @@
 #include "bicgstab.h"
 #include "eo_system.h"
 #include "force.h"
+#include "gauge_md.h"
 #include "multishift.h"
 #include "../../include/ddamg_hip.h"
 #include <vector>
@@ -113,6 +114,9 @@ struct ddamg_hip_ctx : ddamg_hip_ctx_handles {
   ddamg::EoWork eo;
   // the fermion force (ddamg_hip_force_*): links, site tensors and per-plane parts, from the first use on
   ddamg::ForceWork force;
+  // the gauge sector (ddamg_hip_gauge_*, ddamg_hip_links_*, ddamg_hip_momentum_*): the partial sums of its reductions, from the first use on;
+  // the plane slots of the gauge force are force.slots
+  ddamg::GaugeMdWork gauge_md;
   // multi-shift CG on Dhat^dagger Dhat + sigma_s (ddamg_hip_solve_schur_multishift_*): the loop's reduction workspace and the list of
   // even sites, from the first use on; the vectors of a solve live for the call
   ddamg::MultishiftWork ms;

@@ -611,6 +611,48 @@ int ddamg_hip_force_rational_device(ddamg_hip_ctx* ctx, double* force_dev, int n
 int ddamg_hip_force_rational_device_grid(ddamg_hip_ctx* ctx, double* force_dev, int nshift, const double* rho, const double* const* x_e_dev,
                                          const double* const* x_o_dev, double coeff, int accumulate);
 
+/* ---- Gauge sector: gauge action, its force, and the link and momentum updates of the molecular dynamics ------------------------
+ * With these six calls a pure-gauge trajectory runs on the device with no kernel of the caller's; a dynamical one adds the fermion
+ * forces above into the same force_dev and needs only the caller's random numbers.
+ * Links U are the caller's: [V][4][9] complex fp64, lexicographic T,Z,Y,X with X fastest, directions T,Z,Y,X, in device memory,
+ * WITHOUT the anti-periodic sign.  Every closed loop crosses the time boundary an even number of times, so the gauge action of U
+ * and of the operator's W are the same number and there is no anti_pbc argument.
+ * Action.  P_mu_nu(x) is the plaquette, R_mu_nu(x) the rectangle with two steps along mu and one along nu:
+ *     S_g = beta sum_x [ c0 sum_{mu<nu} (1 - 1/3 Re tr P_mu_nu(x)) + c1 sum_{mu!=nu} (1 - 1/3 Re tr R_mu_nu(x)) ],    c0 = 1 - 8 c1,
+ * 6 plaquettes and 12 rectangles per site.  c1 = 0 is the Wilson action, -1/12 tree-level Symanzik (Luescher-Weisz), -0.331 Iwasaki.
+ * Force.  The convention of "Forces" above: under U_mu(x) -> exp(eps Omega_mu(x)) U_mu(x),  d/d eps S = sum tr(Omega_mu(x) G_mu(x)),
+ *     G = TA(M),   M_mu(x) = -(beta/3) U_mu(x) [ c0 sum(6 plaquette staples) + c1 sum(18 rectangle staples) ].
+ * A staple is the rest of a closed loop that starts with the link.  Per nu != mu there are
+ * two plaquette staples and six rectangle staples: the nu-long rectangle, the mu-long one with the link first and the mu-long one
+ * with the link second, each above and below.
+ * Momenta.  P is a field of traceless anti-Hermitian matrices in the layout of the force.  dU/dt = P U, dP/dt = G, and
+ *     H = 1/2 |P|^2 + S = -1/2 sum tr P_mu(x)^2 + S      (|P|^2 the sum of |P_ij|^2 over all links)
+ * is conserved: dS/dt = sum tr(P G) = -d/dt (-1/2 sum tr P^2).  A leapfrog step is momentum_update(eps/2, G), links_update(eps),
+ * momentum_update(eps/2, G of the new links); INTEGRATION.md, "The gauge sector and a whole trajectory".
+ *   gauge_loops        *plaquette_sum = sum_x sum_{mu<nu} Re tr P, *rectangle_sum = sum_x sum_{mu!=nu} Re tr R (18 V and 36 V for unit
+ *                      links); the caller forms S for any beta and c1 from the two.  plaquette_sum / (6 V) is the plaquette that
+ *                      ddamg_hip_set_gauge_device returns.  rectangle_sum may be NULL: the rectangles are then not computed.
+ *   gauge_force        force_dev (+)= coeff * G (accumulate == 0 writes, != 0 adds).  With c1 == 0 no rectangle is touched.
+ *   links_update       U <- exp(eps P) U in place; the exponential by scaling and squaring, exact to fp64 rounding at small norm,
+ *                      with degenerate eigenvalues and for |eps P| up to 10 and beyond.
+ *   links_reunitarize  row 0 normalised, row 1 orthogonalised against row 0 and normalised, row 2 = conj(row 0 x row 1).
+ *                      *max_deviation (may be NULL) = the maximum over all links of max |U U^dagger - 1| before the projection.
+ *   momentum_update    P <- P + eps F for any field F in the layout of the force.
+ *   momentum_kinetic   *kinetic = 1/2 sum |P_ij|^2.
+ * Everything is fp64; every output has exactly one writer, there are no atomics, and sums and the maximum are taken in a fixed
+ * order: two calls give the same bits.  The calls run on the context's stream and wait for their result.  They need the context's
+ * lattice only: no operator, no setup.  links_dev is read, never written, by gauge_loops and gauge_force.
+ * Refused with a message, never computed: a null context or pointer; an array that is not device memory of the context's device
+ * or is too small; outputs that overlap inputs; beta, c1, coeff or eps that are not finite; and
+ *   - a context on a process grid: all six are refused there.  The rectangle needs the neighbours' links two sites deep and the
+ *     shell that ddamg_hip_set_gauge_device_grid exchanges is one site deep; the _grid twins are not built yet. */
+int ddamg_hip_gauge_loops_device(ddamg_hip_ctx* ctx, const double* links_dev, double* plaquette_sum, double* rectangle_sum);
+int ddamg_hip_gauge_force_device(ddamg_hip_ctx* ctx, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate);
+int ddamg_hip_links_update_device(ddamg_hip_ctx* ctx, double* links_dev, const double* mom_dev, double eps);
+int ddamg_hip_links_reunitarize_device(ddamg_hip_ctx* ctx, double* links_dev, double* max_deviation);
+int ddamg_hip_momentum_update_device(ddamg_hip_ctx* ctx, double* mom_dev, const double* force_dev, double eps);
+int ddamg_hip_momentum_kinetic_device(ddamg_hip_ctx* ctx, const double* mom_dev, double* kinetic);
+
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
 int ddamg_hip_residual_history(ddamg_hip_ctx* ctx, double* history, int max_len, int* len);
