@@ -198,6 +198,12 @@ def load_library():
         "ddamg_hip_links_reunitarize_device": [vp, dp, dp],
         "ddamg_hip_momentum_update_device": [vp, dp, dp, ctypes.c_double],
         "ddamg_hip_momentum_kinetic_device": [vp, dp, dp],
+        "ddamg_hip_gauge_loops_device_grid": [vp, dp, dp, dp],
+        "ddamg_hip_gauge_force_device_grid": [vp, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int],
+        "ddamg_hip_links_update_device_grid": [vp, dp, dp, ctypes.c_double],
+        "ddamg_hip_links_reunitarize_device_grid": [vp, dp, dp],
+        "ddamg_hip_momentum_update_device_grid": [vp, dp, dp, ctypes.c_double],
+        "ddamg_hip_momentum_kinetic_device_grid": [vp, dp, dp],
         "ddamg_hip_preconditioner": [vp, dp, dp],
         "ddamg_hip_residual_history": [vp, dp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
         "ddamg_hip_get_site_order": [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
@@ -1112,6 +1118,53 @@ class Context:
         """1/2 sum |P_ij|^2"""
         kin = ctypes.c_double(0)
         _check(self._lib.ddamg_hip_momentum_kinetic_device(self._h, _dev(mom_dev, self.volume(0) * 72, "momentum_kinetic_device"), ctypes.byref(kin)))
+        return kin.value
+
+    # ---- the same six on any process grid: fields are the process's own part, [V_local][4][9].  gauge_loops, gauge_force,
+    # momentum_kinetic and (where the deviation is asked for) links_reunitarize are collective; the other two send nothing ----
+    def gauge_loops_device_grid(self, links_dev, rectangles=True):
+        """gauge_loops_device on any process grid (collective): the sums over the whole lattice, on every process.  The shell of
+        the links is two sites deep with rectangles, else one"""
+        plaq, rect = ctypes.c_double(0), ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_gauge_loops_device_grid(self._h, _dev(links_dev, self.volume(0) * 72, "gauge_loops_device_grid"), ctypes.byref(plaq),
+                                                           ctypes.byref(rect) if rectangles else None))
+        return plaq.value, (rect.value if rectangles else None)
+
+    def gauge_force_device_grid(self, force_dev, links_dev, beta, c1=0.0, coeff=1.0, accumulate=False):
+        """gauge_force_device on any process grid (collective); the bits of the undivided lattice's force.  Returns force_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_gauge_force_device_grid(self._h, _dev(force_dev, n, "gauge_force_device_grid"),
+                                                           _dev(links_dev, n, "gauge_force_device_grid"), float(beta), float(c1), float(coeff),
+                                                           int(bool(accumulate))))
+        return force_dev
+
+    def links_update_device_grid(self, links_dev, mom_dev, eps):
+        """links_update_device on any process grid; nothing is sent.  Returns links_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_links_update_device_grid(self._h, _dev(links_dev, n, "links_update_device_grid"),
+                                                            _dev(mom_dev, n, "links_update_device_grid"), float(eps)))
+        return links_dev
+
+    def links_reunitarize_device_grid(self, links_dev, deviation=True):
+        """links_reunitarize_device on any process grid.  deviation=True (collective; every process must pass it alike): returns the
+        largest |U U^dagger - 1| of the whole lattice before the projection; False: nothing is sent and None is returned"""
+        dev = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_links_reunitarize_device_grid(self._h, _dev(links_dev, self.volume(0) * 72, "links_reunitarize_device_grid"),
+                                                                 ctypes.byref(dev) if deviation else None))
+        return dev.value if deviation else None
+
+    def momentum_update_device_grid(self, mom_dev, force_dev, eps):
+        """momentum_update_device on any process grid; nothing is sent.  Returns mom_dev"""
+        n = self.volume(0) * 72
+        _check(self._lib.ddamg_hip_momentum_update_device_grid(self._h, _dev(mom_dev, n, "momentum_update_device_grid"),
+                                                               _dev(force_dev, n, "momentum_update_device_grid"), float(eps)))
+        return mom_dev
+
+    def momentum_kinetic_device_grid(self, mom_dev):
+        """momentum_kinetic_device on any process grid (collective): 1/2 sum |P_ij|^2 over the whole lattice, on every process"""
+        kin = ctypes.c_double(0)
+        _check(self._lib.ddamg_hip_momentum_kinetic_device_grid(self._h, _dev(mom_dev, self.volume(0) * 72, "momentum_kinetic_device_grid"),
+                                                                ctypes.byref(kin)))
         return kin.value
 
     def _force_multi_call(self, name, force_dev, ys, xs, weights, coeff, accumulate, convert, ptr):

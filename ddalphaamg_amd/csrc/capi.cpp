@@ -1138,87 +1138,184 @@ int ddamg_hip_force_logdet_grid(ddamg_hip_ctx* c, double* force_dev, int parity,
 }
 
 // ---- the gauge sector of the molecular dynamics (gauge_md.h): the context's lattice only, no operator ----
-// the way into each of the six: the device, the refusal of a process grid, and the sites of the lattice
-static size_t enter_gauge_md(const ddamg_hip_ctx* c, const char* name) {
+// the way into each of the twelve: the device, the refusal of a process grid by the plain forms (grid == false; the _grid twins take
+// any context), and the sites of the local lattice.  `name` is the plain call's; name_of adds the suffix
+static std::string name_of(const char* name, bool grid) { return std::string(name) + (grid ? "_grid" : ""); }
+static size_t enter_gauge_md(const ddamg_hip_ctx* c, const char* name, bool grid) {
   enter(c);
   const Geometry& g = c->levels[0]->geom;
-  DDAMG_REQUIRE(!g.distributed(), (std::string(name) + ": refused on a process grid: the rectangle needs the neighbours' links two sites deep and the shell "
-                                   "that ddamg_hip_set_gauge_device_grid exchanges is one site deep; the _grid twins of the gauge sector are not built yet").c_str());
+  DDAMG_REQUIRE(grid || !g.distributed(), (std::string(name) + ": refused on a process grid: the loops and the force need the neighbours' links (two sites deep "
+                                           "with rectangles) and the sums run over all processes, so the call is collective there; this non-collective form "
+                                           "is not built yet for a process grid: use " + name + "_grid there").c_str());
   return (size_t)g.V;
 }
-static void require_finite(double v, const char* what, const char* name) {
-  DDAMG_REQUIRE(std::isfinite(v), (std::string(name) + ": " + what + " is not finite").c_str());
+static void require_finite(double v, const char* what, const std::string& name) {
+  DDAMG_REQUIRE(std::isfinite(v), (name + ": " + what + " is not finite").c_str());
+}
+// what a collective call of the gauge sector asks of a divided context, before the first message: a transport, and for the shell of
+// the links (depth > 0) a local lattice at least as deep as the shell in every split direction
+static void require_gauge_collective(const ddamg_hip_ctx* c, int depth, const std::string& name) {
+  const Geometry& g = c->levels[0]->geom;
+  DDAMG_REQUIRE(c->comm != nullptr, (name + " on a process grid is collective: install a transport first "
+                                     "(ddamg_hip_comm_init_rccl / ddamg_hip_comm_init_host / ddamg_hip_comm_init_mpi)").c_str());
+  for (int mu = 0; mu < 4; mu++)
+    DDAMG_REQUIRE(!g.split[mu] || g.L[mu] >= depth,
+                  (name + ": the local extent " + std::to_string(g.L[mu]) + " of the split direction " + std::to_string(mu) + " is below the depth " +
+                   std::to_string(depth) + " of the shell of the links (2 with rectangles): the shell comes from one neighbour").c_str());
 }
 
+static void gauge_loops_any(ddamg_hip_ctx* c, const double* links_dev, double* plaquette_sum, double* rectangle_sum, const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  DDAMG_REQUIRE(plaquette_sum, "null argument");
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name.c_str());
+  const Geometry& g = c->levels[0]->geom;
+  if (!g.distributed()) {
+    gauge_loops(g.L, links_dev, plaquette_sum, rectangle_sum, c->gauge_md, c->stream);
+    return;
+  }
+  require_gauge_collective(c, gauge_depth(rectangle_sum != nullptr), name);
+  double sums[2] = {0.0, 0.0};
+  gauge_loops_grid(g, c->comm, links_dev, &sums[0], rectangle_sum ? &sums[1] : nullptr, c->gauge_md, c->stream);
+  comm_release_device_staging(c->comm);
+  comm_allreduce_host(c->comm, sums, rectangle_sum ? 2 : 1);
+  *plaquette_sum = sums[0];
+  if (rectangle_sum) *rectangle_sum = sums[1];
+}
 int ddamg_hip_gauge_loops_device(ddamg_hip_ctx* c, const double* links_dev, double* plaquette_sum, double* rectangle_sum) {
   DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_gauge_loops_device";
-  const size_t V = enter_gauge_md(c, name);
-  DDAMG_REQUIRE(plaquette_sum, "null argument");
-  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
-  gauge_loops(c->levels[0]->geom.L, links_dev, plaquette_sum, rectangle_sum, c->gauge_md, c->stream);
+  gauge_loops_any(c, links_dev, plaquette_sum, rectangle_sum, "ddamg_hip_gauge_loops_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_gauge_loops_device_grid(ddamg_hip_ctx* c, const double* links_local_dev, double* plaquette_sum, double* rectangle_sum) {
+  DDAMG_API_BEGIN
+  gauge_loops_any(c, links_local_dev, plaquette_sum, rectangle_sum, "ddamg_hip_gauge_loops_device", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_gauge_force_device(ddamg_hip_ctx* c, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate) {
-  DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_gauge_force_device";
-  const size_t V = enter_gauge_md(c, name);
-  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_disjoint(force_dev, links_dev, sizeof(double) * 72 * V, name);
+static void gauge_force_any(ddamg_hip_ctx* c, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate,
+                            const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_disjoint(force_dev, links_dev, sizeof(double) * 72 * V, name.c_str());
   require_finite(beta, "beta", name); require_finite(c1, "c1", name); require_finite(coeff, "coeff", name);
+  const Geometry& g = c->levels[0]->geom;
+  if (g.distributed()) require_gauge_collective(c, gauge_depth(c1 != 0.0), name);
   const size_t nslots = (size_t)4 * force::SLOTS * 9 * V;     // the plane slots of the fermion force: the same layout and size
   if (!c->force.slots.get()) c->force.slots.alloc(nslots);
   DDAMG_REQUIRE(c->force.slots.size() == nslots, "force workspace of another lattice");
-  gauge_force(c->levels[0]->geom.L, links_dev, beta, c1, coeff, accumulate, force_dev, c->force.slots, c->stream);
+  if (g.distributed()) gauge_force_grid(g, c->comm, links_dev, beta, c1, coeff, accumulate, force_dev, c->force.slots, c->gauge_md, c->stream);
+  else gauge_force(g.L, links_dev, beta, c1, coeff, accumulate, force_dev, c->force.slots, c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (g.distributed()) comm_release_device_staging(c->comm);     // the pinned staging of the host transport
+}
+int ddamg_hip_gauge_force_device(ddamg_hip_ctx* c, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate) {
+  DDAMG_API_BEGIN
+  gauge_force_any(c, force_dev, links_dev, beta, c1, coeff, accumulate, "ddamg_hip_gauge_force_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_gauge_force_device_grid(ddamg_hip_ctx* c, double* force_local_dev, const double* links_local_dev, double beta, double c1, double coeff,
+                                      int accumulate) {
+  DDAMG_API_BEGIN
+  gauge_force_any(c, force_local_dev, links_local_dev, beta, c1, coeff, accumulate, "ddamg_hip_gauge_force_device", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_links_update_device(ddamg_hip_ctx* c, double* links_dev, const double* mom_dev, double eps) {
-  DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_links_update_device";
-  const size_t V = enter_gauge_md(c, name);
-  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_disjoint(links_dev, mom_dev, sizeof(double) * 72 * V, name);
+// nothing is sent: on a grid the plain kernel on the local field
+static void links_update_any(ddamg_hip_ctx* c, double* links_dev, const double* mom_dev, double eps, const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_disjoint(links_dev, mom_dev, sizeof(double) * 72 * V, name.c_str());
   require_finite(eps, "eps", name);
   links_update(V, links_dev, mom_dev, eps, c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+int ddamg_hip_links_update_device(ddamg_hip_ctx* c, double* links_dev, const double* mom_dev, double eps) {
+  DDAMG_API_BEGIN
+  links_update_any(c, links_dev, mom_dev, eps, "ddamg_hip_links_update_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_links_update_device_grid(ddamg_hip_ctx* c, double* links_local_dev, const double* mom_local_dev, double eps) {
+  DDAMG_API_BEGIN
+  links_update_any(c, links_local_dev, mom_local_dev, eps, "ddamg_hip_links_update_device", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_links_reunitarize_device(ddamg_hip_ctx* c, double* links_dev, double* max_deviation) {
-  DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_links_reunitarize_device";
-  const size_t V = enter_gauge_md(c, name);
-  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name);
+// collective where the deviation is asked for.  The transports only sum, so the maximum travels as one slot per process in a zeroed
+// array, summed, and is taken on the host; a NaN wins, as in the kernels
+static void links_reunitarize_any(ddamg_hip_ctx* c, double* links_dev, double* max_deviation, const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  ddamg_require_device_array(c, links_dev, sizeof(double) * 72 * V, name.c_str());
+  const bool collective = c->levels[0]->geom.distributed() && max_deviation;
+  if (collective) require_gauge_collective(c, 0, name);
   links_reunitarize(V, links_dev, max_deviation, c->gauge_md, c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (collective) {
+    std::vector<double> slot((size_t)comm_size(c->comm), 0.0);
+    slot[(size_t)comm_rank(c->comm)] = *max_deviation;
+    comm_allreduce_host(c->comm, slot.data(), (int)slot.size());
+    double m = 0.0;
+    for (double v : slot) m = (v > m || v != v) ? v : m;
+    *max_deviation = m;
+  }
+}
+int ddamg_hip_links_reunitarize_device(ddamg_hip_ctx* c, double* links_dev, double* max_deviation) {
+  DDAMG_API_BEGIN
+  links_reunitarize_any(c, links_dev, max_deviation, "ddamg_hip_links_reunitarize_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_links_reunitarize_device_grid(ddamg_hip_ctx* c, double* links_local_dev, double* max_deviation) {
+  DDAMG_API_BEGIN
+  links_reunitarize_any(c, links_local_dev, max_deviation, "ddamg_hip_links_reunitarize_device", true);
   DDAMG_API_END
 }
 
-int ddamg_hip_momentum_update_device(ddamg_hip_ctx* c, double* mom_dev, const double* force_dev, double eps) {
-  DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_momentum_update_device";
-  const size_t V = enter_gauge_md(c, name);
-  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name);
-  ddamg_require_disjoint(mom_dev, force_dev, sizeof(double) * 72 * V, name);
+static void momentum_update_any(ddamg_hip_ctx* c, double* mom_dev, const double* force_dev, double eps, const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_device_array(c, force_dev, sizeof(double) * 72 * V, name.c_str());
+  ddamg_require_disjoint(mom_dev, force_dev, sizeof(double) * 72 * V, name.c_str());
   require_finite(eps, "eps", name);
   momentum_update(V, mom_dev, force_dev, eps, c->stream);
   DDAMG_HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+int ddamg_hip_momentum_update_device(ddamg_hip_ctx* c, double* mom_dev, const double* force_dev, double eps) {
+  DDAMG_API_BEGIN
+  momentum_update_any(c, mom_dev, force_dev, eps, "ddamg_hip_momentum_update_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_momentum_update_device_grid(ddamg_hip_ctx* c, double* mom_local_dev, const double* force_local_dev, double eps) {
+  DDAMG_API_BEGIN
+  momentum_update_any(c, mom_local_dev, force_local_dev, eps, "ddamg_hip_momentum_update_device", true);
   DDAMG_API_END
 }
 
+// on a grid: this process's fixed-order sum, then the sum over the processes
+static void momentum_kinetic_any(ddamg_hip_ctx* c, const double* mom_dev, double* kinetic, const char* plain, bool grid) {
+  const size_t V = enter_gauge_md(c, plain, grid);
+  const std::string name = name_of(plain, grid);
+  DDAMG_REQUIRE(kinetic, "null argument");
+  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name.c_str());
+  const bool collective = c->levels[0]->geom.distributed();
+  if (collective) require_gauge_collective(c, 0, name);
+  double k = momentum_kinetic(V, mom_dev, c->gauge_md, c->stream);
+  if (collective) comm_allreduce_host(c->comm, &k, 1);
+  *kinetic = k;
+}
 int ddamg_hip_momentum_kinetic_device(ddamg_hip_ctx* c, const double* mom_dev, double* kinetic) {
   DDAMG_API_BEGIN
-  const char* name = "ddamg_hip_momentum_kinetic_device";
-  const size_t V = enter_gauge_md(c, name);
-  DDAMG_REQUIRE(kinetic, "null argument");
-  ddamg_require_device_array(c, mom_dev, sizeof(double) * 72 * V, name);
-  *kinetic = momentum_kinetic(V, mom_dev, c->gauge_md, c->stream);
+  momentum_kinetic_any(c, mom_dev, kinetic, "ddamg_hip_momentum_kinetic_device", false);
+  DDAMG_API_END
+}
+int ddamg_hip_momentum_kinetic_device_grid(ddamg_hip_ctx* c, const double* mom_local_dev, double* kinetic) {
+  DDAMG_API_BEGIN
+  momentum_kinetic_any(c, mom_local_dev, kinetic, "ddamg_hip_momentum_kinetic_device", true);
   DDAMG_API_END
 }
 

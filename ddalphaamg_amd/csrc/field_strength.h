@@ -108,18 +108,19 @@ DDAMG_FS_HD Tile tile_of(const Planes& g, int p, int block) {
 }
 
 // ---- the lattice extended by the neighbours' links on a process grid --------------------------------------------------------
-// The own lattice plus a shell one site deep in every split direction (h[d] = 1; an unsplit direction has h[d] = 0 and keeps
-// wrapping periodically inside the process): extents E[d] = L[d] + 2 h[d], own coordinate c in [-h, L + h) stored at c + h,
-// lexicographic as the own lattice.  Same shell as gauge.cpp builds on the host.
+// The own lattice plus a shell `depth` sites deep in every split direction (h[d] = depth; an unsplit direction has h[d] = 0 and
+// keeps wrapping periodically inside the process): extents E[d] = L[d] + 2 h[d], own coordinate c in [-h, L + h) stored at c + h,
+// lexicographic as the own lattice.  Depth 1 (the leaves of Q, the plaquette staples): the same shell as gauge.cpp builds on the
+// host.  Depth 2: the rectangle staples (gauge_md.h).  A split direction needs L[d] >= depth: the shell is cut from ONE neighbour.
 struct Shell {
   int L[4], h[4], E[4];
   size_t stride[4];      // site strides of the extended array
   size_t V, Ve;          // own sites, sites of the extended array
 };
-inline Shell make_shell(const int L[4], const bool split[4]) {
+inline Shell make_shell(const int L[4], const bool split[4], int depth = 1) {
   Shell s;
   s.V = 1; s.Ve = 1;
-  for (int d = 0; d < 4; d++) { s.L[d] = L[d]; s.h[d] = split[d] ? 1 : 0; s.E[d] = L[d] + 2 * s.h[d]; s.V *= (size_t)L[d]; s.Ve *= (size_t)s.E[d]; }
+  for (int d = 0; d < 4; d++) { s.L[d] = L[d]; s.h[d] = split[d] ? depth : 0; s.E[d] = L[d] + 2 * s.h[d]; s.V *= (size_t)L[d]; s.Ve *= (size_t)s.E[d]; }
   s.stride[3] = 1; s.stride[2] = (size_t)s.E[3]; s.stride[1] = s.stride[2] * s.E[2]; s.stride[0] = s.stride[1] * s.E[1];
   return s;
 }
@@ -159,26 +160,26 @@ DDAMG_FS_HD void extend_links(const Shell& s, const double* __restrict__ U, doub
   *reinterpret_cast<Reals<W>*>(Ue + e * 72 + k) = v;
 }
 
-// One slab of the extended array: the sites with coordinate `plane` (as stored: own coordinate + h) in direction mu.  Directions
-// are exchanged in the order 0, 1, 2, 3; the slab spans the full extended range of the split directions before mu, so that what
-// was received there (the corners) travels along, and the own range of the directions after mu.
+// One slab of the extended array: the h[mu] (the shell's depth) consecutive coordinates of direction mu that start at a given one.
+// Directions are exchanged in the order 0, 1, 2, 3; the slab spans the full extended range of the split directions before mu, so
+// that what was received there (the corners) travels along, and the own range of the directions after mu.
 struct Slab {
   int mu;
-  int n[4];          // sites per direction (n[mu] = 1)
+  int n[4];          // sites per direction (n[mu] = the depth)
   int first[4];      // stored coordinate of the first one (first[mu]: set by the caller, see slab_at)
   size_t sites;
 };
 inline Slab make_slab(const Shell& s, int mu) {
   Slab b; b.mu = mu; b.sites = 1;
   for (int d = 0; d < 4; d++) {
-    if (d == mu) { b.n[d] = 1; b.first[d] = 0; }
+    if (d == mu) { b.n[d] = s.h[d]; b.first[d] = 0; }     // an unsplit mu (h = 0) has no slab: sites = 0, and no caller asks for one
     else if (d < mu) { b.n[d] = s.E[d]; b.first[d] = 0; }
     else { b.n[d] = s.L[d]; b.first[d] = s.h[d]; }
     b.sites *= (size_t)b.n[d];
   }
   return b;
 }
-// the slab at own coordinate c of direction mu: c = L - 1 and 0 are packed, -1 and L are filled from what arrived
+// the slab whose first own coordinate of direction mu is c: c = L - depth and 0 are packed, -depth and L are filled from what arrived
 inline Slab slab_at(const Shell& s, Slab b, int c) { b.first[b.mu] = c + s.h[b.mu]; return b; }
 
 // site `site` of the slab, in the slab's own lexicographic order, as a site of the extended array

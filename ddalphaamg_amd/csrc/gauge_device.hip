@@ -334,8 +334,10 @@ void ExtendedLinks::fill(const Geometry& g, Comm* comm, const double* dU, int an
     const fs::Slab slab = fs::make_slab(shell, mu);
     const unsigned blocks = (unsigned)((slab.sites * 36 + 255) / 256);
     for (int side = 0; side < 2; side++) {
-      // side 0: my slice x_mu = L-1 goes to the +mu neighbour (its x_mu = -1); side 1: x_mu = 0 to the -mu neighbour (its x_mu = L)
-      const int src_c = side == 0 ? shell.L[mu] - 1 : 0, dst_c = side == 0 ? -1 : shell.L[mu];
+      // side 0: my slices x_mu = L-h .. L-1 go to the +mu neighbour (its x_mu = -h .. -1); side 1: x_mu = 0 .. h-1 to the -mu
+      // neighbour (its x_mu = L .. L+h-1); h: the depth of the shell
+      const int h = shell.h[mu];
+      const int src_c = side == 0 ? shell.L[mu] - h : 0, dst_c = side == 0 ? -h : shell.L[mu];
       hipLaunchKernelGGL(link_slab_pack_kernel, dim3(blocks), dim3(256), 0, st, sbuf, Ue, shell, fs::slab_at(shell, slab, src_c));
       DDAMG_HIP_CHECK(hipGetLastError());
       comm_sendrecv_device(comm, sbuf, g.neighbor_rank[side == 0 ? mu : 4 + mu], rbuf, g.neighbor_rank[side == 0 ? 4 + mu : mu],

